@@ -6,14 +6,26 @@ codes) + hard_example_training + backward + 5x Adam, fp32, one process per GPU.
     python bench.py --gpus 1 --steps 20 --warmup 5
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-The LAST line of stdout (rank 0) is ONE JSON object of at most 3 KB (`headline()` below): the driver's contract keys, `roofline`
-of the kernel with the largest serial time in the step (arg-max of the per-launch HIP-event profile, measured live on the
+A plain run does only what the headline figure needs: set-up, W warm-up steps, the execution-mode calibration (`--mode auto`),
+K timed steps, the outputs of the last timed step if `--dump-outputs DIR` is given, and the result line.  `--full` adds everything
+else this script measures, each in runs of its own behind the timed region (or, for the sampled dominant kernel, inside it):
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+
+The LAST line of stdout (rank 0) is ONE JSON object of at most 3 KB (`headline()` below): the driver's contract keys (`ms_per_step`:
+wall time of one timed step) and `roofline_step` (the whole step against its floor, from `ms_per_step` alone); with `--full` also
+`roofline` of the kernel with the largest serial time in the step (arg-max of the per-launch HIP-event profile, measured live on the
 launch stream), `cpu_baseline` (the CPU oracle oracle/ref_cpu.py, a port of the reference's PyTorch-CPU path, timed on one step
 of the same workload on the host cores, N=1 only) and, at N=1, three sub-records cut down to seven numbers each: `config3_bf16`
 (BASELINE configs[2]: targeted masks, bf16), `config5_inference` (configs[4]: 192x192 volume inference) and `config4_random_masks_n1`
 (configs[3]'s masking scheme -- all three schemes randomly sampled -- on one GPU), measured by child processes running this same script.  Everything else (per-family / per-kernel rooflines, per-step times, allocation
 counters, mode calibration, the full sub-records) goes to `bench_detail.json` next to this script and, as one line prefixed
-`BENCH_DETAIL `, to stderr -- stdout carries nothing but the headline line."""
+`BENCH_DETAIL `, to stderr -- stdout carries nothing but the headline line.
+
+`--dump-outputs DIR` writes what the timed path computed in its last timed step as DIR/<name>.npy (float32 / float64): the 8 losses
+the step returns, the latent masks it drew, and every network's weights and BatchNorm buffers after its Adam update (inference: the
+label volume).  Inputs, initial weights and the host RNG streams are seeded, so runs with the same arguments start from identical
+inputs; the dropout draws of an eager step and of a graph replay differ, so pin `--mode` when two builds' outputs are compared."""
 import argparse
 import json
 import os
@@ -60,6 +72,27 @@ PROF_EVERY = 4                   # inside the timed region the dominant kernel's
 SINGLE_STREAM_STEPS = 5
 HEADLINE_MAX_BYTES = 3072        # the driver keeps the last ~8 KB of stdout and parses the last line: the headline line stays under 3 KB
 DETAIL_FILE = "bench_detail.json"
+DUMP_MAX_BYTES = 64 << 20        # --dump-outputs: all arrays together
+DUMP_SAMPLE = 1 << 20            # elements kept of an array larger than its share of DUMP_MAX_BYTES (fixed, seeded sample)
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: every array as `outdir/<name>.npy`, float64 for float64 data, float32 otherwise.  An array larger than its
+    share of DUMP_MAX_BYTES is cut to a fixed, seeded sample of DUMP_SAMPLE elements of its flattened form (same indices every run)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(arrays))
+    total = 0
+    for name, t in arrays.items():
+        a = t.detach().cpu() if isinstance(t, torch.Tensor) else torch.as_tensor(t)
+        a = a.double() if a.dtype == torch.float64 else a.float()
+        a = a.numpy()
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=min(DUMP_SAMPLE, share // a.itemsize), replace=False))
+            a = a.reshape(-1)[idx]
+        total += a.nbytes
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    assert total <= DUMP_MAX_BYTES, total
 
 
 def synthetic(n, h, w, seed, device):
@@ -255,8 +288,10 @@ def inference_main(args, device):
                                   "reference-init weights, non-trivial running statistics are not needed for timing"}}
     recs = {}
     # three calls of the same computation: the reference's arguments (chunk = 10; the engine runs the chunks as one pass, tester.COALESCE_CHUNKS:
-    # exact under eval-mode BatchNorm), the reference's literal loop of 10-slice passes, and the whole volume asked for explicitly
-    for tag, chunk, coalesce in (("reference_arguments_chunk10", 10, None), ("literal_chunk10_loop", 10, False), ("whole_volume", slices, None)):
+    # exact under eval-mode BatchNorm), the reference's literal loop of 10-slice passes, and the whole volume asked for explicitly (--full:
+    # a plain run times the first, the headline, alone)
+    forms = (("reference_arguments_chunk10", 10, None), ("literal_chunk10_loop", 10, False), ("whole_volume", slices, None))
+    for tag, chunk, coalesce in (forms if args.full else forms[:1]):
         fn = lambda: predict_volume(solver, dvol, n_iter=n_iter, chunk=chunk, coalesce=coalesce)
         for _ in range(max(2, args.warmup)):
             lab = fn()
@@ -266,6 +301,12 @@ def inference_main(args, device):
             lab = fn()
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / args.steps
+        if tag == forms[0][0] and args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"label_volume": lab})
+        assert lab.dtype == torch.uint8 and tuple(lab.shape) == (slices, size, size)
+        recs[tag] = {"value": slices / dt, "ms_per_volume": 1e3 * dt, "chunk": chunk}
+        if not args.full:
+            continue
         _ffi.prof_start("")
         for _ in range(3):
             fn()
@@ -276,8 +317,7 @@ def inference_main(args, device):
         kid, kr = max(prof.items(), key=lambda kv: kv[1]["ms"])
         ktf, kgb, pk = kr["flops"] / kr["ms"] / 1e9, kr["bytes"] / kr["ms"] / 1e6, peak_mfma_of(kid, "fp32")
         kbound = "mfma" if ktf / pk >= kgb / PEAK_HBM_GBS else "hbm"
-        recs[tag] = {"value": slices / dt, "ms_per_volume": 1e3 * dt, "chunk": chunk,
-                     "roofline": {"kernel": kid, "bound": kbound, "achieved": ktf if kbound == "mfma" else kgb, "peak": pk if kbound == "mfma" else PEAK_HBM_GBS,
+        recs[tag].update({"roofline": {"kernel": kid, "bound": kbound, "achieved": ktf if kbound == "mfma" else kgb, "peak": pk if kbound == "mfma" else PEAK_HBM_GBS,
                                   "unit": "TFLOP/s" if kbound == "mfma" else "GB/s", "frac": max(ktf / pk, kgb / PEAK_HBM_GBS), "avg_us": 1e3 * kr["ms"] / kr["launches"],
                                   "launches": int(kr["launches"]), "traffic": None,
                                   "measured": "HIP events around every launch of this id in 3 passes behind the timed region; id = arg-max of serial kernel time"},
@@ -286,12 +326,12 @@ def inference_main(args, device):
                                     "serial_conv_kernel_ms": kms},
                      "kernels_by_serial_time": [{"kernel": k, "ms_per_volume": v["ms"] / 3, "avg_us": 1e3 * v["ms"] / v["launches"],
                                                  "tflops": v["flops"] / v["ms"] / 1e9, "hbm_gbs": v["bytes"] / v["ms"] / 1e6}
-                                                for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"])[:8]]}
-        assert lab.dtype == torch.uint8 and tuple(lab.shape) == (slices, size, size)
+                                                for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"])[:8]]})
     head = recs["reference_arguments_chunk10"]
-    out.update({"value": head["value"], "ms_per_step": head["ms_per_volume"], "steps": args.steps, "warmup": args.warmup,
-                "roofline": head["roofline"], "forms": recs})
-    if not args.no_cpu_baseline:
+    out.update({"value": head["value"], "ms_per_step": head["ms_per_volume"], "steps": args.steps, "warmup": args.warmup, "forms": recs})
+    if "roofline" in head:
+        out["roofline"] = head["roofline"]
+    if args.full and not args.no_cpu_baseline:
         from oracle import ref_cpu as O
         from cooperative_training_and_latent_space_data_augmentation_amd.init import reference_init_state_dicts
         threads = args.cpu_threads or min(32, os.cpu_count())
@@ -396,6 +436,12 @@ def main():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl == RCCL; gloo only for control-flow tests)")
     ap.add_argument("--all-on-device0", action="store_true", help="test aid: every rank uses GPU 0 (needs --backend gloo)")
     ap.add_argument("--check-finite", action="store_true", help="debug aid: synchronise and check losses / weights / gradients / buffers after every step of every phase")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the dominant kernel's roofline (single-stream profiles before and "
+                         "behind the timed region, sampled events inside it in eager mode), per-family rooflines, the launch census, the "
+                         "latent-mask roofline, the CPU baselines and, at N=1, the sub-records of the other configs (child processes)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path computed in its last timed step to DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
     args = ap.parse_args()
 
     if args.masks is None:
@@ -438,7 +484,11 @@ def main():
     from cooperative_training_and_latent_space_data_augmentation_amd.solver import AdvancedTripletReconSegmentationModel
     from cooperative_training_and_latent_space_data_augmentation_amd.dist import DataParallel
 
+    import random
+    import numpy as np
     torch.manual_seed(0)                                 # identical initial weights on every rank
+    random.seed(0)                                       # (the host draws of the masking schemes: identical inputs from run to run)
+    np.random.seed(0)
     solver = AdvancedTripletReconSegmentationModel(network_type="FCN_16_standard", image_ch=1, num_classes=4,
                                                    learning_rate=1e-4, use_gpu=True, compute_dtype=args.dtype)
     if args.single_stream:
@@ -447,8 +497,6 @@ def main():
     if use_dist:
         flush_c_stdio()                                   # (the weight broadcast built the communicator: its banner goes out now)
     if use_dist:                                         # per-rank RNG streams (scheme / k / dropout / soft-noise draws), after the weight broadcast
-        import random
-        import numpy as np
         torch.manual_seed(1234 + rank)
         np.random.seed(1234 + rank)
         random.seed(1234 + rank)
@@ -517,14 +565,16 @@ def main():
             solver.two_streams = two
 
     # which kernel is `roofline.kernel`: the arg-max of serial time over the profiling ids of one step (still untimed)
+    # (--full only: a plain run records no per-launch events anywhere)
     dominant = user_filter = args.prof_filter
-    if rank == 0 and dominant is None:
+    if args.full and rank == 0 and dominant is None:
         pre = single_stream_profile(2)
         dominant = max(pre.items(), key=lambda kv: kv[1]["ms"])[0] if pre else ""
-    elif dominant is None:
+    elif args.full and dominant is None:
         single_stream_profile(2)
         dominant = ""
     args.prof_filter = dominant
+    sample_dominant = args.full and rank == 0
     fence()
     # ---- execution mode (still untimed): the step as a hipGraph replay vs Python-issued launches
     from cooperative_training_and_latent_space_data_augmentation_amd.graph import CooperativeStepGraph
@@ -561,10 +611,10 @@ def main():
                 fn()
             fence()
             return 1e3 * (time.perf_counter() - t) / n
-        if rank == 0:                                     # as in the timed region: eager steps carry the per-launch events of the
+        if sample_dominant:                               # as in the timed region: eager steps carry the per-launch events of the
             _ffi.prof_start(args.prof_filter, PROF_EVERY) # dominant kernel (the roofline figure), graph replays cannot
         calib["eager_ms"] = time_steps(eager_step)
-        if rank == 0:
+        if sample_dominant:
             _ffi.prof_stop()
         if gstep is not None:
             calib["graph_ms"] = time_steps(graph_step)
@@ -604,16 +654,18 @@ def main():
         fence()
     # launches of one step: the library's own census over one eager step (untimed; the graph replays the same launches as nodes) +
     # what ATen adds (fills / copies / cats: counted by the profiler once in tools/aten_ops_in_step.py, ~45 per step, not re-counted here)
-    n0 = _ffi.lib.ctl_launch_count()
-    eager_step()
-    fence()
-    launches_per_step = int(_ffi.lib.ctl_launch_count() - n0)
+    launches_per_step = None
+    if args.full:
+        n0 = _ffi.lib.ctl_launch_count()
+        eager_step()
+        fence()
+        launches_per_step = int(_ffi.lib.ctl_launch_count() - n0)
     phase_tm = None
     if rank == 0 and args.lib and hasattr(_ffi.lib, "ctl_debug_timing"):
         import ctypes                                     # -DCTL_TIMING variant build: per-phase cycle counters of the conv kernel
         phase_tm = (ctypes.c_ulonglong * 12)()
         _ffi.lib.ctl_debug_timing(phase_tm)               # reset
-    if rank == 0 and mode == "eager":                     # per-launch HIP events cannot be recorded inside a graph replay
+    if sample_dominant and mode == "eager":               # per-launch HIP events cannot be recorded inside a graph replay
         _ffi.prof_start(args.prof_filter, PROF_EVERY)     # (every 4th launch of the dominant kernel: ~250 samples in 20 steps)
     # per-step record: one event per step on the launch stream (no sync inside the timed region), the host's
     # issue time per step, and the caching allocator's device-allocation counter (a hipMalloc inside the region = a one-off stall)
@@ -633,9 +685,16 @@ def main():
     dt = time.perf_counter() - t0
     step_ms = sorted(step_ev[i].elapsed_time(step_ev[i + 1]) for i in range(args.steps))
     allocs_in_region = torch.cuda.memory_stats().get("num_device_alloc", 0) - alloc0
-    prof = _ffi.prof_stop() if (rank == 0 and mode == "eager") else {}
+    prof = _ffi.prof_stop() if (sample_dominant and mode == "eager") else {}
+    if args.dump_outputs and rank == 0:                  # (before anything behind the timed region steps the solver again)
+        arrays = {"losses": torch.stack([v.detach().double() for v in losses])}
+        arrays.update({f"mask_{k}": m for k, m in sorted(solver.last_masks.items()) if m is not None})
+        for k, m in solver.model.items():
+            arrays[f"weights_{k}"] = m._flat_data
+            arrays[f"bn_buffers_{k}"] = m._bflat
+        dump_outputs(args.dump_outputs, arrays)
     # kernel-quality figures: the same step on ONE stream behind the timed region (see single_stream_profile)
-    prof_all = single_stream_profile(SINGLE_STREAM_STEPS)
+    prof_all = single_stream_profile(SINGLE_STREAM_STEPS) if args.full else {}
     if user_filter:                                      # --prof-filter: report that id (exact, else substring match)
         prof_single = {k: v for k, v in prof_all.items() if k == user_filter} or {k: v for k, v in prof_all.items() if user_filter in k}
     else:                                                # the arg-max of THIS profile (the pre-region pick only chose what to sample in-region)
@@ -674,9 +733,10 @@ def main():
             "device_allocs_in_timed_region": int(allocs_in_region),
             "device_allocs_by_step": [int(b - a) for a, b in zip([alloc0] + alloc_at[:-1], alloc_at)],
             "chain_overlap": getattr(solver, "chain_overlap", None),
-            "launches_per_step": {"library": launches_per_step, "note": "kernels + stream memsets / copies enqueued by libctl_hip.so in one step "
-                                  "(ctl_launch_count); PyTorch adds ~45 fills / copies per step (tools/aten_ops_in_step.py)"},
         }
+        if launches_per_step is not None:
+            out["launches_per_step"] = {"library": launches_per_step, "note": "kernels + stream memsets / copies enqueued by libctl_hip.so in one step "
+                                        "(ctl_launch_count); PyTorch adds ~45 fills / copies per step (tools/aten_ops_in_step.py)"}
         def roofline_of(kid, rec, region_s=None, sampled_every=1):
             secs = rec["ms"] * 1e-3
             tf, gbs = rec["flops"] / secs / 1e12, rec["bytes"] / secs / 1e9
@@ -731,17 +791,17 @@ def main():
             out["kernels_by_serial_time"] = [{"kernel": k, "ms_per_step": v["ms"] / SINGLE_STREAM_STEPS, "launches_per_step": v["launches"] / SINGLE_STREAM_STEPS,
                                               "avg_us": 1e3 * v["ms"] / v["launches"]}
                                              for k, v in sorted(prof_all.items(), key=lambda kv: -kv[1]["ms"])[:16]]
-        if world == 1:
+        if world == 1 and args.full:
             out["roofline_latent_mask"] = latent_mask_roofline(device)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cb_warm, cb_steps = (int(v) for v in args.cpu_baseline_steps.split("+"))
             out["cpu_baseline"] = cpu_baseline(host_batch, args.cpu_threads or min(32, os.cpu_count()), steps=cb_steps, warm=cb_warm, cfgs=(IMG_CFG, SEG_CFG), what=mask_text)
-        if world == 1 and not args.no_cpu_baseline and not args.no_sub_records and args.dtype == "fp32" and args.masks == "dropout":
+        if world == 1 and args.full and not args.no_cpu_baseline and not args.no_sub_records and args.dtype == "fp32" and args.masks == "dropout":
             out["cpu_baselines_other_configs"] = cpu_baselines_other_configs(host_batch, args.cpu_threads or min(32, os.cpu_count()))
-        if world == 1 and not args.no_sub_records and args.dtype == "fp32" and args.masks == "dropout":
+        if world == 1 and args.full and not args.no_sub_records and args.dtype == "fp32" and args.masks == "dropout":
             # BASELINE configs[2] and configs[4], each measured by a child process running this script (a fresh process: its own
             # streams, pools and graphs; this process is idle meanwhile).  The headline keys above are untouched.
-            common = ["--steps", str(args.steps), "--warmup", str(args.warmup), "--no-sub-records", "--cpu-baseline-steps", "1+3"] + \
+            common = ["--full", "--steps", str(args.steps), "--warmup", str(args.warmup), "--no-sub-records", "--cpu-baseline-steps", "1+3"] + \
                      (["--no-cpu-baseline"] if args.no_cpu_baseline else []) + \
                      (["--lib", args.lib] if args.lib else []) + [x for kv in args.set for x in ("--set", kv)]
             # the control next to the X3 headline: the same step with every contraction on the fp32 matrix pipe

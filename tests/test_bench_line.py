@@ -47,11 +47,11 @@ def test_headline_survives_failed_sub_records_and_missing_parts():
 
 @pytest.mark.gpu
 def test_bench_last_stdout_line_is_the_small_headline(tmp_path):
-    """bench.py end to end at a small size: the last stdout line parses, is < 3 KB, carries roofline.frac and cpu_baseline.value, the
-    detail file holds the families; stdout carries nothing else."""
+    """bench.py --full end to end at a small size: the last stdout line parses, is < 3 KB, carries roofline.frac and cpu_baseline.value,
+    the detail file holds the families; stdout carries nothing else."""
     dfile = "bench_detail_test.json"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--size", "64", "--batch", "4", "--steps", "2", "--warmup", "1", "--cpu-threads", "8",
-           "--detail-file", dfile]
+           "--detail-file", dfile, "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = out.stdout.strip().splitlines()
@@ -131,3 +131,59 @@ def test_gpus_2_without_a_launcher_runs_two_ranks():
         os.remove(os.path.join(ROOT, "bench_detail_test2.json"))
     except OSError:
         pass
+
+
+def test_dump_outputs_writes_npy_within_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 / float64 .npy per array; an array over its share of the cap becomes the same seeded sample every time."""
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 3 * 4096)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 512)
+    big = torch.arange(10000, dtype=torch.float32)
+    arrays = {"losses": torch.tensor([1.0, 2.0], dtype=torch.float64), "mask": torch.tensor([True, False]), "big": big}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in arrays}
+    assert a["losses"].dtype == np.float64 and a["losses"].tolist() == [1.0, 2.0]
+    assert a["mask"].dtype == np.float32 and a["mask"].tolist() == [1.0, 0.0]
+    assert a["big"].dtype == np.float32 and a["big"].shape == (512,) and len(set(a["big"].tolist())) == 512
+    assert np.array_equal(a["big"], np.load(tmp_path / "b" / "big.npy"))
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_MAX_BYTES
+
+
+def test_full_and_dump_outputs_are_options():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert "--full" in out.stdout and "--dump-outputs" in out.stdout
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) times exactly --steps steps, prints the contract keys and none of what --full measures, and with
+    --dump-outputs writes the last timed step's losses, masks and updated weights; a second run with the same arguments starts from
+    the same inputs and ends with the same outputs."""
+    import numpy as np
+    recs, dumps = [], []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--size", "64", "--batch", "4", "--steps", "3", "--warmup", "1", "--mode", "graph",
+               "--detail-file", "bench_detail_test_plain.json", "--dump-outputs", str(tmp_path / d)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-3000:]
+        recs.append(json.loads(out.stdout.strip().splitlines()[-1]))
+        dumps.append({f[:-4]: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    os.remove(os.path.join(ROOT, "bench_detail_test_plain.json"))
+    rec = recs[0]
+    for k in CONTRACT:
+        assert k in rec, k
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["mode"] == "graph"
+    assert rec["ms_per_step"] > 0 and abs(rec["value"] - 4 * 1e3 / rec["ms_per_step"]) <= 1e-6 * rec["value"]
+    for k in ("roofline", "cpu_baseline", "config2_fp32_mfma", "config3_bf16", "config5_inference", "config4_random_masks_n1", "latent_mask_hbm_frac"):
+        assert k not in rec, k
+    a, b = dumps
+    assert a["losses"].dtype == np.float64 and a["losses"].shape == (8,) and np.isfinite(a["losses"]).all()
+    assert {"mask_image", "mask_seg"} <= set(a) and len([k for k in a if k.startswith("weights_")]) == 5
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert set(a) == set(b)
+    for k in a:
+        assert np.allclose(a[k], b[k], rtol=1e-4, atol=1e-6), k

@@ -432,7 +432,7 @@ def test_bench_two_ranks_control_flow():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29547", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--size", "64",
-           "--batch", "4", "--backend", "gloo", "--all-on-device0"]
+           "--batch", "4", "--backend", "gloo", "--all-on-device0", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     line = out.stdout.strip().splitlines()[-1]          # the driver parses the LAST line of stdout

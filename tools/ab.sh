@@ -13,7 +13,7 @@ mkdir -p $out
 for rep in $(seq 1 $reps); do
   for v in "$@"; do
     label=${v%%|*}; args=${v#*|}
-    timeout 900 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-sub-records $args > $out/${label}_$rep.json 2> $out/${label}_$rep.err
+    timeout 900 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-sub-records $args > $out/${label}_$rep.json 2> $out/${label}_$rep.err
     python3 - "$out/${label}_$rep.json" "$label" "$rep" <<'PY'
 import json, sys
 try:

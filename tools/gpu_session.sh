@@ -9,7 +9,7 @@ if [ "$tests" = "tests" ]; then
   timeout 3000 python3 -m pytest tests -m gpu -x -q > $out/pytest_gpu.log 2>&1; echo "pytest exit $?" | tee -a $out/pytest_gpu.log
   tail -5 $out/pytest_gpu.log
 fi
-timeout 1200 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err; echo "bench exit $?"
+timeout 1200 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err; echo "bench exit $?"
 cp bench_detail.json $out/bench_detail.json; cp bench_detail_config3_bf16.json bench_detail_config5_inference.json bench_detail_config4_random_masks_n1.json $out/ 2>/dev/null
 python3 - $out <<'PY'
 import json, sys

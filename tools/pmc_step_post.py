@@ -61,7 +61,7 @@ for k, cs in acc.items():
         for c, key in (("SQ_WAIT_INST_ANY", "wait_inst_frac"), ("SQ_WAIT_ANY", "wait_any_frac"), ("SQ_ACTIVE_INST_VALU", "valu_active_frac")):
             rec[key] = mean.get(c, 0.0) / mean["SQ_WAVE_CYCLES"]
     res[k] = rec
-meta = {"method": "rocprofv3 --kernel-trace --pmc <set> --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-sub-records --mode eager "
+meta = {"method": "rocprofv3 --kernel-trace --pmc <set> --output-format csv -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-sub-records --mode eager "
                   + bench_args + " ; five passes (FETCH_SIZE | WRITE_SIZE | MFMA busy | LDS + waits | instruction mix); FETCH_SIZE x 1024 x 2, WRITE_SIZE x 1024; "
                   "mfma_busy_frac = SQ_VALU_MFMA_BUSY_CYCLES / (SQ_BUSY_CYCLES / 32 shader engines x 1024 SIMDs); wait / active fractions over SQ_WAVE_CYCLES", "tag": tag}
 json.dump({"meta": meta, "kernels": res}, open(f"{out}/counters_by_kernel.json", "w"), indent=1)

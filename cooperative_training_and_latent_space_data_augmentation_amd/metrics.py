@@ -65,10 +65,55 @@ def _border(mask: np.ndarray, connectivity: int) -> np.ndarray:
     return mask ^ binary_erosion(mask, structure=generate_binary_structure(mask.ndim, connectivity), iterations=1)
 
 
+def _on_device(a, b) -> bool:
+    import torch
+    return torch.is_tensor(a) and torch.is_tensor(b) and a.is_cuda and b.is_cuda
+
+
+def _raise_if_empty(first_empty, second_empty):
+    if first_empty:
+        raise RuntimeError("The first supplied array does not contain any binary object.")
+    if second_empty:
+        raise RuntimeError("The second supplied array does not contain any binary object.")
+
+
+def _device_table(result, reference, spacing, connectivity, per_slice):
+    """ops.surface_stats of two binary device objects (non-zero = inside): table [1, 2, slices or 1, 4], side 0 = result."""
+    from . import ops
+    if result.dim() not in (2, 3) or tuple(result.shape) != tuple(reference.shape) or (per_slice and result.dim() != 3):
+        raise ValueError(f"device surface distances need two [H,W] or [D,H,W] tensors of one shape, got {tuple(result.shape)} and "
+                         f"{tuple(reference.shape)}")
+    vol = (-1,) + tuple(result.shape[-2:])
+    return ops.surface_stats((result != 0).reshape(vol), (reference != 0).reshape(vol), 2, spacing, connectivity,
+                             "2d" if (per_slice or result.dim() == 2) else "3d", foreground_only=True)
+
+
+def _hd_stack_from_table(t) -> float:
+    """t: host table [2, slices, 4] of one class in the per-slice form -> `hd_2D_stack`: slices with an empty mask are left out."""
+    vals = [float(np.sqrt(max(t[0, z, 0], t[1, z, 0]))) for z in range(t.shape[1]) if t[0, z, 3] == 0]
+    return sum(vals) / len(vals) if vals else -1
+
+
+def _asd_from_table(t) -> float:
+    """t: host table [2, 4] of one class in the whole-volume form -> `asd` result -> reference (side 1 = distances to the reference)."""
+    return float(t[1, 1] / t[1, 2]) if t[1, 3] == 0 else 1e100
+
+
+def _surface_distances_device(result, reference, voxelspacing, connectivity):
+    import torch
+    from . import ops
+    a, b = result != 0, reference != 0
+    _raise_if_empty(not bool(a.any()), not bool(b.any()))
+    return torch.sqrt(ops.edt_sq(b, voxelspacing, connectivity))[ops.surface_of(a, connectivity)]
+
+
 def surface_distances(result, reference, voxelspacing=None, connectivity=1) -> np.ndarray:
     """Distances from every surface voxel of `result` to the nearest surface voxel of `reference` (the surface-distance
     construction of medpy 0.4.0 `metric.binary`, carried by measure.py:1096-1128): surface = mask XOR its erosion, distances from
-    the Euclidean distance transform of the reference surface's complement.  Host code (scipy), as upstream."""
+    the Euclidean distance transform of the reference surface's complement.  Host code (scipy), as upstream, for host inputs; two
+    CUDA tensors give a device fp64 vector in the same (C) order from the HIP distance transform (ops.edt_sq / ops.surface_of)."""
+    if _on_device(result, reference):
+        return _surface_distances_device(result, reference, voxelspacing, connectivity)
     from scipy.ndimage import distance_transform_edt
     a, b = np.atleast_1d(np.asarray(result).astype(bool)), np.atleast_1d(np.asarray(reference).astype(bool))
     if not a.any():
@@ -81,20 +126,29 @@ def surface_distances(result, reference, voxelspacing=None, connectivity=1) -> n
 
 
 def hd(result, reference, voxelspacing=None, connectivity=1) -> float:
-    """Symmetric Hausdorff distance (measure.py:333-378)."""
+    """Symmetric Hausdorff distance (measure.py:333-378).  Two CUDA tensors ([H,W] or [D,H,W]): one fused ops.surface_stats call."""
+    if _on_device(result, reference):
+        t = _device_table(result, reference, voxelspacing, connectivity, per_slice=False)[0, :, 0].cpu().numpy()
+        _raise_if_empty(t[1, 2] == 0, t[0, 2] == 0)
+        return float(np.sqrt(max(t[0, 0], t[1, 0])))
     return max(surface_distances(result, reference, voxelspacing, connectivity).max(),
                surface_distances(reference, result, voxelspacing, connectivity).max())
 
 
 def hd_2D_stack(result, reference, pixelspacing=None, connectivity=1) -> float:
     """Mean in-plane Hausdorff distance over the slices where both masks are non-empty; -1 when there is none
-    (measure.py:381-399)."""
+    (measure.py:381-399).  Two CUDA [D,H,W] tensors: every slice and both directions in one fused ops.surface_stats call."""
+    if _on_device(result, reference):
+        return _hd_stack_from_table(_device_table(result, reference, pixelspacing, connectivity, per_slice=True)[0].cpu().numpy())
     vals = [hd(r, g, pixelspacing, connectivity) for r, g in zip(result, reference) if r.sum() > 0 and g.sum() > 0]
     return sum(vals) / len(vals) if vals else -1
 
 
 def asd(result, reference, voxelspacing=None, connectivity=1) -> float:
-    """Directed average surface distance result -> reference; 1e100 when either mask is empty (measure.py:458-548)."""
+    """Directed average surface distance result -> reference; 1e100 when either mask is empty (measure.py:458-548).  Two CUDA tensors
+    ([H,W] or [D,H,W]): one fused ops.surface_stats call."""
+    if _on_device(result, reference):
+        return _asd_from_table(_device_table(result, reference, voxelspacing, connectivity, per_slice=False)[0, :, 0].cpu().numpy())
     if np.sum(result) > 0 and np.sum(reference) > 0:
         return surface_distances(result, reference, voxelspacing, connectivity).mean()
     return 1e100
@@ -105,8 +159,9 @@ class runningMySegmentationScore(object):
 
     'Dice', 'VolError' and 'VolSim' are functions of three voxel counts per class (|pred|, |gt|, |pred & gt|); for device tensors
     those come from the confusion-matrix kernel (one launch pair and one 2*n^2-word readback per patient instead of 2*(n-1)
-    full-volume host copies and masks).  The surface-distance metrics 'HD' and 'ASD' are scipy distance transforms on the host,
-    as upstream (measure.py:333-548); asking for them brings the two label volumes to the host once per patient."""
+    full-volume host copies and masks).  The surface-distance metrics 'HD' and 'ASD' (measure.py:333-548) are, for device tensors,
+    one `ops.surface_stats` call each (exact fp64 distance transform of every class and both directions in 4 / 5 launches) and one
+    readback of their small tables per patient: no label volume leaves the device.  numpy inputs run scipy on the host, as upstream."""
     SUPPORTED = ("Dice", "VolError", "VolSim", "HD", "ASD")
 
     def __init__(self, n_classes, idx2cls_dict=None, metrics_list=("Dice",), foreground_only=False):
@@ -149,6 +204,25 @@ class runningMySegmentationScore(object):
             pc, gc, ic = np.array([0, pc[1:].sum()]), np.array([0, gc[1:].sum()]), np.array([0, fg_i])
         return pc, gc, ic
 
+    def _surface_tables(self, preds, gts, surf, voxel_spacing):
+        """{'HD': host table [classes, 2, slices, 4], 'ASD': [classes, 2, 1, 4]} of one patient from ops.surface_stats (same masks,
+        8- / 18-neighbourhood surfaces and spacing convention as the host branch of `update`); both tables come back in one copy."""
+        import torch
+        from . import ops
+        if any(c >= self.n_classes for c in self.idx2cls_dict):
+            raise ValueError("idx2cls_dict names a class outside [0, n_classes): pass host arrays")
+        tabs = {}
+        if "HD" in surf:
+            tabs["HD"] = ops.surface_stats(preds, gts, self.n_classes, voxel_spacing[:2], 2, "2d", self.foreground_only)
+        if "ASD" in surf:
+            tabs["ASD"] = ops.surface_stats(preds, gts, self.n_classes, voxel_spacing, 2, "3d", self.foreground_only)
+        flat = torch.cat([t.reshape(-1) for t in tabs.values()]).cpu().numpy()
+        out, lo = {}, 0
+        for k, t in tabs.items():
+            out[k] = flat[lo:lo + t.numel()].reshape(tuple(t.shape))
+            lo += t.numel()
+        return out
+
     def update(self, pid, preds, gts, voxel_spacing=None):
         """preds / gts: integer volumes [n_slices, H, W] (numpy, or both torch tensors on the GPU); returns the patient's row."""
         if tuple(preds.shape) != tuple(gts.shape):
@@ -162,8 +236,12 @@ class runningMySegmentationScore(object):
                 raise ValueError("'HD' / 'ASD' need the voxel spacing (x, y, z) of the volume")
             if "HD" in surf:      # metrics.py:225-229: the in-plane pair is voxel_spacing[:2]; upstream's own guard on the axis order
                 assert voxel_spacing[0] >= voxel_spacing[2], "z spacing should be in last dim in the cardiac imaging"
-            p_h = preds.detach().cpu().numpy() if hasattr(preds, "detach") else np.asarray(preds)
-            g_h = gts.detach().cpu().numpy() if hasattr(gts, "detach") else np.asarray(gts)
+            if _on_device(preds, gts):                     # one fused launch sequence per metric, ONE readback of the small tables
+                dev_tab = self._surface_tables(preds, gts, surf, voxel_spacing)
+            else:
+                dev_tab = None
+                p_h = preds.detach().cpu().numpy() if hasattr(preds, "detach") else np.asarray(preds)
+                g_h = gts.detach().cpu().numpy() if hasattr(gts, "detach") else np.asarray(gts)
         row = [str(pid)]
         for c, name in self.idx2cls_dict.items():
             if c == 0:
@@ -172,6 +250,9 @@ class runningMySegmentationScore(object):
             for m in self.metrics:
                 if m == "Dice":                            # medpy dc: ZeroDivisionError -> 0.0
                     score = 2.0 * inter / float(v1 + v2) if v1 + v2 else 0.0
+                elif m in ("HD", "ASD") and dev_tab is not None:
+                    t = dev_tab[m][0 if self.foreground_only else c - 1]
+                    score = float(_hd_stack_from_table(t) if m == "HD" else _asd_from_table(t[:, 0]))
                 elif m in ("HD", "ASD"):
                     pm = (p_h > 0) if self.foreground_only else (p_h == c)
                     gm = (g_h > 0) if self.foreground_only else (g_h == c)

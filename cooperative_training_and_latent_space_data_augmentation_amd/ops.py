@@ -5,6 +5,7 @@ PyTorch is used here only for device memory and the stream handle.  4-D activati
 """
 from __future__ import annotations
 
+import ctypes as C
 from typing import Optional
 
 import numpy as np
@@ -350,6 +351,77 @@ def confusion_hist(label_true: torch.Tensor, label_pred: torch.Tensor, n_class: 
         hist = torch.zeros((n_class, n_class), dtype=torch.int64, device=lt.device)
     check(lib.ctl_confusion_hist(ptr(lt), ptr(lp), lt.numel(), n_class, ptr(hist), stream_ptr()), "ctl_confusion_hist")
     return hist
+
+
+def _surface_mode(mode) -> int:
+    m = {2: 2, 3: 3, "2d": 2, "3d": 3, "2D": 2, "3D": 3}.get(mode)
+    if m is None:
+        raise ValueError(f"surface mode {mode!r}: '2d' (every slice on its own) or '3d' (the whole volume)")
+    return m
+
+
+def _surface_sampling(sampling, ndim: int):
+    """None, a scalar or `ndim` values in array-axis order -> a host array of `ndim` doubles (or None = unit sampling)."""
+    if sampling is None:
+        return None
+    s = np.ascontiguousarray(np.broadcast_to(np.asarray(sampling, dtype=np.float64), (ndim,)))
+    return (C.c_double * ndim)(*s.tolist())
+
+
+def surface_stats(pred: torch.Tensor, gt: torch.Tensor, n_class: int, sampling=None, connectivity: int = 1, mode="3d",
+                  foreground_only: bool = False) -> torch.Tensor:
+    """Surface-distance statistics of every foreground class and both directions of one patient (measure.py:333-548, 1096-1128 on
+    device): pred / gt are [D,H,W] label volumes.  -> fp64 device table [classes, 2, D if mode == '2d' else 1, 4]; entry [c - 1, side]
+    takes the exact Euclidean distance map of the surface of side's mask (0 = pred, 1 = gt) and samples it at the surface voxels of the
+    other side's mask: (max d^2, sum of d, number of sampled voxels, 1.0 if either mask is empty).  4 ('2d') or 5 ('3d') launches."""
+    require_gpu(pred, gt)
+    mode = _surface_mode(mode)
+    if pred.dim() != 3 or tuple(pred.shape) != tuple(gt.shape):
+        raise ValueError(f"surface_stats: expected two [D,H,W] volumes of one shape, got {tuple(pred.shape)} and {tuple(gt.shape)}")
+    p, g = pred.to(torch.uint8).contiguous(), gt.long().contiguous()
+    d, h, w = (int(v) for v in p.shape)
+    samp = _surface_sampling(sampling, mode)
+    rows = lib.ctl_surface_stats_rows(d, n_class, int(foreground_only), mode)
+    if rows < 0:
+        check(rows, "ctl_surface_stats_rows")
+    table = torch.empty((rows, 4), dtype=torch.float64, device=p.device)
+    nbytes = lib.ctl_surface_stats_ws_bytes(d, h, w, n_class, int(foreground_only), mode)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=p.device)
+    check(lib.ctl_surface_stats(ptr(p), ptr(g), d, h, w, n_class, int(foreground_only), mode, int(connectivity), samp, ptr(table), ptr(ws),
+                                nbytes, stream_ptr()), "ctl_surface_stats")
+    return table.view(-1, 2, d if mode == 2 else 1, 4)
+
+
+def _surface_map(mask: torch.Tensor, sampling, connectivity: int, per_slice: bool, want_d2: bool):
+    require_gpu(mask)
+    if mask.dim() not in (2, 3) or (per_slice and mask.dim() != 3):
+        raise ValueError(f"expected a [H,W] or [D,H,W] mask ([D,H,W] with per_slice), got {tuple(mask.shape)}")
+    mode = 2 if (mask.dim() == 2 or per_slice) else 3
+    m = (mask != 0).to(torch.uint8).reshape((-1,) + tuple(mask.shape[-2:])).contiguous()
+    d, h, w = (int(v) for v in m.shape)
+    samp = _surface_sampling(sampling, mode)
+    if want_d2:
+        out = torch.empty((d, h, w), dtype=torch.float64, device=m.device)
+        nbytes = lib.ctl_surface_map_ws_bytes(d, h, w, mode)
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=m.device)
+        check(lib.ctl_surface_map(ptr(m), d, h, w, mode, int(connectivity), samp, ptr(out), None, ptr(ws), nbytes, stream_ptr()), "ctl_surface_map")
+    else:
+        out = torch.empty((d, h, w), dtype=torch.uint8, device=m.device)
+        check(lib.ctl_surface_map(ptr(m), d, h, w, mode, int(connectivity), samp, None, ptr(out), None, 0, stream_ptr()), "ctl_surface_map")
+        out = out.bool()
+    return out.reshape(mask.shape)
+
+
+def surface_of(mask: torch.Tensor, connectivity: int = 1, per_slice: bool = False) -> torch.Tensor:
+    """`metrics._border` on device: mask XOR binary_erosion(mask, generate_binary_structure(ndim, connectivity)) as a bool tensor of
+    mask's shape ([H,W] or [D,H,W]; per_slice: every [H,W] slice of a volume on its own)."""
+    return _surface_map(mask, None, connectivity, per_slice, False)
+
+
+def edt_sq(mask: torch.Tensor, sampling=None, connectivity: int = 1, per_slice: bool = False) -> torch.Tensor:
+    """fp64 map of the SQUARED exact Euclidean distance of every voxel to the nearest voxel of `surface_of(mask, connectivity)`, i.e.
+    distance_transform_edt(~_border(mask), sampling) ** 2 (measure.py:1096-1128); +inf where the mask (of the slice) is empty."""
+    return _surface_map(mask, sampling, connectivity, per_slice, True)
 
 
 def rescale_intensity(data: torch.Tensor, new_min: float = 0.0, new_max: float = 1.0, eps: float = 1e-20) -> torch.Tensor:

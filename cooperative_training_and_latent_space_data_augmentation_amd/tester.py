@@ -91,7 +91,10 @@ class TestSegmentationNetwork(object):
     def evaluate(self, i, data_tensor_pack, total_number, maximum_batch_size=10, coalesce=None):
         """One patient: `predict` over the volume, device arg-max into one uint8 volume, metric update from the device tensors.
         maximum_batch_size = 10 is upstream's default argument (a GPU-memory workaround); the chunks it asks for are run as one pass
-        (tester.COALESCE_CHUNKS, exact: see predict_volume; 2x the slices/s on a 40-slice volume); coalesce=False: the literal loop."""
+        (tester.COALESCE_CHUNKS, exact: see predict_volume; 2x the slices/s on a 40-slice volume); coalesce=False: the literal loop.
+        The metric update reads back only small tables (voxel counts, and for 'HD' / 'ASD' the per-slice / per-class surface statistics
+        of ops.surface_stats), so with keep_results=False and save_soft_prediction=False a patient is scored without any full-volume
+        device-to-host copy."""
         dev = torch.device("cuda", torch.cuda.current_device())
         image = data_tensor_pack["image"]
         if image.dim() == 5:                              # DataLoader(batch_size=1) adds a leading axis upstream

@@ -375,6 +375,41 @@ int ctl_noise_clamp(const float* x, const float* noise, uint64_t seed, float sig
 int ctl_crop_or_pad(const void* src, void* dst, int32_t elem_bytes, int32_t n, int32_t h, int32_t w, int32_t new_h,
                     int32_t new_w, ctl_stream stream);
 
+/* ------------------------------------------------------------------------------------------------ surface distances
+ * 'HD' / 'ASD' of the patient score table (medseg/common_utils/metrics.py:224-230) = medpy 0.4.0 `hd` / `asd` as carried by
+ * medseg/common_utils/measure.py:333-548 on the surface-distance construction of measure.py:1096-1128, which upstream runs on
+ * the host per class, per direction and (HD) per slice: scipy binary_erosion + distance_transform_edt.  Here, for EVERY class and
+ * BOTH directions of one patient in 4 (mode 2) or 5 (mode 3) kernel launches, whatever D, H, W and n_class are:
+ *   masks     class c (1 <= c < n_class): pred == c and gt == c; foreground_only: pred > 0 and gt > 0 (one class).  pred is uint8
+ *             [D,H,W] (as written by ctl_argmax_c), gt int64 [D,H,W]; a gt label outside [0, n_class) belongs to no class.
+ *   surface   mask XOR erosion(mask), scipy defaults: border_value 0 (a mask voxel on the edge of the array is a surface voxel),
+ *             structuring element generate_binary_structure(mode, connectivity) = the neighbours at L1 offset <= connectivity.
+ *   mode      2: every [H,W] slice on its own (`hd_2D_stack`), sampling = {s_y, s_x};  3: the volume, sampling = {s_z, s_y, s_x};
+ *             `sampling` is a HOST array in array-axis order, read during the call, NULL = 1; 1 <= connectivity <= mode.
+ *   distance  EXACT Euclidean distance to the nearest surface voxel of the other mask: separable lower envelope evaluated over all
+ *             candidates of a row / column / slice axis in fp64 (no window, no chamfer, no jump flooding); with unit sampling every
+ *             squared distance is an exact integer.
+ *   table     fp64 [rows][4], row = (class_index * 2 + side) * (mode == 2 ? D : 1) + (mode == 2 ? z : 0), class_index = c - 1,
+ *             rows as ctl_surface_stats_rows says.  Row (c, side) takes the distance map of the surface of side's mask (0 = pred,
+ *             1 = gt) and samples it at the surface voxels of the OTHER side's mask: {max d^2, sum of d, number of sampled voxels,
+ *             1.0 if either mask (of this slice, mode 2) is empty else 0.0}.  With an empty target mask d is +inf.
+ *             HD of a slice = sqrt(max of the two sides' max d^2); ASD(pred -> gt) = sum / number of row (c, 1).
+ *             Sums are per-block partials combined in a fixed order: no floating-point atomics, identical bits on every call.
+ * ctl_surface_map: the same passes for ONE mask (uint8, non-zero = inside): d2_out (fp64 [D,H,W], may be NULL) = squared distance of
+ *   every voxel to the nearest surface voxel of the mask (+inf when there is none), surface_out (uint8 [D,H,W] of 0 / 1, may be NULL) =
+ *   the surface map itself; 1 to 4 launches.  The workspace is needed only with d2_out.
+ * Workspaces are caller-owned, sized by the *_ws_bytes queries (0 for arguments the call itself would refuse) and need 256-byte
+ * alignment.  Every axis is limited to 65534 elements. */
+int32_t ctl_surface_stats_rows(int32_t d, int32_t n_class, int32_t foreground_only, int32_t mode);
+size_t ctl_surface_stats_ws_bytes(int32_t d, int32_t h, int32_t w, int32_t n_class, int32_t foreground_only, int32_t mode);
+int ctl_surface_stats(const uint8_t* pred, const int64_t* gt, int32_t d, int32_t h, int32_t w, int32_t n_class,
+                      int32_t foreground_only, int32_t mode, int32_t connectivity, const double* sampling, double* table,
+                      void* workspace, size_t workspace_bytes, ctl_stream stream);
+size_t ctl_surface_map_ws_bytes(int32_t d, int32_t h, int32_t w, int32_t mode);
+int ctl_surface_map(const uint8_t* mask, int32_t d, int32_t h, int32_t w, int32_t mode, int32_t connectivity,
+                    const double* sampling, double* d2_out, uint8_t* surface_out, void* workspace, size_t workspace_bytes,
+                    ctl_stream stream);
+
 /* ------------------------------------------------------------------------------------------------ optimizer
  * torch.optim.Adam defaults (model.py:774-785), one flat buffer: p,g,m,v [count].  step = 1-based step index.
  * grad_scale folds the 1/world_size of the data-parallel all-reduce. */

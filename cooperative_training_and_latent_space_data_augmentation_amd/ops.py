@@ -424,6 +424,50 @@ def edt_sq(mask: torch.Tensor, sampling=None, connectivity: int = 1, per_slice: 
     return _surface_map(mask, sampling, connectivity, per_slice, True)
 
 
+def _cc_volume(labelmap: torch.Tensor, per_slice: bool, who: str):
+    """A [H,W] or [D,H,W] uint8 device label map -> (contiguous [D,H,W] view, D, H, W, mode)."""
+    require_gpu(labelmap)
+    if labelmap.dtype != torch.uint8:
+        raise TypeError(f"{who}: expected a uint8 label map (what ops.argmax_c writes), got {labelmap.dtype}")
+    if labelmap.dim() not in (2, 3):
+        raise ValueError(f"{who}: expected a [H,W] or [D,H,W] label map, got {tuple(labelmap.shape)}")
+    mode = 2 if (labelmap.dim() == 2 or per_slice) else 3
+    m = labelmap.reshape((-1,) + tuple(labelmap.shape[-2:])).contiguous()
+    d, h, w = (int(v) for v in m.shape)
+    return m, d, h, w, mode
+
+
+def connected_components(labelmap: torch.Tensor, n_class: int, connectivity: int = 1, per_slice: bool = False) -> torch.Tensor:
+    """Connected components of every foreground class of a uint8 label map ([H,W] or [D,H,W]; per_slice: every [H,W] slice of a volume
+    on its own) -> int32 tensor of the same shape: for a voxel of class 1 <= c < n_class the smallest C-order linear index (within the
+    array, or within its slice with per_slice) of any voxel of its component, -1 elsewhere.  connectivity as
+    scipy.ndimage.generate_binary_structure(ndim, connectivity).  3 launches, no readback."""
+    m, d, h, w, mode = _cc_volume(labelmap, per_slice, "connected_components")
+    labels = torch.empty((d, h, w), dtype=torch.int32, device=m.device)
+    check(lib.ctl_cc_label(ptr(m), d, h, w, int(n_class), mode, int(connectivity), ptr(labels), stream_ptr()), "ctl_cc_label")
+    return labels.reshape(labelmap.shape)
+
+
+def keep_largest_components(labelmap: torch.Tensor, n_class: int, connectivity: int = 1, per_slice: bool = False,
+                            out: Optional[torch.Tensor] = None, want_table: bool = False):
+    """`keep_largest_connected_components` (post_process.py:5-22) on device: the uint8 label map with every voxel set to 0 that is not in
+    the largest component of its class (of its slice with per_slice); among components of equal size the one that starts first in C
+    order is kept.  `out` (uint8, labelmap's shape, contiguous) may be labelmap itself.  want_table: also the int64 device table
+    [groups, n_class - 1, 3] = (components, voxels of the kept one, its label or -1), groups = slices with per_slice else 1.
+    5 launches, no readback."""
+    m, d, h, w, mode = _cc_volume(labelmap, per_slice, "keep_largest_components")
+    if out is None:
+        out = torch.empty(labelmap.shape, dtype=torch.uint8, device=m.device)
+    elif not (out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == tuple(labelmap.shape) and out.is_contiguous()):
+        raise ValueError("keep_largest_components: `out` must be a contiguous uint8 device tensor of labelmap's shape")
+    table = torch.empty((d if mode == 2 else 1, int(n_class) - 1, 3), dtype=torch.int64, device=m.device) if want_table else None
+    nbytes = lib.ctl_cc_ws_bytes(d, h, w, int(n_class), mode)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=m.device)
+    check(lib.ctl_cc_keep_largest(ptr(m), d, h, w, int(n_class), mode, int(connectivity), ptr(out), ptr(table), ptr(ws), nbytes, stream_ptr()),
+          "ctl_cc_keep_largest")
+    return (out, table) if want_table else out
+
+
 def rescale_intensity(data: torch.Tensor, new_min: float = 0.0, new_max: float = 1.0, eps: float = 1e-20) -> torch.Tensor:
     """basic_operations.py:232-245 on device; data: [N,C,H,W] float32 in plain NCHW memory (each (n,c) plane contiguous)."""
     require_gpu(data)

@@ -55,14 +55,21 @@ def predict_volume(segmentation_model, image_d: torch.Tensor, n_iter=None, chunk
     return pred
 
 
+# `post_process` of TestSegmentationNetwork -> per_slice of ops.keep_largest_components (None: the prediction is scored as it is)
+POST_PROCESS = {None: None, "largest_cc": False, "largest_cc_2d": True}
+
+
 class TestSegmentationNetwork(object):
     __test__ = False                     # not a pytest class
 
     def __init__(self, test_dataset, crop_size, segmentation_model, use_gpu=True, save_path="", summary_report_file_name="result.csv",
                  detailed_report_file_name="details.csv", patient_wise=True, metrics_list=("Dice", "HD"), foreground_only=False,
-                 save_soft_prediction=False, keep_results=True):
+                 save_soft_prediction=False, keep_results=True, post_process=None):
         if not use_gpu:
             raise ValueError("this build has no CPU path")
+        if post_process not in POST_PROCESS:
+            raise ValueError("post_process {!r}: one of {}".format(post_process, sorted(POST_PROCESS, key=str)))
+        self.post_process = post_process
         self.test_dataset, self.crop_size, self.segmentation_model = test_dataset, crop_size, segmentation_model
         self.num_classes = segmentation_model.num_classes
         self.segmentation_metric = runningMySegmentationScore(n_classes=self.num_classes,
@@ -94,7 +101,9 @@ class TestSegmentationNetwork(object):
         (tester.COALESCE_CHUNKS, exact: see predict_volume; 2x the slices/s on a 40-slice volume); coalesce=False: the literal loop.
         The metric update reads back only small tables (voxel counts, and for 'HD' / 'ASD' the per-slice / per-class surface statistics
         of ops.surface_stats), so with keep_results=False and save_soft_prediction=False a patient is scored without any full-volume
-        device-to-host copy."""
+        device-to-host copy.  That also holds with `post_process` ("largest_cc": the volume as one 3-D object, "largest_cc_2d": every slice
+        on its own), which is applied on the device between the arg-max and the metric update; 'pred' of the result is then the
+        post-processed volume."""
         dev = torch.device("cuda", torch.cuda.current_device())
         image = data_tensor_pack["image"]
         if image.dim() == 5:                              # DataLoader(batch_size=1) adds a leading axis upstream
@@ -119,6 +128,8 @@ class TestSegmentationNetwork(object):
             pred_d[lo:hi] = ops.argmax_c(logit)
             if soft is not None:
                 soft.append(logit)
+        if self.post_process is not None:                 # largest component of every class (post_process.py:5-22), in place on the device
+            ops.keep_largest_components(pred_d, self.num_classes, per_slice=POST_PROCESS[self.post_process], out=pred_d)
         spacing = self.test_dataset.get_voxel_spacing() if hasattr(self.test_dataset, "get_voxel_spacing") else None
         self.segmentation_metric.update(pid=pid, preds=pred_d, gts=label_d, voxel_spacing=spacing)
         result = None

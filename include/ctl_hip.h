@@ -410,6 +410,30 @@ int ctl_surface_map(const uint8_t* mask, int32_t d, int32_t h, int32_t w, int32_
                     const double* sampling, double* d2_out, uint8_t* surface_out, void* workspace, size_t workspace_bytes,
                     ctl_stream stream);
 
+/* ------------------------------------------------------------------------------------------------ connected components
+ * Largest-connected-component post-processing of a predicted label volume (medseg/common_utils/post_process.py:5-22,
+ * `keep_largest_connected_components`, which upstream runs on the host with skimage.measure.label per class), and the labelling under it.
+ *   labelmap  uint8 [D,H,W] (as written by ctl_argmax_c).  A component is a maximal connected set of voxels that carry the SAME class c,
+ *             1 <= c < n_class (2..255); voxels of class 0 and voxels whose value is >= n_class belong to no component.
+ *   mode      2: every [H,W] slice on its own;  3: the volume (the numbering of ctl_surface_stats).
+ *   connectivity  1..mode, as scipy.ndimage.generate_binary_structure(mode, connectivity): neighbours at L1 offset <= connectivity
+ *             (1 = the 4- / 6-neighbourhood, what upstream uses).
+ * ctl_cc_label: labels (int32 [D,H,W]) = for a voxel of a component the smallest C-order linear index (within the volume in mode 3,
+ *   within its slice in mode 2) of any voxel of that component, -1 elsewhere.  The numbering is canonical: it does not depend on the
+ *   launch geometry or on the order of the merges.  3 launches; `labels` itself is the union-find parent array, no workspace.
+ * ctl_cc_keep_largest: out (uint8 [D,H,W], may alias labelmap) = labelmap with every voxel set to 0 that is not in the largest
+ *   component of its class (per slice in mode 2).  Largest = most voxels; among components of equal size the one whose first voxel in C
+ *   order comes first (np.argmax over components numbered in scan order).  table (int64 [groups][n_class - 1][3], may be NULL;
+ *   groups = D in mode 2, 1 in mode 3) = {number of components, voxels of the kept one, its label (-1: the class is absent)}.  5 launches.
+ * The sequence of launches is fixed (no loop "until nothing changes", no readback), whatever the volume holds; only integer atomics
+ * (min / max / add) are used, so every result is the same bits on every call.  Labels are 32-bit: D * H * W must be below 2^31.
+ * The workspace is caller-owned, sized by ctl_cc_ws_bytes (0 for arguments the call itself would refuse), 256-byte aligned. */
+size_t ctl_cc_ws_bytes(int32_t d, int32_t h, int32_t w, int32_t n_class, int32_t mode);
+int ctl_cc_label(const uint8_t* labelmap, int32_t d, int32_t h, int32_t w, int32_t n_class, int32_t mode, int32_t connectivity,
+                 int32_t* labels, ctl_stream stream);
+int ctl_cc_keep_largest(const uint8_t* labelmap, int32_t d, int32_t h, int32_t w, int32_t n_class, int32_t mode, int32_t connectivity,
+                        uint8_t* out, int64_t* table, void* workspace, size_t workspace_bytes, ctl_stream stream);
+
 /* ------------------------------------------------------------------------------------------------ optimizer
  * torch.optim.Adam defaults (model.py:774-785), one flat buffer: p,g,m,v [count].  step = 1-based step index.
  * grad_scale folds the 1/world_size of the data-parallel all-reduce. */

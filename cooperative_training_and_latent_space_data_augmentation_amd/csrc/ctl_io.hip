@@ -93,6 +93,7 @@ extern "C" int ctl_rescale_intensity(const float* x, float* out, float* workspac
     const dim3 grid(RS_BPP, (unsigned)planes), blk(IOB);
     minmax_partial_kernel<<<grid, blk, 0, S_>>>(x, plane_elems, workspace);
     rescale_apply_kernel<<<grid, blk, 0, S_>>>(x, workspace, plane_elems, new_min, new_max - new_min, eps, out);
+    ctl_count_launches(1);                                     // two kernels, CTL_LAUNCH_CHECK counts one
     CTL_LAUNCH_CHECK("rescale_intensity");
     return CTL_OK;
 }

@@ -468,12 +468,101 @@ def keep_largest_components(labelmap: torch.Tensor, n_class: int, connectivity: 
     return (out, table) if want_table else out
 
 
-def rescale_intensity(data: torch.Tensor, new_min: float = 0.0, new_max: float = 1.0, eps: float = 1e-20) -> torch.Tensor:
-    """basic_operations.py:232-245 on device; data: [N,C,H,W] float32 in plain NCHW memory (each (n,c) plane contiguous)."""
+def _aug_vec(v, n: int, dtype, device, who: str, name: str) -> torch.Tensor:
+    """A per-sample parameter: a scalar (broadcast) or n values -> contiguous device tensor [n] of dtype."""
+    if not isinstance(v, torch.Tensor):
+        v = torch.as_tensor(v)
+    if v.dim() == 0:
+        v = v.expand(n)
+    if v.numel() != n:
+        raise ValueError(f"{who}: {name} must be a scalar or hold one value per sample ({n}), got {tuple(v.shape)}")
+    return v.reshape(n).to(device=device, dtype=dtype).contiguous()
+
+
+def _aug_ws(nbytes: int, n: int, hp: int, wp: int, hc: int, wc: int, device, who: str):
+    """The workspace of an augmentation entry: (uint8 device tensor, bytes).  Refused shapes (a size query of 0) raise."""
+    if nbytes == 0:
+        raise ValueError(f"{who}: n={n}, {hp}x{wp} -> {hc}x{wc} is refused: sizes must be positive, planes at most 512x512 and the crop "
+                         "no larger than the input")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
+
+
+def aug_elastic_field(n: int, hp: int, wp: int, alpha, sigma, seed, noise: Optional[torch.Tensor] = None, device=None,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Elastic displacement of `MyElasticTransform` (elastic_transform.py:41-58) for a batch -> float32 device tensor [n,2,hp,wp]
+    (rows, cols) = alpha * gaussian_filter(u, sigma, mode='constant', truncate=4) with u uniform in [-1, 1): `noise` ([n,2,hp,wp]) when
+    given, else the counter hash of (seed, sample, axis, pixel).  alpha, sigma, seed: a scalar or one value per sample (host values or
+    device tensors; device tensors are read by the kernels, nothing returns to the host).  alpha == 0 gives a zero field.  2 launches."""
+    n, hp, wp = int(n), int(hp), int(wp)
+    if noise is not None:
+        require_gpu(noise)
+        if tuple(noise.shape) != (n, 2, hp, wp) or noise.dtype != torch.float32:
+            raise ValueError(f"aug_elastic_field: noise must be float32 [n,2,hp,wp] = {(n, 2, hp, wp)}, got {noise.dtype} {tuple(noise.shape)}")
+        noise = noise.contiguous()
+        device = noise.device
+    elif device is None:
+        device = next((v.device for v in (alpha, sigma, seed) if isinstance(v, torch.Tensor) and v.is_cuda), torch.device("cuda"))
+    ws, nbytes = _aug_ws(lib.ctl_aug_ws_bytes(n, hp, wp), n, hp, wp, 1, 1, device, "aug_elastic_field")
+    a = _aug_vec(alpha, n, torch.float32, device, "aug_elastic_field", "alpha")
+    s = _aug_vec(sigma, n, torch.float32, device, "aug_elastic_field", "sigma")
+    sd = _aug_vec(seed, n, torch.int64, device, "aug_elastic_field", "seed")
+    if out is None:
+        out = torch.empty((n, 2, hp, wp), dtype=torch.float32, device=device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (n, 2, hp, wp) and out.is_contiguous()):
+        raise ValueError("aug_elastic_field: `out` must be a contiguous float32 device tensor [n,2,hp,wp]")
+    check(lib.ctl_aug_field(ptr(noise), ptr(sd), ptr(a), ptr(s), n, hp, wp, ptr(out), ptr(ws), nbytes, stream_ptr()), "ctl_aug_field")
+    return out
+
+
+def aug_warp(image: torch.Tensor, label: torch.Tensor, matrix: torch.Tensor, intensity: torch.Tensor, crop,
+             field: Optional[torch.Tensor] = None, out=None):
+    """One resampling of a batch (transform.py:46-82 without the normalisation): image float32 [n,1,hp,wp] and label int64 [n,hp,wp] ->
+    (image [n,1,hc,wc], label [n,hc,wc]) for crop = (hc, wc), the centre window of MySpecialCrop.  matrix: float32 [n,2,3], the
+    output -> input map about the plane centre in (row, col) order; intensity: float32 [n,2] = (scale, brightness) applied to every tap
+    and clamped to the plane's min / max; field: float32 [n,2,hp,wp] from aug_elastic_field, None = no elastic.  Image taps are
+    bilinear with zeros outside, label taps nearest.  `out` = (image_out, label_out): contiguous device tensors of the result's shapes
+    and dtypes that share no memory with each other or with any input (the gather reads whole input planes).  2 launches, no readback."""
+    require_gpu(image, label, matrix, intensity, field)
+    if image.dim() != 4 or image.shape[1] != 1 or image.dtype != torch.float32:
+        raise ValueError(f"aug_warp: image must be float32 [n,1,hp,wp], got {image.dtype} {tuple(image.shape)}")
+    n, _, hp, wp = (int(v) for v in image.shape)
+    if label.dtype != torch.int64 or tuple(label.shape) != (n, hp, wp):
+        raise ValueError(f"aug_warp: label must be int64 [n,hp,wp] = {(n, hp, wp)}, got {label.dtype} {tuple(label.shape)}")
+    if matrix.dtype != torch.float32 or tuple(matrix.shape) != (n, 2, 3):
+        raise ValueError(f"aug_warp: matrix must be float32 [n,2,3], got {matrix.dtype} {tuple(matrix.shape)}")
+    if intensity.dtype != torch.float32 or tuple(intensity.shape) != (n, 2):
+        raise ValueError(f"aug_warp: intensity must be float32 [n,2], got {intensity.dtype} {tuple(intensity.shape)}")
+    if field is not None and (field.dtype != torch.float32 or tuple(field.shape) != (n, 2, hp, wp)):
+        raise ValueError(f"aug_warp: field must be float32 [n,2,hp,wp], got {field.dtype} {tuple(field.shape)}")
+    hc, wc = int(crop[0]), int(crop[1])
+    ws, nbytes = _aug_ws(lib.ctl_aug_warp_ws_bytes(n, hp, wp, hc, wc), n, hp, wp, hc, wc, image.device, "aug_warp")
+    if out is None:
+        io = torch.empty((n, 1, hc, wc), dtype=torch.float32, device=image.device)
+        lo = torch.empty((n, hc, wc), dtype=torch.int64, device=image.device)
+    else:
+        io, lo = out
+        if not (io.is_cuda and io.dtype == torch.float32 and tuple(io.shape) == (n, 1, hc, wc) and io.is_contiguous()
+                and lo.is_cuda and lo.dtype == torch.int64 and tuple(lo.shape) == (n, hc, wc) and lo.is_contiguous()):
+            raise ValueError("aug_warp: `out` must be (float32 [n,1,hc,wc], int64 [n,hc,wc]) contiguous device tensors")
+    image, label, matrix, intensity = image.contiguous(), label.contiguous(), matrix.contiguous(), intensity.contiguous()
+    check(lib.ctl_aug_warp(ptr(image), ptr(label), ptr(matrix), ptr(intensity), ptr(None if field is None else field.contiguous()), n, hp, wp,
+                           hc, wc, ptr(io), ptr(lo), ptr(ws), nbytes, stream_ptr()), "ctl_aug_warp")
+    return io, lo
+
+
+def rescale_intensity(data: torch.Tensor, new_min: float = 0.0, new_max: float = 1.0, eps: float = 1e-20,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """basic_operations.py:232-245 on device; data: [N,C,H,W] float32 in plain NCHW memory (each (n,c) plane contiguous).  `out`:
+    a contiguous float32 device tensor of data's shape to write into, not data itself."""
     require_gpu(data)
     x = data.float().contiguous()
     n, c, h, w = x.shape
-    out = torch.empty_like(x)
+    if out is None:
+        out = torch.empty_like(x)
+    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == tuple(x.shape) and out.is_contiguous()):
+        raise ValueError("rescale_intensity: `out` must be a contiguous float32 device tensor of data's shape")
+    elif out.data_ptr() == x.data_ptr():
+        raise ValueError("rescale_intensity: `out` must not be the input")
     ws = torch.empty(lib.ctl_rescale_intensity_ws_floats(n * c), dtype=torch.float32, device=x.device)
     check(lib.ctl_rescale_intensity(ptr(x), ptr(out), ptr(ws), n * c, h * w, new_min, new_max, eps, stream_ptr()), "ctl_rescale_intensity")
     return out

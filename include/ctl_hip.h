@@ -434,6 +434,50 @@ int ctl_cc_label(const uint8_t* labelmap, int32_t d, int32_t h, int32_t w, int32
 int ctl_cc_keep_largest(const uint8_t* labelmap, int32_t d, int32_t h, int32_t w, int32_t n_class, int32_t mode, int32_t connectivity,
                         uint8_t* out, int64_t* table, void* workspace, size_t workspace_bytes, ctl_stream stream);
 
+/* ------------------------------------------------------------------------------------------------ training augmentation
+ * The per-slice host chain of medseg/dataset_loader/transform.py:46-86 (flip, contrast / brightness, random affine, choice rotation,
+ * elastic deformation, centre crop) for a whole batch that is already on the device: image float [n,1,Hp,Wp] and label int64 [n,Hp,Wp]
+ * -> image_out float [n,1,Hc,Wc] and label_out int64 [n,Hc,Wc].  Every array is resampled ONCE (upstream resamples up to three times).
+ * The min-max normalisation that ends the chain (MyNormalizeMedicPercentile with percentiles (0, 100), transform.py:83-84) is
+ * ctl_rescale_intensity on image_out.
+ *   source    output pixel (y, x) is p = (y + cy, x + cx) on the padded grid, cy = ceil((Hp - Hc) / 2), cx = ceil((Wp - Wc) / 2)
+ *             (MySpecialCrop, _utils/affine_transform.py:280-283).  Its source coordinate is s = M (p + d(p) - c) + c with
+ *             c = ((Hp - 1) / 2, (Wp - 1) / 2), d = the sample's elastic displacement (rows, cols; zero without a field) and M = the
+ *             sample's 2x3 output -> input matrix in (row, col) order: s_r = m[0] q_r + m[1] q_c + m[2] + c_r, s_c = m[3] q_r + m[4] q_c +
+ *             m[5] + c_c for q = p + d - c.  The host composes M = F A Rc from the flips (MyRandomFlip, affine_transform.py:200-244), the
+ *             random affine A = R(theta) T(ty, tx) Sh(phi) Z(zy, zx) (ts.RandomAffine, transform.py:70-73) and the choice rotation
+ *             (MyRandomChoiceRotate, affine_transform.py:750-804): upstream's flip -> affine -> rotate -> elastic chain as one map.
+ *             Coordinates are fp32.
+ *   image     bilinear over the four taps around s; a tap outside the array contributes 0 (scipy.ndimage.map_coordinates(order=1,
+ *             mode='grid-constant', cval=0)).  Every tap first goes through clamp(v * scale + brightness, mn, mx) with intensity[b] =
+ *             {scale, brightness} and mn / mx = the minimum / maximum of the sample's whole padded input plane
+ *             (RandomBrightnessFluctuation with preserve_range, _utils/intensity_transform.py:136-162, which upstream applies pointwise
+ *             before any geometry: the same function).  {1, 0} switches it off.  The taps are combined in fp64 and rounded once.
+ *   label     nearest neighbour: the tap at floor(s + 0.5) per axis, 0 outside the array.  (Upstream's per-class cubic spline and
+ *             threshold, _utils/elastic_transform.py:84-92, is deliberately not reproduced.)
+ *   field     float [n,2,Hp,Wp], d of sample b = (field[b][0], field[b][1]); NULL = no elastic deformation for the whole batch.
+ * ctl_aug_field: field[b][axis] = alpha[b] * G_sigma[b](u[b][axis]) (MyElasticTransform.gen_deformation_field, elastic_transform.py:41-58,
+ *   with alpha / sigma drawn as in :72-75).  G_sigma = scipy.ndimage.gaussian_filter(mode='constant', cval=0, truncate=4.0): separable,
+ *   radius int(4 sigma + 0.5) (clamped to 1024 = twice the largest side), weights normalised over the whole radius in fp64, fp32
+ *   accumulation; sigma <= 0 is the identity.  u is uniform in [-1, 1): noise (float [n,2,Hp,Wp]) when given, as ctl_noise_clamp takes
+ *   one, else 2^-23 * (h >> 40) - 1 for the counter hash h of (seeds[b], b * 2 + axis, y * Wp + x) (the splitmix64 finaliser of
+ *   ctl_noise_clamp / ctl_dropout2d).  alpha, sigma: device float [n]; seeds: device uint64 [n] (may be NULL with noise).  A sample with
+ *   alpha == 0 gets zeros without filtering.  2 launches: rows from an LDS-staged row, columns from an LDS-staged 16-column tile.
+ * ctl_aug_warp: the gather above, 2 launches: per-plane min / max partials (the scheme of ctl_rescale_intensity), then one pass over the
+ *   crop window that writes image_out and label_out together.
+ * Hp, Wp <= 512 (the LDS staging of the field passes), Hc <= Hp, Wc <= Wp, n <= 65535.  The launch counts do not depend on n; there is no
+ * host synchronisation and no atomic: two calls give the same bits.  Workspaces are caller-owned, 256-byte aligned and sized by
+ * ctl_aug_ws_bytes for ctl_aug_field (the row-filtered planes) and by ctl_aug_warp_ws_bytes for ctl_aug_warp (the min / max partials);
+ * both return 0 for arguments the call would refuse.  No written array (field, image_out, label_out, a workspace) may overlap another
+ * array of the same call. */
+size_t ctl_aug_ws_bytes(int32_t n, int32_t hp, int32_t wp);
+size_t ctl_aug_warp_ws_bytes(int32_t n, int32_t hp, int32_t wp, int32_t hc, int32_t wc);
+int ctl_aug_field(const float* noise, const uint64_t* seeds, const float* alpha, const float* sigma, int32_t n, int32_t hp, int32_t wp,
+                  float* field, void* workspace, size_t workspace_bytes, ctl_stream stream);
+int ctl_aug_warp(const float* image, const int64_t* label, const float* matrix, const float* intensity, const float* field, int32_t n,
+                 int32_t hp, int32_t wp, int32_t hc, int32_t wc, float* image_out, int64_t* label_out, void* workspace,
+                 size_t workspace_bytes, ctl_stream stream);
+
 /* ------------------------------------------------------------------------------------------------ optimizer
  * torch.optim.Adam defaults (model.py:774-785), one flat buffer: p,g,m,v [count].  step = 1-based step index.
  * grad_scale folds the 1/world_size of the data-parallel all-reduce. */

@@ -515,8 +515,13 @@ __global__ __launch_bounds__(EB) void softmax_t_bwd_kernel(const float* __restri
         row_load<CT>(p, i, c, pv);
         row_load<CT>(dp, i, c, dv);
         float dot = 0.f;
+        // products rounded on their own: left to the compiler, CT = 4 came out as packed multiplies + adds and CT = 0 as
+        // fma, one ulp apart
+        {
+#pragma clang fp contract(off)
 #pragma unroll
-        for (int k = 0; k < c; ++k) dot += pv[k] * dv[k];
+            for (int k = 0; k < c; ++k) dot += pv[k] * dv[k];
+        }
 #pragma unroll
         for (int k = 0; k < c; ++k) dv[k] = pv[k] * (dv[k] - dot) * inv_t;
         row_store<CT>(dx, i, c, dv);

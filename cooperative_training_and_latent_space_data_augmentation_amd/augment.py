@@ -6,6 +6,9 @@ them again in fp64 numpy / scipy and is the host path for numpy inputs.
 
     aug = BatchAugmenter("ACDC_affine_elastic_intensity", crop_size=(192, 192), seed=0)
     image, label = aug(image, label)          # [n,1,Hp,Wp] float32, [n,Hp,Wp] int64 on the device -> [n,1,192,192], [n,192,192]
+
+BatchAugmenter(..., interp="cubic", num_classes=K) reads image and label through upstream's cubic spline (ctl_aug_warp_cubic) in place of
+bilinear / nearest; the default is unchanged.
 """
 from __future__ import annotations
 
@@ -166,9 +169,20 @@ def source_coords(matrix, hp: int, wp: int, hc: int, wc: int, field=None) -> np.
     return np.stack([e(0) * qr + e(1) * qc + e(2) + cr, e(3) * qr + e(4) * qc + e(5) + cc], axis=1)
 
 
-def warp_host(image, label, matrix, intensity, crop, field=None):
-    """ctl_aug_warp in fp64: (image fp64 [n,1,hc,wc], label int64 [n,hc,wc])."""
+def _inside(s, hp: int, wp: int) -> np.ndarray:
+    """Where a cubic value is read: -0.5 <= s_r <= Hp - 0.5 and -0.5 <= s_c <= Wp - 0.5 (elsewhere the result is 0).  s: [2,hc,wc]"""
+    return (s[0] >= -0.5) & (s[0] <= hp - 0.5) & (s[1] >= -0.5) & (s[1] <= wp - 0.5)
+
+
+def warp_host(image, label, matrix, intensity, crop, field=None, interp="linear", n_class=None):
+    """ctl_aug_warp (interp="linear") or ctl_aug_warp_cubic (interp="cubic", with n_class) in fp64: (image fp64 [n,1,hc,wc], label int64
+    [n,hc,wc]).  Cubic: map_coordinates(order=3, mode='reflect') of the intensity-mapped image and of every indicator label == k inside
+    the array, 0 outside; the label is the largest k whose value is >= 0.5 (_utils/elastic_transform.py:84-92)."""
     from scipy import ndimage
+    if interp not in ("linear", "cubic"):
+        raise ValueError(f"warp_host: interp must be 'linear' or 'cubic', got {interp!r}")
+    if interp == "cubic" and (n_class is None or not 1 <= int(n_class) <= 16):
+        raise ValueError(f"warp_host: interp='cubic' needs n_class in 1..16, got {n_class!r}")
     image, label = np.asarray(image, dtype=np.float64), np.asarray(label)
     n, _, hp, wp = image.shape
     hc, wc = int(crop[0]), int(crop[1])
@@ -177,6 +191,13 @@ def warp_host(image, label, matrix, intensity, crop, field=None):
     io, lo = np.zeros((n, 1, hc, wc)), np.zeros((n, hc, wc), dtype=np.int64)
     for b in range(n):
         v = np.clip(image[b, 0] * it[b, 0] + it[b, 1], image[b, 0].min(), image[b, 0].max())
+        if interp == "cubic":
+            inside = _inside(s[b], hp, wp)
+            io[b, 0] = np.where(inside, ndimage.map_coordinates(v, s[b], order=3, mode="reflect"), 0.0)
+            for k in range(int(n_class)):
+                val = ndimage.map_coordinates((label[b] == k).astype(np.float64), s[b], order=3, mode="reflect")
+                lo[b][inside & (val >= 0.5)] = k
+            continue
         io[b, 0] = ndimage.map_coordinates(v, s[b], order=1, mode="grid-constant", cval=0.0)
         r = np.floor(s[b] + 0.5).astype(np.int64)
         inside = (r[0] >= 0) & (r[0] < hp) & (r[1] >= 0) & (r[1] < wp)
@@ -191,11 +212,11 @@ def rescale_host(image, new_min=0.0, new_max=1.0, eps=1e-20):
     return (image - mn) / (mx - mn + eps) * (new_max - new_min) + new_min
 
 
-def apply_host(image, label, params, noise=None, field=None):
+def apply_host(image, label, params, noise=None, field=None, interp="linear", n_class=None):
     """The whole chain on the host in fp64 numpy / scipy, from the definitions of include/ctl_hip.h: image [n,1,Hp,Wp], label [n,Hp,Wp],
     params as BatchAugmenter.draw returns them -> (image float32 [n,1,Hc,Wc] in [0, 1], label int64 [n,Hc,Wc]).  noise: explicit u
     [n,2,Hp,Wp] in place of the counter hash; field: an explicit displacement in place of the filtered noise.  The elastic stage runs
-    only when params carries alpha (a policy with elastic deformation)."""
+    only when params carries alpha (a policy with elastic deformation).  interp, n_class: as warp_host."""
     image, label = _np(image), _np(label)
     n, _, hp, wp = image.shape
     hc, wc = (int(v) for v in _np(params["crop"]))
@@ -203,7 +224,7 @@ def apply_host(image, label, params, noise=None, field=None):
         field = elastic_field_host(_np(params["alpha"]), _np(params["sigma"]), hp, wp, seeds=_np(params["seed"]), noise=None if noise is None else _np(noise))
     elif field is not None:
         field = _np(field)
-    io, lo = warp_host(image, label, _np(params["matrix"]), _np(params["intensity"]), (hc, wc), field)
+    io, lo = warp_host(image, label, _np(params["matrix"]), _np(params["intensity"]), (hc, wc), field, interp=interp, n_class=n_class)
     return rescale_host(io).astype(np.float32), lo
 
 
@@ -230,9 +251,20 @@ class BatchAugmenter:
                       then be device tensors whose content is refreshed between replays).  6 launches with an elastic policy (field 2,
                       warp 2, rescale 2), else 4.  out = (image_out, label_out) must not share memory with image or label.
                       numpy arrays: apply_host.
-    __call__(image, label)   draw, a pinned non-blocking upload of the parameters, apply."""
+    __call__(image, label)   draw, a pinned non-blocking upload of the parameters, apply.
 
-    def __init__(self, policy: str, crop_size, seed: int = 0):
+    interp="cubic" (with num_classes, 1..16) reads image and label through a cubic spline as upstream's elastic stage does: the image by
+    map_coordinates(order=3, mode='reflect'), the label as per-class indicator maps thresholded at 0.5, zero outside the array; still one
+    resampling.  draw does not depend on interp.  The warp then takes 4 launches (min / max partials, prefilter rows, prefilter columns,
+    gather): 8 launches per batch with an elastic policy, else 6, whatever n is."""
+
+    def __init__(self, policy: str, crop_size, seed: int = 0, interp: str = "linear", num_classes=None):
+        if interp not in ("linear", "cubic"):
+            raise ValueError(f"BatchAugmenter: interp must be 'linear' or 'cubic', got {interp!r}")
+        if interp == "cubic" and (num_classes is None or not 1 <= int(num_classes) <= 16):
+            raise ValueError(f"BatchAugmenter: interp='cubic' needs num_classes in 1..16 (one indicator plane per class), got {num_classes!r}")
+        self.interp = interp
+        self.num_classes = None if num_classes is None else int(num_classes)
         self.policy_name = policy
         self.policy = get_policy(policy)
         self.crop_size = (int(crop_size[0]), int(crop_size[1]))
@@ -282,7 +314,7 @@ class BatchAugmenter:
 
     def apply(self, image, label, params: dict, out=None):
         if isinstance(image, np.ndarray):
-            return apply_host(image, label, params)
+            return apply_host(image, label, params, interp=self.interp, n_class=self.num_classes)
         ops.require_gpu(image, label, *(params.get(k) for k in DEVICE_KEYS))
         n, _, hp, wp = image.shape
         crop = self.crop_size
@@ -292,7 +324,8 @@ class BatchAugmenter:
         if params.get("alpha") is not None:
             field = ops.aug_elastic_field(n, hp, wp, params["alpha"], params["sigma"], params["seed"], device=image.device)
         warped, lab = ops.aug_warp(image, label, params["matrix"], params["intensity"], crop, field=field,
-                                   out=None if out is None else (torch.empty_like(out[0]), out[1]))
+                                   out=None if out is None else (torch.empty_like(out[0]), out[1]), interp=self.interp,
+                                   n_class=self.num_classes if self.interp == "cubic" else None)
         return ops.rescale_intensity(warped, 0.0, 1.0, out=None if out is None else out[0]), lab
 
     def __call__(self, image, label):

@@ -5,7 +5,9 @@
 //                   column pass, each from an LDS-staged line with the normalised weights of scipy's gaussian_filter
 //   ctl_aug_warp    per-plane min / max partials, then one gather over the crop window: bilinear image taps through the intensity
 //                   map (intensity_transform.py:136-162), nearest-neighbour label
-// The contract of both is written out in include/ctl_hip.h.
+//   ctl_aug_spline_coeffs / ctl_aug_warp_cubic   the same gather through a cubic spline (elastic_transform.py:84-92): B-spline coefficients
+//                   of the image and of every class indicator, then 4x4 taps; at the end of this file
+// The contract of all of them is written out in include/ctl_hip.h.
 #include "ctl_common.h"
 
 #define AUG_B 256
@@ -174,6 +176,25 @@ __global__ __launch_bounds__(AUG_B) void aug_minmax_partial_kernel(const float* 
     if (threadIdx.x == 0) { partial[((int64_t)blockIdx.y * AUG_BPP + blockIdx.x) * 2] = mn; partial[((int64_t)blockIdx.y * AUG_BPP + blockIdx.x) * 2 + 1] = mx; }
 }
 
+// s = M (p + d(p) - c) + c of output pixel (y, x) of sample b in fp32 (prm = the sample's matrix), shared by both gathers
+__device__ __forceinline__ void aug_source(const float* __restrict__ field, const float* prm, int b, int y, int x, int hp, int wp, int cy,
+                                           int cx, float& sr, float& sc) {
+    const int py = y + cy, px = x + cx;                        // inside the padded grid: cy + hc <= hp, cx + wc <= wp
+    const int64_t plane = (int64_t)hp * wp;
+    float qr = (float)py, qc = (float)px;
+    if (field) {
+        qr += field[(int64_t)b * 2 * plane + (int64_t)py * wp + px];
+        qc += field[((int64_t)b * 2 + 1) * plane + (int64_t)py * wp + px];
+    }
+    const float cr = 0.5f * (float)(hp - 1), cc = 0.5f * (float)(wp - 1);
+    qr -= cr; qc -= cc;
+    sr = prm[0] * qr + prm[1] * qc + prm[2] + cr;
+    sc = prm[3] * qr + prm[4] * qc + prm[5] + cc;
+    // everything at or beyond one pixel outside the array is zero: clamping there changes no result and keeps the conversions defined
+    sr = fminf(fmaxf(sr, -2.f), (float)hp + 1.f);
+    sc = fminf(fmaxf(sc, -2.f), (float)wp + 1.f);
+}
+
 __global__ __launch_bounds__(AUG_B) void aug_warp_kernel(const float* __restrict__ image, const int64_t* __restrict__ label,
                                                           const float* __restrict__ matrix, const float* __restrict__ intensity,
                                                           const float* __restrict__ field, const float* __restrict__ partial, int hp, int wp,
@@ -189,20 +210,9 @@ __global__ __launch_bounds__(AUG_B) void aug_warp_kernel(const float* __restrict
     aug_block_minmax(mn, mx, sm);                              // its barriers also publish prm[]
     const int x = (int)blockIdx.x * AUG_TW + (threadIdx.x & 63), y = (int)blockIdx.y * (AUG_B / AUG_TW) + (threadIdx.x >> 6);
     if (x >= wc || y >= hc) return;
-    const int py = y + cy, px = x + cx;                        // inside the padded grid: cy + hc <= hp, cx + wc <= wp
     const int64_t plane = (int64_t)hp * wp;
-    float qr = (float)py, qc = (float)px;
-    if (field) {
-        qr += field[(int64_t)b * 2 * plane + (int64_t)py * wp + px];
-        qc += field[((int64_t)b * 2 + 1) * plane + (int64_t)py * wp + px];
-    }
-    const float cr = 0.5f * (float)(hp - 1), cc = 0.5f * (float)(wp - 1);
-    qr -= cr; qc -= cc;
-    float sr = prm[0] * qr + prm[1] * qc + prm[2] + cr;
-    float sc = prm[3] * qr + prm[4] * qc + prm[5] + cc;
-    // everything at or beyond one pixel outside the array is zero: clamping there changes no result and keeps the conversions defined
-    sr = fminf(fmaxf(sr, -2.f), (float)hp + 1.f);
-    sc = fminf(fmaxf(sc, -2.f), (float)wp + 1.f);
+    float sr, sc;
+    aug_source(field, prm, b, y, x, hp, wp, cy, cx, sr, sc);
     const float fy0 = floorf(sr), fx0 = floorf(sc);
     const int y0 = (int)fy0, x0 = (int)fx0;
     const double wy = (double)(sr - fy0), wx = (double)(sc - fx0);
@@ -251,5 +261,242 @@ extern "C" int ctl_aug_warp(const float* image, const int64_t* label, const floa
         image, label, matrix, intensity, field, partial, hp, wp, hc, wc, cy, cx, image_out, label_out);
     ctl_count_launches(1);
     CTL_LAUNCH_CHECK("aug_warp");
+    return CTL_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ cubic spline
+// Coefficients C(v) = scipy.ndimage.spline_filter(v, order=3, mode='reflect') of 1 + n_class planes per sample (plane 0: the image through
+// the intensity map, plane 1 + k: the indicator of label k, formed while the row is staged), then a 4x4-tap gather over them.  The
+// one-pole recursion of the prefilter (z = sqrt(3) - 2) is the two-sided sequence h[k] = sqrt(3) z^|k| over the symmetric extension
+// d c b a | a b c d | d c b a; it is cut at |k| <= AUG_SP_R, where what is dropped is below 1e-23 of the sum, so each pass is an FIR over an
+// LDS-staged, already reflected line like the passes of ctl_aug_field.  fp64 accumulation, fp32 storage of both stages.
+// A line shorter than AUG_SP_SHORT is the one case where scipy is not that exact inverse: the last term of its causal initialisation
+// reads the running sum in place of the first sample, an error of about |z|^(2 len) (4e-7 at 5 samples, below 1e-17 from 16 on).  The
+// contract is scipy's result, so such a line goes through scipy's own recursion, by one thread: at most 15 samples.
+#define AUG_SP_R 40
+#define AUG_SP_SHORT 16
+#define AUG_MAX_CLASS 16          // as ctl_confusion_hist
+
+static inline bool aug_spline_ok(int n, int hp, int wp, int n_class, int min_class) {
+    return aug_shape_ok(n, hp, wp, 1, 1) && n_class >= min_class && n_class <= AUG_MAX_CLASS;
+}
+static inline size_t aug_planes_bytes(int n, int hp, int wp, int n_class) { return aug_align((size_t)n * (1 + n_class) * hp * wp * sizeof(float)); }
+static inline size_t aug_spline_bytes(int n, int hp, int wp, int n_class) { return aug_partial_bytes(n) + aug_planes_bytes(n, hp, wp, n_class); }
+static inline size_t aug_cubic_bytes(int n, int hp, int wp, int n_class) { return aug_partial_bytes(n) + 2 * aug_planes_bytes(n, hp, wp, n_class); }
+
+extern "C" size_t ctl_aug_spline_ws_bytes(int32_t n, int32_t hp, int32_t wp, int32_t n_class) {
+    return aug_spline_ok(n, hp, wp, n_class, 0) ? aug_spline_bytes(n, hp, wp, n_class) : 0;
+}
+extern "C" size_t ctl_aug_warp_cubic_ws_bytes(int32_t n, int32_t hp, int32_t wp, int32_t hc, int32_t wc, int32_t n_class) {
+    return aug_shape_ok(n, hp, wp, hc, wc) && aug_spline_ok(n, hp, wp, n_class, 1) ? aug_cubic_bytes(n, hp, wp, n_class) : 0;
+}
+
+// index i of a line of `len` samples under the half-sample symmetric extension, folded as often as it takes (len may be 1)
+__device__ __forceinline__ int aug_reflect(int i, int len) {
+    const int period = 2 * len;
+    int m = i % period;
+    if (m < 0) m += period;
+    return m < len ? m : period - 1 - m;
+}
+// h[k] = (-6 z / (1 - z^2)) z^k = sqrt(3) z^k for k = 0 .. AUG_SP_R; the caller's barrier publishes it
+__device__ __forceinline__ void aug_spline_taps(double* __restrict__ h) {
+    if (threadIdx.x <= AUG_SP_R) {
+        const double z = sqrt(3.0) - 2.0;
+        double p = sqrt(3.0);
+        for (int k = 0; k < (int)threadIdx.x; ++k) p *= z;
+        h[threadIdx.x] = p;
+    }
+}
+// scipy's spline_filter1d(order=3, mode='reflect') on c[0], c[stride], .. (n < AUG_SP_SHORT samples) in place, statement by statement
+// (ni_splines.c: gain, _init_causal_reflect, the causal and the anticausal sweep)
+__device__ void aug_spline_recursion(double* c, int n, int stride) {
+    const double z = sqrt(3.0) - 2.0;
+    double z_n = 1.0;
+    for (int i = 0; i < n; ++i) { c[i * stride] *= (1.0 - z) * (1.0 - 1.0 / z); z_n *= z; }
+    const double c0 = c[0];
+    double z_i = z;
+    c[0] = c[0] + z_n * c[(n - 1) * stride];
+    for (int i = 1; i < n; ++i) {                              // at i = n - 1 this reads c[0] as it stands: scipy's result, not the exact sum
+        c[0] += z_i * (c[i * stride] + z_n * c[(n - 1 - i) * stride]);
+        z_i *= z;
+    }
+    c[0] = c[0] * (z / (1.0 - z_n * z_n)) + c0;
+    for (int i = 1; i < n; ++i) c[i * stride] += z * c[(i - 1) * stride];
+    c[(n - 1) * stride] *= z / (z - 1.0);
+    for (int i = n - 2; i >= 0; --i) c[i * stride] = z * (c[(i + 1) * stride] - c[i * stride]);
+}
+#define AUG_SP_FIR(line, at, stride)                                                                         \
+    double acc = 0.0;                                                                                        \
+    for (int k = AUG_SP_R; k > 0; --k) acc = fma(h[k], (double)line[((at) - k) * (stride)] + (double)line[((at) + k) * (stride)], acc); \
+    acc = fma(h[0], (double)line[(at) * (stride)], acc)
+
+// one block = one row of one (sample, plane): the reflected row of v or of the indicator staged in fp64, filtered along x
+__global__ __launch_bounds__(AUG_B) void aug_spline_row_kernel(const float* __restrict__ image, const int64_t* __restrict__ label,
+                                                                const float* __restrict__ intensity, const float* __restrict__ partial, int hp,
+                                                                int wp, float* __restrict__ tmp) {
+    __shared__ double ext[AUG_MAX_SIDE + 2 * AUG_SP_R];
+    __shared__ double h[AUG_SP_R + 1];
+    __shared__ float sm[2 * AUG_B / 64];
+    const int y = blockIdx.x, pl = blockIdx.y, b = blockIdx.z;
+    const int64_t in_row = ((int64_t)b * hp + y) * wp;
+    aug_spline_taps(h);
+    if (pl == 0) {                                             // block-uniform
+        float mn = INFINITY, mx = -INFINITY;
+        if (threadIdx.x < AUG_BPP) { mn = partial[((int64_t)b * AUG_BPP + threadIdx.x) * 2]; mx = partial[((int64_t)b * AUG_BPP + threadIdx.x) * 2 + 1]; }
+        aug_block_minmax(mn, mx, sm);
+        const double scale = (double)intensity[b * 2], bright = (double)intensity[b * 2 + 1];
+        for (int j = threadIdx.x; j < wp + 2 * AUG_SP_R; j += AUG_B)
+            ext[j] = fmin(fmax(fma((double)image[in_row + aug_reflect(j - AUG_SP_R, wp)], scale, bright), (double)mn), (double)mx);
+    } else {
+        const int64_t k = pl - 1;
+        for (int j = threadIdx.x; j < wp + 2 * AUG_SP_R; j += AUG_B) ext[j] = label[in_row + aug_reflect(j - AUG_SP_R, wp)] == k ? 1.0 : 0.0;
+    }
+    __syncthreads();
+    const int64_t out_row = (((int64_t)b * gridDim.y + pl) * hp + y) * wp;
+    if (wp < AUG_SP_SHORT) {                                   // block-uniform
+        if (threadIdx.x == 0) aug_spline_recursion(ext + AUG_SP_R, wp, 1);
+        __syncthreads();
+        if ((int)threadIdx.x < wp) tmp[out_row + threadIdx.x] = (float)ext[AUG_SP_R + threadIdx.x];
+        return;
+    }
+    for (int x = threadIdx.x; x < wp; x += AUG_B) {
+        AUG_SP_FIR(ext, x + AUG_SP_R, 1);
+        tmp[out_row + x] = (float)acc;
+    }
+}
+
+// one block = AUG_COLS columns of one (sample, plane) over the whole reflected height: filtered along y
+__global__ __launch_bounds__(AUG_B) void aug_spline_col_kernel(const float* __restrict__ tmp, int hp, int wp, float* __restrict__ coeffs) {
+    __shared__ float col[(AUG_MAX_SIDE + 2 * AUG_SP_R) * AUG_COLS];
+    __shared__ double h[AUG_SP_R + 1];
+    __shared__ double line[AUG_SP_SHORT * AUG_COLS];
+    const int lx = threadIdx.x % AUG_COLS, ly = threadIdx.x / AUG_COLS, x = (int)blockIdx.x * AUG_COLS + lx;
+    const int64_t base = ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * hp * wp;
+    if (hp < AUG_SP_SHORT) {                                   // block-uniform: one thread per column
+        if (ly == 0 && x < wp) {
+            for (int y = 0; y < hp; ++y) line[y * AUG_COLS + lx] = (double)tmp[base + (int64_t)y * wp + x];
+            aug_spline_recursion(line + lx, hp, AUG_COLS);
+            for (int y = 0; y < hp; ++y) coeffs[base + (int64_t)y * wp + x] = (float)line[y * AUG_COLS + lx];
+        }
+        return;
+    }
+    aug_spline_taps(h);
+    for (int j = ly; j < hp + 2 * AUG_SP_R; j += AUG_B / AUG_COLS)
+        col[j * AUG_COLS + lx] = x < wp ? tmp[base + (int64_t)aug_reflect(j - AUG_SP_R, hp) * wp + x] : 0.f;
+    __syncthreads();
+    const float* cl = col + lx;
+    for (int y = ly; y < hp; y += AUG_B / AUG_COLS) {
+        AUG_SP_FIR(cl, y + AUG_SP_R, AUG_COLS);
+        if (x < wp) coeffs[base + (int64_t)y * wp + x] = (float)acc;
+    }
+}
+
+// min / max partials, rows, columns: 3 launches
+static void aug_spline_launch(const float* image, const int64_t* label, const float* intensity, int n, int hp, int wp, int n_class,
+                              void* workspace, float* coeffs, ctl_stream stream) {
+    float* partial = (float*)workspace;
+    float* tmp = (float*)((char*)workspace + aug_partial_bytes(n));
+    aug_minmax_partial_kernel<<<dim3(AUG_BPP, (unsigned)n), dim3(AUG_B), 0, S_>>>(image, hp * wp, partial);
+    aug_spline_row_kernel<<<dim3((unsigned)hp, (unsigned)(1 + n_class), (unsigned)n), dim3(AUG_B), 0, S_>>>(image, label, intensity, partial, hp, wp, tmp);
+    aug_spline_col_kernel<<<dim3((unsigned)ctl_cdiv(wp, AUG_COLS), (unsigned)(1 + n_class), (unsigned)n), dim3(AUG_B), 0, S_>>>(tmp, hp, wp, coeffs);
+}
+
+extern "C" int ctl_aug_spline_coeffs(const float* image, const int64_t* label, const float* intensity, int32_t n, int32_t hp, int32_t wp,
+                                     int32_t n_class, float* coeffs, void* workspace, size_t workspace_bytes, ctl_stream stream) {
+    CTL_REQUIRE(n > 0 && n <= 65535 && hp > 0 && wp > 0, "aug_spline_coeffs: n (1..65535), hp and wp must be positive (got %d, %d, %d)", n, hp, wp);
+    CTL_REQUIRE(hp <= AUG_MAX_SIDE && wp <= AUG_MAX_SIDE, "aug_spline_coeffs: the LDS staging holds planes up to %d x %d, got %d x %d", AUG_MAX_SIDE,
+                AUG_MAX_SIDE, hp, wp);
+    CTL_REQUIRE(n_class >= 0 && n_class <= AUG_MAX_CLASS, "aug_spline_coeffs: n_class must be 0..%d, got %d", AUG_MAX_CLASS, n_class);
+    CTL_REQUIRE(image && intensity, "aug_spline_coeffs: image and intensity (float [n,2]) are required");
+    CTL_REQUIRE(label || n_class == 0, "aug_spline_coeffs: n_class %d asks for indicator planes, but there is no label", n_class);
+    CTL_REQUIRE(coeffs, "aug_spline_coeffs: no output coeffs");
+    CTL_REQUIRE(workspace && ((uintptr_t)workspace & 255) == 0, "aug_spline_coeffs: the workspace must be a 256-byte aligned device buffer");
+    CTL_REQUIRE(workspace_bytes >= aug_spline_bytes(n, hp, wp, n_class), "aug_spline_coeffs: workspace of %zu bytes, ctl_aug_spline_ws_bytes asks for %zu",
+                workspace_bytes, aug_spline_bytes(n, hp, wp, n_class));
+    const size_t in_px = (size_t)n * hp * wp;
+    const aug_range r[] = {{coeffs, in_px * (1 + n_class) * 4}, {workspace, aug_spline_bytes(n, hp, wp, n_class)}, {image, in_px * 4},
+                           {n_class ? label : nullptr, in_px * 8}, {intensity, (size_t)n * 8}};
+    CTL_REQUIRE(!aug_any_overlap(r, 5, 2), "aug_spline_coeffs: coeffs and workspace must not overlap each other or an input");
+    aug_spline_launch(image, label, intensity, n, hp, wp, n_class, workspace, coeffs, stream);
+    ctl_count_launches(2);
+    CTL_LAUNCH_CHECK("aug_spline_coeffs");
+    return CTL_OK;
+}
+
+// cubic B-spline weights of the taps floor(s) - 1 .. floor(s) + 2 for t = s - floor(s)
+__device__ __forceinline__ void aug_bspline3(double t, double* __restrict__ w) {
+    const double u = 1.0 - t;
+    w[0] = u * u * u * (1.0 / 6.0);
+    w[1] = (4.0 - 6.0 * t * t + 3.0 * t * t * t) * (1.0 / 6.0);
+    w[2] = (4.0 - 6.0 * u * u + 3.0 * u * u * u) * (1.0 / 6.0);
+    w[3] = t * t * t * (1.0 / 6.0);
+}
+
+__global__ __launch_bounds__(AUG_B) void aug_warp_cubic_kernel(const float* __restrict__ coeffs, const float* __restrict__ matrix,
+                                                                const float* __restrict__ field, int hp, int wp, int hc, int wc, int cy, int cx,
+                                                                int n_class, float* __restrict__ image_out, int64_t* __restrict__ label_out) {
+    __shared__ float prm[6];
+    const int b = blockIdx.z;
+    if (threadIdx.x < 6) prm[threadIdx.x] = matrix[b * 6 + threadIdx.x];
+    __syncthreads();
+    const int x = (int)blockIdx.x * AUG_TW + (threadIdx.x & 63), y = (int)blockIdx.y * (AUG_B / AUG_TW) + (threadIdx.x >> 6);
+    if (x >= wc || y >= hc) return;
+    float sr, sc;
+    aug_source(field, prm, b, y, x, hp, wp, cy, cx, sr, sc);
+    const int64_t o = ((int64_t)b * hc + y) * wc + x;
+    if (!(sr >= -0.5f && sr <= (float)hp - 0.5f && sc >= -0.5f && sc <= (float)wp - 0.5f)) {      // a border pulled into view is zero
+        image_out[o] = 0.f;
+        label_out[o] = 0;
+        return;
+    }
+    const float fy0 = floorf(sr), fx0 = floorf(sc);
+    double wy[4], wx[4];                                       // formed once, shared by the 1 + n_class planes
+    aug_bspline3((double)(sr - fy0), wy);
+    aug_bspline3((double)(sc - fx0), wx);
+    int ry[4], rx[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) { ry[t] = aug_reflect((int)fy0 - 1 + t, hp) * wp; rx[t] = aug_reflect((int)fx0 - 1 + t, wp); }
+    const int64_t plane = (int64_t)hp * wp;
+    const float* cp = coeffs + (int64_t)b * (1 + n_class) * plane;
+    int64_t lv = 0;
+    for (int pl = 0; pl <= n_class; ++pl, cp += plane) {
+        double val = 0.0;                                      // 16 taps combined in fp64, rounded once
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const float* rp = cp + ry[t];
+            val += wy[t] * (wx[0] * (double)rp[rx[0]] + wx[1] * (double)rp[rx[1]] + wx[2] * (double)rp[rx[2]] + wx[3] * (double)rp[rx[3]]);
+        }
+        if (pl == 0) image_out[o] = (float)val;
+        else if (val >= 0.5) lv = pl - 1;                      // ascending: the largest class at or above 0.5 stays (elastic_transform.py:84-92)
+    }
+    label_out[o] = lv;
+}
+
+extern "C" int ctl_aug_warp_cubic(const float* image, const int64_t* label, const float* matrix, const float* intensity, const float* field,
+                                  int32_t n, int32_t hp, int32_t wp, int32_t hc, int32_t wc, int32_t n_class, float* image_out,
+                                  int64_t* label_out, void* workspace, size_t workspace_bytes, ctl_stream stream) {
+    CTL_REQUIRE(n > 0 && n <= 65535 && hp > 0 && wp > 0 && hc > 0 && wc > 0,
+                "aug_warp_cubic: n (1..65535) and every size must be positive (got n %d, %d x %d -> %d x %d)", n, hp, wp, hc, wc);
+    CTL_REQUIRE(hp <= AUG_MAX_SIDE && wp <= AUG_MAX_SIDE, "aug_warp_cubic: planes up to %d x %d (the LDS staging of the prefilter), got %d x %d",
+                AUG_MAX_SIDE, AUG_MAX_SIDE, hp, wp);
+    CTL_REQUIRE(hc <= hp && wc <= wp, "aug_warp_cubic: the crop %d x %d is larger than the input %d x %d", hc, wc, hp, wp);
+    CTL_REQUIRE(n_class >= 1 && n_class <= AUG_MAX_CLASS, "aug_warp_cubic: n_class must be 1..%d, got %d", AUG_MAX_CLASS, n_class);
+    CTL_REQUIRE(image && label, "aug_warp_cubic: image and label are both required");
+    CTL_REQUIRE(matrix && intensity, "aug_warp_cubic: matrix (float [n,2,3]) and intensity (float [n,2]) are required");
+    CTL_REQUIRE(image_out && label_out, "aug_warp_cubic: image_out and label_out are both required");
+    CTL_REQUIRE(workspace && ((uintptr_t)workspace & 255) == 0, "aug_warp_cubic: the workspace must be a 256-byte aligned device buffer");
+    CTL_REQUIRE(workspace_bytes >= aug_cubic_bytes(n, hp, wp, n_class), "aug_warp_cubic: workspace of %zu bytes, ctl_aug_warp_cubic_ws_bytes asks for %zu",
+                workspace_bytes, aug_cubic_bytes(n, hp, wp, n_class));
+    const size_t in_px = (size_t)n * hp * wp, out_px = (size_t)n * hc * wc;
+    const aug_range r[] = {{image_out, out_px * 4}, {label_out, out_px * 8}, {workspace, aug_cubic_bytes(n, hp, wp, n_class)}, {image, in_px * 4},
+                           {label, in_px * 8}, {field, in_px * 8}, {matrix, (size_t)n * 24}, {intensity, (size_t)n * 8}};
+    CTL_REQUIRE(!aug_any_overlap(r, 8, 3), "aug_warp_cubic: an output or the workspace overlaps another array (the gather reads whole coefficient planes)");
+    float* coeffs = (float*)((char*)workspace + aug_spline_bytes(n, hp, wp, n_class));
+    const int cy = (hp - hc + 1) / 2, cx = (wp - wc + 1) / 2;
+    aug_spline_launch(image, label, intensity, n, hp, wp, n_class, workspace, coeffs, stream);
+    aug_warp_cubic_kernel<<<dim3((unsigned)ctl_cdiv(wc, AUG_TW), (unsigned)ctl_cdiv(hc, AUG_B / AUG_TW), (unsigned)n), dim3(AUG_B), 0, S_>>>(
+        coeffs, matrix, field, hp, wp, hc, wc, cy, cx, n_class, image_out, label_out);
+    ctl_count_launches(3);
+    CTL_LAUNCH_CHECK("aug_warp_cubic");
     return CTL_OK;
 }

@@ -514,14 +514,55 @@ def aug_elastic_field(n: int, hp: int, wp: int, alpha, sigma, seed, noise: Optio
     return out
 
 
+def _aug_class_count(n_class, lo: int, who: str) -> int:
+    if n_class is None or not lo <= int(n_class) <= 16:
+        raise ValueError(f"{who}: n_class must be {lo}..16, got {n_class!r}")
+    return int(n_class)
+
+
+def aug_spline_coeffs(image: torch.Tensor, label: Optional[torch.Tensor] = None, intensity: Optional[torch.Tensor] = None, n_class: int = 0,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Cubic B-spline coefficients scipy.ndimage.spline_filter(v, order=3, mode='reflect') of a batch -> float32 [n,1+n_class,hp,wp]:
+    plane 0 of image float32 [n,1,hp,wp] through the intensity map (float32 [n,2] = (scale, brightness), clamped to the plane's min / max;
+    None = (1, 0)), plane 1 + k of the indicator label == k for k < n_class (label int64 [n,hp,wp]; not read when n_class is 0).  What
+    aug_warp(interp="cubic") gathers from.  3 launches, no readback."""
+    require_gpu(image, label, intensity)
+    if image.dim() != 4 or image.shape[1] != 1 or image.dtype != torch.float32:
+        raise ValueError(f"aug_spline_coeffs: image must be float32 [n,1,hp,wp], got {image.dtype} {tuple(image.shape)}")
+    n, _, hp, wp = (int(v) for v in image.shape)
+    n_class = _aug_class_count(n_class, 0, "aug_spline_coeffs")
+    if n_class and (label is None or label.dtype != torch.int64 or tuple(label.shape) != (n, hp, wp)):
+        raise ValueError(f"aug_spline_coeffs: n_class={n_class} needs label int64 [n,hp,wp] = {(n, hp, wp)}")
+    if intensity is None:
+        intensity = torch.zeros((n, 2), dtype=torch.float32, device=image.device)
+        intensity[:, 0] = 1.0
+    if intensity.dtype != torch.float32 or tuple(intensity.shape) != (n, 2):
+        raise ValueError(f"aug_spline_coeffs: intensity must be float32 [n,2], got {intensity.dtype} {tuple(intensity.shape)}")
+    ws, nbytes = _aug_ws(lib.ctl_aug_spline_ws_bytes(n, hp, wp, n_class), n, hp, wp, 1, 1, image.device, "aug_spline_coeffs")
+    if out is None:
+        out = torch.empty((n, 1 + n_class, hp, wp), dtype=torch.float32, device=image.device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (n, 1 + n_class, hp, wp) and out.is_contiguous()):
+        raise ValueError("aug_spline_coeffs: `out` must be a contiguous float32 device tensor [n,1+n_class,hp,wp]")
+    check(lib.ctl_aug_spline_coeffs(ptr(image.contiguous()), ptr(label.contiguous() if n_class else None), ptr(intensity.contiguous()), n, hp, wp,
+                                    n_class, ptr(out), ptr(ws), nbytes, stream_ptr()), "ctl_aug_spline_coeffs")
+    return out
+
+
 def aug_warp(image: torch.Tensor, label: torch.Tensor, matrix: torch.Tensor, intensity: torch.Tensor, crop,
-             field: Optional[torch.Tensor] = None, out=None):
+             field: Optional[torch.Tensor] = None, out=None, interp: str = "linear", n_class: Optional[int] = None):
     """One resampling of a batch (transform.py:46-82 without the normalisation): image float32 [n,1,hp,wp] and label int64 [n,hp,wp] ->
     (image [n,1,hc,wc], label [n,hc,wc]) for crop = (hc, wc), the centre window of MySpecialCrop.  matrix: float32 [n,2,3], the
     output -> input map about the plane centre in (row, col) order; intensity: float32 [n,2] = (scale, brightness) applied to every tap
     and clamped to the plane's min / max; field: float32 [n,2,hp,wp] from aug_elastic_field, None = no elastic.  Image taps are
     bilinear with zeros outside, label taps nearest.  `out` = (image_out, label_out): contiguous device tensors of the result's shapes
-    and dtypes that share no memory with each other or with any input (the gather reads whole input planes).  2 launches, no readback."""
+    and dtypes that share no memory with each other or with any input (the gather reads whole input planes).  2 launches, no readback.
+    interp="cubic": image and per-class label indicators (label == k for k < n_class, 1 <= n_class <= 16) are read through a cubic
+    spline, map_coordinates(order=3, mode='reflect') inside the array and 0 outside it, the label being the largest class at or above
+    0.5 (ctl_aug_warp_cubic in include/ctl_hip.h); 4 launches."""
+    if interp not in ("linear", "cubic"):
+        raise ValueError(f"aug_warp: interp must be 'linear' or 'cubic', got {interp!r}")
+    if interp == "cubic":
+        n_class = _aug_class_count(n_class, 1, "aug_warp(interp='cubic')")
     require_gpu(image, label, matrix, intensity, field)
     if image.dim() != 4 or image.shape[1] != 1 or image.dtype != torch.float32:
         raise ValueError(f"aug_warp: image must be float32 [n,1,hp,wp], got {image.dtype} {tuple(image.shape)}")
@@ -535,7 +576,8 @@ def aug_warp(image: torch.Tensor, label: torch.Tensor, matrix: torch.Tensor, int
     if field is not None and (field.dtype != torch.float32 or tuple(field.shape) != (n, 2, hp, wp)):
         raise ValueError(f"aug_warp: field must be float32 [n,2,hp,wp], got {field.dtype} {tuple(field.shape)}")
     hc, wc = int(crop[0]), int(crop[1])
-    ws, nbytes = _aug_ws(lib.ctl_aug_warp_ws_bytes(n, hp, wp, hc, wc), n, hp, wp, hc, wc, image.device, "aug_warp")
+    ws_bytes = lib.ctl_aug_warp_cubic_ws_bytes(n, hp, wp, hc, wc, n_class) if interp == "cubic" else lib.ctl_aug_warp_ws_bytes(n, hp, wp, hc, wc)
+    ws, nbytes = _aug_ws(ws_bytes, n, hp, wp, hc, wc, image.device, "aug_warp")
     if out is None:
         io = torch.empty((n, 1, hc, wc), dtype=torch.float32, device=image.device)
         lo = torch.empty((n, hc, wc), dtype=torch.int64, device=image.device)
@@ -545,7 +587,12 @@ def aug_warp(image: torch.Tensor, label: torch.Tensor, matrix: torch.Tensor, int
                 and lo.is_cuda and lo.dtype == torch.int64 and tuple(lo.shape) == (n, hc, wc) and lo.is_contiguous()):
             raise ValueError("aug_warp: `out` must be (float32 [n,1,hc,wc], int64 [n,hc,wc]) contiguous device tensors")
     image, label, matrix, intensity = image.contiguous(), label.contiguous(), matrix.contiguous(), intensity.contiguous()
-    check(lib.ctl_aug_warp(ptr(image), ptr(label), ptr(matrix), ptr(intensity), ptr(None if field is None else field.contiguous()), n, hp, wp,
+    field = None if field is None else field.contiguous()
+    if interp == "cubic":
+        check(lib.ctl_aug_warp_cubic(ptr(image), ptr(label), ptr(matrix), ptr(intensity), ptr(field), n, hp, wp, hc, wc, n_class, ptr(io), ptr(lo),
+                                     ptr(ws), nbytes, stream_ptr()), "ctl_aug_warp_cubic")
+        return io, lo
+    check(lib.ctl_aug_warp(ptr(image), ptr(label), ptr(matrix), ptr(intensity), ptr(field), n, hp, wp,
                            hc, wc, ptr(io), ptr(lo), ptr(ws), nbytes, stream_ptr()), "ctl_aug_warp")
     return io, lo
 

@@ -454,7 +454,7 @@ int ctl_cc_keep_largest(const uint8_t* labelmap, int32_t d, int32_t h, int32_t w
  *             (RandomBrightnessFluctuation with preserve_range, _utils/intensity_transform.py:136-162, which upstream applies pointwise
  *             before any geometry: the same function).  {1, 0} switches it off.  The taps are combined in fp64 and rounded once.
  *   label     nearest neighbour: the tap at floor(s + 0.5) per axis, 0 outside the array.  (Upstream's per-class cubic spline and
- *             threshold, _utils/elastic_transform.py:84-92, is deliberately not reproduced.)
+ *             threshold, _utils/elastic_transform.py:84-92, is what ctl_aug_warp_cubic below offers.)
  *   field     float [n,2,Hp,Wp], d of sample b = (field[b][0], field[b][1]); NULL = no elastic deformation for the whole batch.
  * ctl_aug_field: field[b][axis] = alpha[b] * G_sigma[b](u[b][axis]) (MyElasticTransform.gen_deformation_field, elastic_transform.py:41-58,
  *   with alpha / sigma drawn as in :72-75).  G_sigma = scipy.ndimage.gaussian_filter(mode='constant', cval=0, truncate=4.0): separable,
@@ -469,7 +469,33 @@ int ctl_cc_keep_largest(const uint8_t* labelmap, int32_t d, int32_t h, int32_t w
  * host synchronisation and no atomic: two calls give the same bits.  Workspaces are caller-owned, 256-byte aligned and sized by
  * ctl_aug_ws_bytes for ctl_aug_field (the row-filtered planes) and by ctl_aug_warp_ws_bytes for ctl_aug_warp (the min / max partials);
  * both return 0 for arguments the call would refuse.  No written array (field, image_out, label_out, a workspace) may overlap another
- * array of the same call. */
+ * array of the same call.
+ *
+ * Cubic-spline resampling (an option: ctl_aug_warp above is unchanged).  Source coordinates, crop window, field and the closing rescale are
+ * as above; only how a value is read at s changes.
+ *   coefficients  of a plane v [Hp,Wp]: C(v) = scipy.ndimage.spline_filter(v, order=3, mode='reflect'), the separable inverse of the cubic
+ *             B-spline under the half-sample symmetric extension d c b a | a b c d | d c b a, for any plane length (a line shorter than
+ *             the filter's reach is folded as often as it takes).  Per axis the one-pole recursion with z = sqrt(3) - 2 is the two-sided
+ *             sequence h[k] = (-6 z / (1 - z^2)) z^|k| = sqrt(3) z^|k| over the extended line; it is applied for |k| <= 40 (the dropped
+ *             tail is below 1e-23 of the sum), rows then columns, accumulated in fp64, each stage stored as fp32.  A line of fewer than
+ *             16 samples is where scipy itself leaves that inverse (its causal initialisation is off by about |z|^(2 len): 4e-7 at 5
+ *             samples, below 1e-17 from 16 on); such a line is filtered by scipy's own recursion, so the result is scipy's at any length.
+ *   value at s  if -0.5 <= s_r <= Hp - 0.5 and -0.5 <= s_c <= Wp - 0.5: the 4x4 cubic B-spline sum over C(v) at the taps floor(s) - 1 ..
+ *             floor(s) + 2 per axis with reflected tap indices = scipy.ndimage.map_coordinates(v, s, order=3, mode='reflect'); the 16 taps
+ *             are combined in fp64 and rounded once.  Otherwise 0: a border pulled into view is zero, as above.
+ *   image     v = clamp(x * scale + brightness, mn, mx), the intensity map above, applied pointwise (in fp64) to the padded plane before
+ *             the prefilter.
+ *   label     each indicator plane 1[label == k], k in [0, n_class), is resampled like the image; the output is the largest k whose value
+ *             is >= 0.5, and 0 if there is none or s is outside (upstream's ascending result[res_new >= 0.5] = c,
+ *             _utils/elastic_transform.py:84-92).  n_class <= 16 as for ctl_confusion_hist; a label outside [0, n_class) belongs to no
+ *             class.  The indicator planes are formed while a row is staged and never written.
+ * ctl_aug_spline_coeffs: coeffs float [n, 1 + n_class, Hp, Wp] = C of the image plane (plane 0) and of the n_class indicator planes;
+ *   n_class may be 0 (label may then be NULL).  3 launches: min / max partials, rows from an LDS-staged reflected row, columns from an
+ *   LDS-staged reflected 16-column tile.  Workspace: ctl_aug_spline_ws_bytes (the partials and the row-filtered planes).
+ * ctl_aug_warp_cubic: ctl_aug_warp's arguments plus n_class (1..16), 4 launches: the three above into the workspace, then one pass over
+ *   the crop window that writes image_out and label_out together, the tap weights formed once per pixel for all 1 + n_class planes.
+ *   Workspace: ctl_aug_warp_cubic_ws_bytes (the partials, the row-filtered planes and the coefficients).
+ * Limits, determinism, alignment and the overlap rule are those above; both size queries return 0 for arguments the call would refuse. */
 size_t ctl_aug_ws_bytes(int32_t n, int32_t hp, int32_t wp);
 size_t ctl_aug_warp_ws_bytes(int32_t n, int32_t hp, int32_t wp, int32_t hc, int32_t wc);
 int ctl_aug_field(const float* noise, const uint64_t* seeds, const float* alpha, const float* sigma, int32_t n, int32_t hp, int32_t wp,
@@ -477,6 +503,13 @@ int ctl_aug_field(const float* noise, const uint64_t* seeds, const float* alpha,
 int ctl_aug_warp(const float* image, const int64_t* label, const float* matrix, const float* intensity, const float* field, int32_t n,
                  int32_t hp, int32_t wp, int32_t hc, int32_t wc, float* image_out, int64_t* label_out, void* workspace,
                  size_t workspace_bytes, ctl_stream stream);
+size_t ctl_aug_spline_ws_bytes(int32_t n, int32_t hp, int32_t wp, int32_t n_class);
+size_t ctl_aug_warp_cubic_ws_bytes(int32_t n, int32_t hp, int32_t wp, int32_t hc, int32_t wc, int32_t n_class);
+int ctl_aug_spline_coeffs(const float* image, const int64_t* label, const float* intensity, int32_t n, int32_t hp, int32_t wp,
+                          int32_t n_class, float* coeffs, void* workspace, size_t workspace_bytes, ctl_stream stream);
+int ctl_aug_warp_cubic(const float* image, const int64_t* label, const float* matrix, const float* intensity, const float* field, int32_t n,
+                       int32_t hp, int32_t wp, int32_t hc, int32_t wc, int32_t n_class, float* image_out, int64_t* label_out,
+                       void* workspace, size_t workspace_bytes, ctl_stream stream);
 
 /* ------------------------------------------------------------------------------------------------ optimizer
  * torch.optim.Adam defaults (model.py:774-785), one flat buffer: p,g,m,v [count].  step = 1-based step index.

@@ -2,7 +2,9 @@
 training step it feeds.
 
 Batches of 16 slices, policy ACDC_affine_elastic_intensity, 224x224 -> 192x192 and 256x256 -> 256x256.  Per size two rows: the parameters
-as the policy draws them (elastic on for about half of the samples) and elastic forced on for all 16 (the worst case).  Per row:
+as the policy draws them (elastic on for about half of the samples) and elastic forced on for all 16 (the worst case); each row once per
+interpolation of --interp (linear: bilinear image / nearest label; cubic: cubic spline for both, 4 classes; both: the two side by side
+from the same run, on the same batch and parameters).  Per row:
   device   HIP events around one apply() on an idle stream, warm, median of repeated calls; eagerly and as the replay of a captured graph
   host     augment.apply_host on the same batch and parameters (fp64 numpy / scipy, one sample after the other: scipy.ndimage does not
            thread); wall time, with the number of CPUs the process may use
@@ -11,7 +13,7 @@ as the policy draws them (elastic on for about half of the samples) and elastic 
 Checks that device and host agree on the labels of the first row, and writes profiles/aug_batch.json.
 
     python bench.py --gpus 1 --steps 20 --warmup 5 > step_fp32.json
-    python tools/bench_aug.py --step-line step_fp32.json [--step-line step_bf16.json] [--out profiles/aug_batch.json]
+    python tools/bench_aug.py --interp both --step-line step_fp32.json [--step-line step_bf16.json] [--out profiles/aug_batch.json]
 """
 import argparse
 import json
@@ -32,6 +34,7 @@ from cooperative_training_and_latent_space_data_augmentation_amd.augment import 
 POLICY = "ACDC_affine_elastic_intensity"
 N = 16
 SIZES = [((224, 224), (192, 192)), ((256, 256), (256, 256))]
+CLASSES = 4                      # batch() draws the labels 0..3
 
 
 def batch(n, hp, wp, seed):
@@ -82,17 +85,19 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "aug_batch.json"))
     ap.add_argument("--device-reps", type=int, default=50)
     ap.add_argument("--host-reps", type=int, default=2)
+    ap.add_argument("--interp", choices=("linear", "cubic", "both"), default="both")
     ap.add_argument("--step-line", action="append", default=[], help="file holding the JSON line of a bench.py run of this session")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_aug.py measures on the GPU: no device found")
     steps = read_step_lines(args.step_line)
+    interps = ("linear", "cubic") if args.interp == "both" else (args.interp,)
     rows = []
     for (hp, wp), crop in SIZES:
         image_h, label_h = batch(N, hp, wp, 1)
         image, label = torch.from_numpy(image_h).cuda(), torch.from_numpy(label_h).cuda()
-        for forced in (False, True):
-            aug = BatchAugmenter(POLICY, crop, seed=0)
+        for forced, interp in ((f, i) for f in (False, True) for i in interps):
+            aug = BatchAugmenter(POLICY, crop, seed=0, interp=interp, num_classes=CLASSES if interp == "cubic" else None)
             p = aug.draw(N, hp, wp)
             if forced:
                 off = p["alpha"] == 0
@@ -118,12 +123,12 @@ def main():
             host = []
             for _ in range(args.host_reps):
                 t0 = time.perf_counter()
-                want_i, want_l = augment.apply_host(image_h, label_h, p)
+                want_i, want_l = augment.apply_host(image_h, label_h, p, interp=interp, n_class=aug.num_classes)
                 host.append((time.perf_counter() - t0) * 1e3)
             host_ms = statistics.median(host)
             agree = float((got_l.cpu().numpy() == want_l).mean())
             assert agree > 0.97, agree         # the fp32 / fp64 displacements differ by up to 4e-5 * alpha px: labels on a rounding boundary
-            rec = {"policy": POLICY, "batch": N, "input": [hp, wp], "crop": list(crop), "elastic_samples": int(p["elastic_on"].sum()),
+            rec = {"policy": POLICY, "interp": interp, "n_class": aug.num_classes, "batch": N, "input": [hp, wp], "crop": list(crop), "elastic_samples": int(p["elastic_on"].sum()),
                    "elastic_forced_on": forced, "sigma_px_max": float(p["sigma"].max()), "device_eager_ms": eager[0],
                    "device_eager_ms_min_max": [eager[1], eager[2]], "device_graph_replay_ms": replay[0],
                    "device_graph_replay_ms_min_max": [replay[1], replay[2]], "device_eager_wall_ms": wall_ms, "device_reps": args.device_reps,
@@ -134,10 +139,11 @@ def main():
                                       "host_over_step": host_ms / s["ms_per_step"]} for s in steps]}
             print(json.dumps(rec), flush=True)
             rows.append(rec)
-    out = {"what": "augment.BatchAugmenter.apply on one batch of 16 slices (ctl_aug_field 2 launches, ctl_aug_warp 2, ctl_rescale_intensity 2): "
+    out = {"what": "augment.BatchAugmenter.apply on one batch of 16 slices (ctl_aug_field 2 launches, ctl_aug_warp 2 or ctl_aug_warp_cubic 4, "
+                   "ctl_rescale_intensity 2): "
                    "device time between HIP events (median, warm), eager and as a graph replay, vs augment.apply_host (fp64 numpy / scipy) on "
                    "the same batch and parameters, and as a share of the training step of the bench.py runs of the same session",
-           "launches": "6 per batch with an elastic policy, whatever n is", "steps": steps,
+           "launches": "6 per batch with an elastic policy (8 with interp cubic), whatever n is", "interp": list(interps), "steps": steps,
            "device": torch.cuda.get_device_name(0), "arch": torch.cuda.get_device_properties(0).gcnArchName, "rocm": torch.version.hip,
            "torch": torch.__version__, "host_cpus_usable": len(os.sched_getaffinity(0)), "rows": rows}
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -6,7 +6,9 @@
 //   ctl_aug_warp    per-plane min / max partials, then one gather over the crop window: bilinear image taps through the intensity
 //                   map (intensity_transform.py:136-162), nearest-neighbour label
 //   ctl_aug_spline_coeffs / ctl_aug_warp_cubic   the same gather through a cubic spline (elastic_transform.py:84-92): B-spline coefficients
-//                   of the image and of every class indicator, then 4x4 taps; at the end of this file
+//                   of the image and of every class indicator, then 4x4 taps
+//   ctl_aug_bias    smooth multiplicative bias field, min-max normalisation, Gaussian noise (intensity_transform.py:373-546), a pre-pass
+//   ctl_aug_coarse_field   the displacement of the 3x3 coarse grid (elastic_transform.py:105-172); both at the end of this file
 // The contract of all of them is written out in include/ctl_hip.h.
 #include "ctl_common.h"
 
@@ -498,5 +500,229 @@ extern "C" int ctl_aug_warp_cubic(const float* image, const int64_t* label, cons
         coeffs, matrix, field, hp, wp, hc, wc, cy, cx, n_class, image_out, label_out);
     ctl_count_launches(3);
     CTL_LAUNCH_CHECK("aug_warp_cubic");
+    return CTL_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ bias field
+// MyRandomPurtarbationV2 (intensity_transform.py:373-546) as a pre-pass that writes a new image: the host fits the bicubic spline and hands
+// over its knots, coefficients and the normalisation scalar (the record of include/ctl_hip.h); launch 1 evaluates it per pixel (de Boor in
+// both axes from per-block LDS tables of the four non-zero basis values of every row and column), multiplies, and leaves min / max / sum
+// partials; launch 2 reduces them, normalises, adds the noise.  fp64 from the fp32 record, one rounding per launch.
+#define AUG_BIAS_FLOATS 192
+#define AUG_BIAS_KNOTS 16
+#define AUG_BIAS_COEF 12
+#define AUG_BIAS_MIN_SIDE 128
+#define AUG_BIAS_TY 8             // offsets into the record
+#define AUG_BIAS_TX 24
+#define AUG_BIAS_C 40
+#define AUG_COARSE_FLOATS 24
+
+static inline bool aug_bias_ok(int n, int hp, int wp) {
+    return n > 0 && n <= 65535 && hp == wp && (hp & 1) == 0 && hp >= AUG_BIAS_MIN_SIDE && hp <= AUG_MAX_SIDE;
+}
+static inline size_t aug_bias_plane_bytes(int n, int hp, int wp) { return aug_align((size_t)n * hp * wp * sizeof(float)); }
+static inline size_t aug_bias_partial_bytes(int n) { return aug_align((size_t)n * AUG_BPP * 3 * sizeof(double)); }
+static inline size_t aug_bias_bytes(int n, int hp, int wp) { return aug_bias_plane_bytes(n, hp, wp) + aug_bias_partial_bytes(n); }
+
+extern "C" size_t ctl_aug_bias_ws_bytes(int32_t n, int32_t hp, int32_t wp) { return aug_bias_ok(n, hp, wp) ? aug_bias_bytes(n, hp, wp) : 0; }
+
+// FITPACK's fpbspl for degree 3: x is clamped to [t[3], t[nt - 4]] (what bispev does with an argument beyond the data), l = the span with
+// t[l] <= x < t[l + 1] (the last one at the right end), h[0..3] = B_{l-3} .. B_l at x
+__device__ __forceinline__ int aug_bias_basis(const double* __restrict__ t, int nt, double x, double* __restrict__ h) {
+    x = fmin(fmax(x, t[3]), t[nt - 4]);
+    int l = 3;
+    while (l < nt - 5 && x >= t[l + 1]) ++l;
+    h[0] = 1.0;
+    h[1] = h[2] = h[3] = 0.0;
+#pragma unroll
+    for (int j = 1; j <= 3; ++j) {
+        double hh[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) hh[i] = h[i];
+        h[0] = 0.0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            if (i < j) {
+                const int li = l + 1 + i, lj = li - j;
+                const double f = hh[i] / (t[li] - t[lj]);
+                h[i] += f * (t[li] - x);
+                h[i + 1] = f * (x - t[lj]);
+            }
+        }
+    }
+    return l;
+}
+// knot count of an axis as the kernels use it: whatever the record holds, every index derived from it stays inside the record
+__device__ __forceinline__ int aug_bias_knots(float v) { return v >= 8.f && v <= (float)AUG_BIAS_KNOTS ? (int)v : 8; }
+
+// grid (AUG_BPP, n): a block strides over its sample's plane.  partial: double [n][AUG_BPP][3] = {min v, max v, sum of the input}
+__global__ __launch_bounds__(AUG_B) void aug_bias_field_kernel(const float* __restrict__ image, const float* __restrict__ bias, int side,
+                                                                float* __restrict__ v_out, double* __restrict__ partial) {
+    __shared__ double ty[AUG_BIAS_KNOTS], tx[AUG_BIAS_KNOTS], cf[AUG_BIAS_COEF * AUG_BIAS_COEF];
+    __shared__ double by[AUG_MAX_SIDE * 4], bx[AUG_MAX_SIDE * 4];
+    __shared__ unsigned char ly[AUG_MAX_SIDE], lx[AUG_MAX_SIDE];
+    __shared__ double red[3 * AUG_B / 64];
+    const int b = blockIdx.y;
+    const float* rec = bias + (int64_t)b * AUG_BIAS_FLOATS;
+    if (rec[0] == 0.f) return;                                 // block-uniform: launch 2 copies this sample through
+    const int nty = aug_bias_knots(rec[1]), ntx = aug_bias_knots(rec[2]);
+    if (threadIdx.x < AUG_BIAS_KNOTS) { ty[threadIdx.x] = (double)rec[AUG_BIAS_TY + threadIdx.x]; tx[threadIdx.x] = (double)rec[AUG_BIAS_TX + threadIdx.x]; }
+    if (threadIdx.x < AUG_BIAS_COEF * AUG_BIAS_COEF) cf[threadIdx.x] = (double)rec[AUG_BIAS_C + threadIdx.x];
+    __syncthreads();
+    const int half = side / 2;                                 // pixel (y, x) sits at (y - Hp / 2, x - Wp / 2) of the knot grid
+    for (int i = threadIdx.x; i < 2 * side; i += AUG_B) {
+        const bool rows = i < side;
+        const int p = rows ? i : i - side;
+        double h[4];
+        const int l = aug_bias_basis(rows ? ty : tx, rows ? nty : ntx, (double)(p - half), h);
+        double* dst = (rows ? by : bx) + p * 4;
+        dst[0] = h[0]; dst[1] = h[1]; dst[2] = h[2]; dst[3] = h[3];
+        (rows ? ly : lx)[p] = (unsigned char)(l - 3);
+    }
+    __syncthreads();
+    const double scale = (double)rec[3], lo = 1.0 - (double)rec[4], hi = 1.0 + (double)rec[4];
+    const int plane = side * side;
+    const float* ip = image + (int64_t)b * plane;
+    float* vp = v_out + (int64_t)b * plane;
+    double mn = INFINITY, mx = -INFINITY, sum = 0.0;
+    for (int i = (int)blockIdx.x * AUG_B + threadIdx.x; i < plane; i += AUG_BPP * AUG_B) {
+        const int y = i / side, x = i - y * side;
+        const double* hy = by + y * 4;
+        const double* hx = bx + x * 4;
+        const double* c = cf + (int)ly[y] * AUG_BIAS_COEF + (int)lx[x];
+        double s = 0.0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            s += hy[r] * (hx[0] * c[r * AUG_BIAS_COEF] + hx[1] * c[r * AUG_BIAS_COEF + 1] + hx[2] * c[r * AUG_BIAS_COEF + 2] + hx[3] * c[r * AUG_BIAS_COEF + 3]);
+        const float pix = ip[i];
+        const float v = (float)((double)pix * fmin(fmax(scale * s, lo), hi));
+        vp[i] = v;
+        mn = fmin(mn, (double)v); mx = fmax(mx, (double)v); sum += (double)pix;
+    }
+    for (int o = 32; o > 0; o >>= 1) { mn = fmin(mn, __shfl_xor(mn, o)); mx = fmax(mx, __shfl_xor(mx, o)); }
+    sum = wave_sum_double(sum);
+    const int wv = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { red[wv * 3] = mn; red[wv * 3 + 1] = mx; red[wv * 3 + 2] = sum; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int i = 1; i < AUG_B / 64; ++i) { mn = fmin(mn, red[i * 3]); mx = fmax(mx, red[i * 3 + 1]); sum += red[i * 3 + 2]; }
+        double* pp = partial + ((int64_t)b * AUG_BPP + blockIdx.x) * 3;
+        pp[0] = mn; pp[1] = mx; pp[2] = sum;
+    }
+}
+
+// standard normal from (seed, sample, pixel): the counter hash and the two uniforms of ctl_noise_clamp, Box-Muller in fp64
+__device__ __forceinline__ double aug_normal(uint64_t seed, int sample, int pixel) {
+    const uint64_t h = aug_mix(seed ^ aug_mix(((uint64_t)(uint32_t)sample << 32) | (uint32_t)pixel));
+    const double u1 = (double)((h >> 40) + 1) * (1.0 / 16777216.0);          // (0, 1]
+    const double u2 = (double)((h >> 8) & 0xFFFFFFu) * (1.0 / 16777216.0);   // [0, 1)
+    return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+}
+
+__global__ __launch_bounds__(AUG_B) void aug_bias_norm_kernel(const float* __restrict__ image, const float* __restrict__ v,
+                                                               const float* __restrict__ bias, const double* __restrict__ partial,
+                                                               const float* __restrict__ noise, const uint64_t* __restrict__ seeds, int plane,
+                                                               float* __restrict__ out) {
+    __shared__ double st[3];
+    const int b = blockIdx.y;
+    const float* rec = bias + (int64_t)b * AUG_BIAS_FLOATS;
+    const bool on = rec[0] != 0.f;                             // block-uniform
+    if (on && threadIdx.x < 64) {                              // AUG_BPP partials = one wave, combined in a fixed order
+        const double* pp = partial + ((int64_t)b * AUG_BPP + threadIdx.x) * 3;
+        double mn = pp[0], mx = pp[1];
+        for (int o = 32; o > 0; o >>= 1) { mn = fmin(mn, __shfl_xor(mn, o)); mx = fmax(mx, __shfl_xor(mx, o)); }
+        const double sum = wave_sum_double(pp[2]);
+        if (threadIdx.x == 0) { st[0] = mn; st[1] = mx; st[2] = sum; }
+    }
+    __syncthreads();
+    const float* ip = image + (int64_t)b * plane;
+    float* op = out + (int64_t)b * plane;
+    if (!on || !(fabs(st[2]) > 1e-6)) {                        // stage off, or a black plane: bit for bit
+        for (int i = (int)blockIdx.x * AUG_B + threadIdx.x; i < plane; i += AUG_BPP * AUG_B) op[i] = ip[i];
+        return;
+    }
+    const double mn = st[0], den = (st[1] - st[0]) + 1e-8, eps = (double)rec[5];
+    const float* vp = v + (int64_t)b * plane;
+    const uint64_t seed = seeds ? seeds[b] : 0;
+    for (int i = (int)blockIdx.x * AUG_B + threadIdx.x; i < plane; i += AUG_BPP * AUG_B) {
+        double o = ((double)vp[i] - mn) / den;
+        if (eps > 0.0) {
+            const double nz = noise ? (double)noise[(int64_t)b * plane + i] : aug_normal(seed, b, i);
+            o = fmin(fmax(o + eps * nz, 0.0), 1.0);
+        }
+        op[i] = (float)o;
+    }
+}
+
+extern "C" int ctl_aug_bias(const float* image, const float* bias, const float* noise, const uint64_t* seeds, int32_t n, int32_t hp, int32_t wp,
+                            float* out, void* workspace, size_t workspace_bytes, ctl_stream stream) {
+    CTL_REQUIRE(n > 0 && n <= 65535, "aug_bias: n must be 1..65535, got %d", n);
+    CTL_REQUIRE(hp == wp && (hp & 1) == 0 && hp >= AUG_BIAS_MIN_SIDE && hp <= AUG_MAX_SIDE,
+                "aug_bias: the plane must be square with an even side of %d..%d (intensity_transform.py:439, :448), got %d x %d", AUG_BIAS_MIN_SIDE,
+                AUG_MAX_SIDE, hp, wp);
+    CTL_REQUIRE(image && bias, "aug_bias: image and bias (float [n,%d]) are required", AUG_BIAS_FLOATS);
+    CTL_REQUIRE(noise || seeds, "aug_bias: neither a noise array nor per-sample seeds");
+    CTL_REQUIRE(out, "aug_bias: no output image");
+    CTL_REQUIRE(workspace && ((uintptr_t)workspace & 255) == 0, "aug_bias: the workspace must be a 256-byte aligned device buffer");
+    CTL_REQUIRE(workspace_bytes >= aug_bias_bytes(n, hp, wp), "aug_bias: workspace of %zu bytes, ctl_aug_bias_ws_bytes asks for %zu", workspace_bytes,
+                aug_bias_bytes(n, hp, wp));
+    const size_t px = (size_t)n * hp * wp * sizeof(float);
+    const aug_range r[] = {{out, px}, {workspace, aug_bias_bytes(n, hp, wp)}, {image, px}, {noise, px}, {bias, (size_t)n * AUG_BIAS_FLOATS * 4},
+                           {seeds, (size_t)n * 8}};
+    CTL_REQUIRE(!aug_any_overlap(r, 6, 2), "aug_bias: out and workspace must not overlap each other or an input");
+    float* v = (float*)workspace;
+    double* partial = (double*)((char*)workspace + aug_bias_plane_bytes(n, hp, wp));
+    aug_bias_field_kernel<<<dim3(AUG_BPP, (unsigned)n), dim3(AUG_B), 0, S_>>>(image, bias, hp, v, partial);
+    aug_bias_norm_kernel<<<dim3(AUG_BPP, (unsigned)n), dim3(AUG_B), 0, S_>>>(image, v, bias, partial, noise, seeds, hp * wp, out);
+    ctl_count_launches(1);
+    CTL_LAUNCH_CHECK("aug_bias");
+    return CTL_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ coarse-grid displacement
+// MyElasticTransformCoarseGrid.gen_deformation_field (elastic_transform.py:121-137): two 3x3 planes resized to Hp x Wp by a cubic spline
+// under the whole-sample symmetric extension c b | a b c | b a, clipped to the planes' own range.  The host hands over the prefiltered
+// coefficients and the clip bounds; one launch, 4x4 taps per pixel in fp64, rounded once.
+__device__ __forceinline__ int aug_mirror3(int i) {
+    int m = i % 4;
+    if (m < 0) m += 4;
+    return m < 3 ? m : 4 - m;
+}
+__global__ __launch_bounds__(AUG_B) void aug_coarse_field_kernel(const float* __restrict__ coarse, int hp, int wp, float* __restrict__ field) {
+    const int b = blockIdx.z, a = blockIdx.y;
+    const float* rec = coarse + (int64_t)b * AUG_COARSE_FLOATS;
+    const int i = (int)blockIdx.x * AUG_B + threadIdx.x;
+    if (i >= hp * wp) return;
+    float* fp = field + ((int64_t)b * 2 + a) * hp * wp;
+    if (rec[22] == 0.f) { fp[i] = 0.f; return; }              // block-uniform
+    const int r = i / wp, c = i - r * wp;
+    const double sy = ((double)r + 0.5) * (3.0 / (double)hp) - 0.5, sx = ((double)c + 0.5) * (3.0 / (double)wp) - 0.5;
+    const double fy = floor(sy), fx = floor(sx);
+    double wy[4], wx[4];
+    aug_bspline3(sy - fy, wy);
+    aug_bspline3(sx - fx, wx);
+    const float* cf = rec + a * 9;
+    double val = 0.0;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const float* rp = cf + aug_mirror3((int)fy - 1 + t) * 3;
+        double row = 0.0;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) row += wx[u] * (double)rp[aug_mirror3((int)fx - 1 + u)];
+        val += wy[t] * row;
+    }
+    fp[i] = (float)fmin(fmax(val, (double)rec[18 + a * 2]), (double)rec[19 + a * 2]);
+}
+
+extern "C" int ctl_aug_coarse_field(const float* coarse, int32_t n, int32_t hp, int32_t wp, float* field, ctl_stream stream) {
+    CTL_REQUIRE(n > 0 && n <= 65535 && hp > 0 && wp > 0, "aug_coarse_field: n (1..65535), hp and wp must be positive (got %d, %d, %d)", n, hp, wp);
+    CTL_REQUIRE(hp <= AUG_MAX_SIDE && wp <= AUG_MAX_SIDE, "aug_coarse_field: planes up to %d x %d (the limit of ctl_aug_warp), got %d x %d", AUG_MAX_SIDE,
+                AUG_MAX_SIDE, hp, wp);
+    CTL_REQUIRE(coarse, "aug_coarse_field: coarse (float [n,%d]) is required", AUG_COARSE_FLOATS);
+    CTL_REQUIRE(field, "aug_coarse_field: no output field");
+    const aug_range r[] = {{field, (size_t)n * 2 * hp * wp * sizeof(float)}, {coarse, (size_t)n * AUG_COARSE_FLOATS * 4}};
+    CTL_REQUIRE(!aug_any_overlap(r, 2, 1), "aug_coarse_field: field must not overlap coarse");
+    aug_coarse_field_kernel<<<dim3((unsigned)ctl_cdiv(hp * wp, AUG_B), 2, (unsigned)n), dim3(AUG_B), 0, S_>>>(coarse, hp, wp, field);
+    CTL_LAUNCH_CHECK("aug_coarse_field");
     return CTL_OK;
 }

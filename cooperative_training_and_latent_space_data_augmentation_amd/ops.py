@@ -514,6 +514,64 @@ def aug_elastic_field(n: int, hp: int, wp: int, alpha, sigma, seed, noise: Optio
     return out
 
 
+BIAS_FLOATS = 192                    # floats of one sample's record of ctl_aug_bias / ctl_aug_coarse_field (include/ctl_hip.h)
+COARSE_FLOATS = 24
+
+
+def aug_bias_field(image: torch.Tensor, bias: torch.Tensor, seed=None, noise: Optional[torch.Tensor] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Bias-field pre-pass of `MyRandomPurtarbationV2` (intensity_transform.py:373-546) for a batch: image float32 [n,1,hp,hp] -> a new
+    float32 [n,1,hp,hp] = the image times the clipped bicubic field of each sample's record, min-max normalised, plus eps * N(0, 1) clipped
+    to [0, 1] when the record's eps is positive.  bias: float32 device tensor [n,192], the record of include/ctl_hip.h
+    (augment.bias_record); N: `noise` (float32 [n,1,hp,hp]) when given, else standard normals from the counter hash of (seed, sample,
+    pixel), seed a scalar or one int64 per sample (None = 0).  A sample whose record is off and a black plane are copied bit for bit.
+    hp == wp, even, 128..512.  2 launches, no readback."""
+    require_gpu(image, bias, noise)
+    if image.dim() != 4 or image.shape[1] != 1 or image.dtype != torch.float32:
+        raise ValueError(f"aug_bias_field: image must be float32 [n,1,hp,wp], got {image.dtype} {tuple(image.shape)}")
+    n, _, hp, wp = (int(v) for v in image.shape)
+    if hp != wp or hp % 2 or not 128 <= hp <= 512:
+        raise ValueError(f"aug_bias_field: the plane must be square with an even side of 128..512, got {hp}x{wp}")
+    if bias.dtype != torch.float32 or tuple(bias.shape) != (n, BIAS_FLOATS):
+        raise ValueError(f"aug_bias_field: bias must be float32 [n,{BIAS_FLOATS}] = {(n, BIAS_FLOATS)}, got {bias.dtype} {tuple(bias.shape)}")
+    if noise is not None:
+        if tuple(noise.shape) != (n, 1, hp, wp) or noise.dtype != torch.float32:
+            raise ValueError(f"aug_bias_field: noise must be float32 [n,1,hp,wp] = {(n, 1, hp, wp)}, got {noise.dtype} {tuple(noise.shape)}")
+        noise = noise.contiguous()
+    sd = _aug_vec(0 if seed is None else seed, n, torch.int64, image.device, "aug_bias_field", "seed")
+    ws, nbytes = _aug_ws(lib.ctl_aug_bias_ws_bytes(n, hp, wp), n, hp, wp, hp, wp, image.device, "aug_bias_field")
+    if out is None:
+        out = torch.empty((n, 1, hp, wp), dtype=torch.float32, device=image.device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (n, 1, hp, wp) and out.is_contiguous()):
+        raise ValueError("aug_bias_field: `out` must be a contiguous float32 device tensor [n,1,hp,wp]")
+    check(lib.ctl_aug_bias(ptr(image.contiguous()), ptr(bias.contiguous()), ptr(noise), ptr(sd), n, hp, wp, ptr(out), ptr(ws), nbytes,
+                           stream_ptr()), "ctl_aug_bias")
+    return out
+
+
+def aug_coarse_field(n: int, hp: int, wp: int, coarse: torch.Tensor, device=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Displacement of `MyElasticTransformCoarseGrid` (elastic_transform.py:105-172) for a batch -> float32 device tensor [n,2,hp,wp]
+    (rows, cols): each sample's two 3x3 planes resized by a cubic spline (scipy.ndimage.zoom(order=3, mode='mirror', grid_mode=True))
+    and clipped to their own range.  coarse: float32 [n,24], the record of include/ctl_hip.h (augment.coarse_record: prefiltered
+    coefficients, clip bounds, on); a host tensor is uploaded, a device tensor is read by the kernel.  A sample that is off gets zeros.
+    hp, wp <= 512.  1 launch."""
+    n, hp, wp = int(n), int(hp), int(wp)
+    if not isinstance(coarse, torch.Tensor) or coarse.dtype != torch.float32 or tuple(coarse.shape) != (n, COARSE_FLOATS):
+        raise ValueError(f"aug_coarse_field: coarse must be a float32 tensor [n,{COARSE_FLOATS}] = {(n, COARSE_FLOATS)}, got "
+                         f"{getattr(coarse, 'dtype', type(coarse))} {tuple(getattr(coarse, 'shape', ()))}")
+    if n < 1 or n > 65535 or hp < 1 or wp < 1 or hp > 512 or wp > 512:
+        raise ValueError(f"aug_coarse_field: n={n}, {hp}x{wp} is refused: sizes must be positive and planes at most 512x512")
+    if device is None:
+        device = coarse.device if coarse.is_cuda else torch.device("cuda")
+    coarse = coarse.to(device).contiguous()
+    if out is None:
+        out = torch.empty((n, 2, hp, wp), dtype=torch.float32, device=device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (n, 2, hp, wp) and out.is_contiguous()):
+        raise ValueError("aug_coarse_field: `out` must be a contiguous float32 device tensor [n,2,hp,wp]")
+    check(lib.ctl_aug_coarse_field(ptr(coarse), n, hp, wp, ptr(out), stream_ptr()), "ctl_aug_coarse_field")
+    return out
+
+
 def _aug_class_count(n_class, lo: int, who: str) -> int:
     if n_class is None or not lo <= int(n_class) <= 16:
         raise ValueError(f"{who}: n_class must be {lo}..16, got {n_class!r}")

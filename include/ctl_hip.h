@@ -495,7 +495,36 @@ int ctl_cc_keep_largest(const uint8_t* labelmap, int32_t d, int32_t h, int32_t w
  * ctl_aug_warp_cubic: ctl_aug_warp's arguments plus n_class (1..16), 4 launches: the three above into the workspace, then one pass over
  *   the crop window that writes image_out and label_out together, the tap weights formed once per pixel for all 1 + n_class planes.
  *   Workspace: ctl_aug_warp_cubic_ws_bytes (the partials, the row-filtered planes and the coefficients).
- * Limits, determinism, alignment and the overlap rule are those above; both size queries return 0 for arguments the call would refuse. */
+ * Limits, determinism, alignment and the overlap rule are those above; both size queries return 0 for arguments the call would refuse.
+ *
+ * Bias field and coarse-grid displacement: the two stages of transform.py:46-86 that BatchAugmenter.from_config adds to the chain above.
+ * Both take their per-sample parameters as a float record that the host fills (augment.bias_record / augment.coarse_record).
+ * ctl_aug_bias: MyRandomPurtarbationV2 (_utils/intensity_transform.py:373-546; the constructor pins the control-point spacing to 64, :404)
+ *   as a pre-pass image float [n,1,Hp,Wp] -> out of the same shape, which the warp then reads.  Upstream fits
+ *   RectBivariateSpline(x, x, z, s=3) through z = 1 + U(-m, m) on x = arange(-xmax, xmax + 1, 64), xmax = (Hp + 96) // 2, evaluates it on
+ *   arange(-xmax, xmax)^2 (an argument beyond the last data point is clamped by FITPACK), multiplies by h w / (sum + 1e-12) and keeps the
+ *   centre Hp x Wp window: pixel (y, x) sits at the argument (y - Hp / 2, x - Wp / 2).  The fit and the sum are the host's (the sum from
+ *   separability, in fp64); the record bias float [n,192] of sample b holds
+ *     [0] on (0 = the sample is copied through)   [1] knots along the rows   [2] knots along the columns (8..16 each)
+ *     [3] scale = h w / (sum + 1e-12)   [4] m   [5] eps (0 = no noise)   [6..7] unused
+ *     [8..23] row knots   [24..39] column knots   [40..183] B-spline coefficients, entry (i, j) at 40 + 12 i + j   [184..191] unused
+ *   Launch 1, per pixel: the span of each axis and its four non-zero cubic basis values (FITPACK's fpbspl; the argument clamped to
+ *   [t[3], t[nt - 4]]), S = the 4x4 sum, v = image * clamp(scale * S, 1 - m, 1 + m), all in fp64 from the fp32 record and rounded once,
+ *   written to the workspace with per-plane {min v, max v, sum of the input} partials (64 blocks per plane, the scheme of ctl_aug_warp /
+ *   ctl_rescale_intensity, as doubles).  Launch 2: the partials reduced in a fixed order, out = (v - min) / (max - min + 1e-8), and with
+ *   eps > 0 out = clamp(out + eps * N, 0, 1), in fp64 and rounded once; N = noise (float [n,1,Hp,Wp]) when given, else the standard normal
+ *   sqrt(-2 ln u1) cos(2 pi u2) in fp64 with u1 = 2^-24 ((h >> 40) + 1), u2 = 2^-24 ((h >> 8) & 0xFFFFFF) for the counter hash h of
+ *   (seeds[b], b, y * Wp + x) (the hash and the uniforms of ctl_noise_clamp, keyed like ctl_aug_field).  A sample that is off and a plane
+ *   with |sum of the input| <= 1e-6 (upstream's black image, :436) are copied bit for bit.  Hp == Wp, even, 128..512 (upstream's own
+ *   assertions, :439 and :448).  Workspace: ctl_aug_bias_ws_bytes (v and the partials).
+ * ctl_aug_coarse_field: MyElasticTransformCoarseGrid.gen_deformation_field (_utils/elastic_transform.py:105-172): two 3x3 planes of N(0, 10)
+ *   pixels resized to Hp x Wp = scipy.ndimage.zoom(m, (Hp / 3, Wp / 3), order=3, mode='mirror', grid_mode=True) clipped to [min m, max m]
+ *   (what skimage.transform.resize(order=3, mode='reflect') documents from 0.19 on): the cubic B-spline sum over
+ *   spline_filter(m, order=3, mode='mirror') at ((r + 0.5) 3 / Hp - 0.5, (c + 0.5) 3 / Wp - 0.5) with the tap indices mirrored about the
+ *   first and last sample (c b | a b c | b a).  The record coarse float [n,24] of sample b holds [0..8] the coefficients of the row
+ *   displacement, [9..17] of the column displacement, [18..21] {min, max} of either plane, [22] on, [23] unused.  1 launch: weights and
+ *   sum in fp64, clipped, rounded once into field float [n,2,Hp,Wp] (the field argument of ctl_aug_warp); zeros for a sample that is off.
+ *   Any Hp, Wp <= 512; no workspace. */
 size_t ctl_aug_ws_bytes(int32_t n, int32_t hp, int32_t wp);
 size_t ctl_aug_warp_ws_bytes(int32_t n, int32_t hp, int32_t wp, int32_t hc, int32_t wc);
 int ctl_aug_field(const float* noise, const uint64_t* seeds, const float* alpha, const float* sigma, int32_t n, int32_t hp, int32_t wp,
@@ -510,6 +539,10 @@ int ctl_aug_spline_coeffs(const float* image, const int64_t* label, const float*
 int ctl_aug_warp_cubic(const float* image, const int64_t* label, const float* matrix, const float* intensity, const float* field, int32_t n,
                        int32_t hp, int32_t wp, int32_t hc, int32_t wc, int32_t n_class, float* image_out, int64_t* label_out,
                        void* workspace, size_t workspace_bytes, ctl_stream stream);
+size_t ctl_aug_bias_ws_bytes(int32_t n, int32_t hp, int32_t wp);
+int ctl_aug_bias(const float* image, const float* bias, const float* noise, const uint64_t* seeds, int32_t n, int32_t hp, int32_t wp,
+                 float* out, void* workspace, size_t workspace_bytes, ctl_stream stream);
+int ctl_aug_coarse_field(const float* coarse, int32_t n, int32_t hp, int32_t wp, float* field, ctl_stream stream);
 
 /* ------------------------------------------------------------------------------------------------ optimizer
  * torch.optim.Adam defaults (model.py:774-785), one flat buffer: p,g,m,v [count].  step = 1-based step index.

@@ -11,9 +11,13 @@ from the same run, on the same batch and parameters).  Per row:
   launches kernels enqueued per apply() (the library's census)
   share    device time / step time, for every step time given with --step-line (the JSON line of a `bench.py` run of the same session)
 Checks that device and host agree on the labels of the first row, and writes profiles/aug_batch.json.
+--config v2 / coarse measures a config-dict chain (BatchAugmenter.from_config) in place of the policy: upstream's ACDC_affine_all config
+(bias field + Gaussian elastic + intensity) or its ACDC_affine_elastic_intensity_v2 config (coarse-grid elastic + intensity); the
+"forced" row then sets the probabilities of those stages to 1.
 
     python bench.py --gpus 1 --steps 20 --warmup 5 > step_fp32.json
     python tools/bench_aug.py --interp both --step-line step_fp32.json [--step-line step_bf16.json] [--out profiles/aug_batch.json]
+    python tools/bench_aug.py --config v2 --interp linear --out profiles/aug_batch_v2.json
 """
 import argparse
 import json
@@ -35,6 +39,19 @@ POLICY = "ACDC_affine_elastic_intensity"
 N = 16
 SIZES = [((224, 224), (192, 192)), ((256, 256), (256, 256))]
 CLASSES = 4                      # batch() draws the labels 0..3
+CONFIGS = {"v2": "ACDC_affine_all", "coarse": "ACDC_affine_elastic_intensity_v2"}       # --config: the upstream config each choice measures
+
+
+def make_augmenter(choice, forced, crop, interp):
+    """(augmenter, what it is called) for one row."""
+    kw = dict(seed=0, interp=interp, num_classes=CLASSES if interp == "cubic" else None)
+    if choice == "policy":
+        return BatchAugmenter(POLICY, crop, **kw), POLICY
+    config = augment.reference_config(CONFIGS[choice])
+    if forced:
+        for k in ("elastic_prob", "elastic_probv2", "perturb_v2_prob"):
+            config[k] = 1.0 if config[k] > 0 else config[k]
+    return BatchAugmenter.from_config(config, crop, **kw), "config of " + CONFIGS[choice]
 
 
 def batch(n, hp, wp, seed):
@@ -86,6 +103,8 @@ def main():
     ap.add_argument("--device-reps", type=int, default=50)
     ap.add_argument("--host-reps", type=int, default=2)
     ap.add_argument("--interp", choices=("linear", "cubic", "both"), default="both")
+    ap.add_argument("--config", choices=("policy",) + tuple(CONFIGS), default="policy",
+                    help="policy: BatchAugmenter(%s); v2 / coarse: from_config of upstream's %s / %s config" % ((POLICY,) + tuple(CONFIGS.values())))
     ap.add_argument("--step-line", action="append", default=[], help="file holding the JSON line of a bench.py run of this session")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -97,9 +116,9 @@ def main():
         image_h, label_h = batch(N, hp, wp, 1)
         image, label = torch.from_numpy(image_h).cuda(), torch.from_numpy(label_h).cuda()
         for forced, interp in ((f, i) for f in (False, True) for i in interps):
-            aug = BatchAugmenter(POLICY, crop, seed=0, interp=interp, num_classes=CLASSES if interp == "cubic" else None)
+            aug, what = make_augmenter(args.config, forced, crop, interp)
             p = aug.draw(N, hp, wp)
-            if forced:
+            if forced and args.config == "policy":
                 off = p["alpha"] == 0
                 p["alpha"][off] = float(np.float32(1.75 * hp))
                 p["elastic_on"][:] = True
@@ -128,8 +147,10 @@ def main():
             host_ms = statistics.median(host)
             agree = float((got_l.cpu().numpy() == want_l).mean())
             assert agree > 0.97, agree         # the fp32 / fp64 displacements differ by up to 4e-5 * alpha px: labels on a rounding boundary
-            rec = {"policy": POLICY, "interp": interp, "n_class": aug.num_classes, "batch": N, "input": [hp, wp], "crop": list(crop), "elastic_samples": int(p["elastic_on"].sum()),
-                   "elastic_forced_on": forced, "sigma_px_max": float(p["sigma"].max()), "device_eager_ms": eager[0],
+            on = {k: (None if p.get(k) is None else int(p[k].sum())) for k in ("bias_on", "coarse_on")}
+            rec = {"policy": what, "interp": interp, "n_class": aug.num_classes, "batch": N, "input": [hp, wp], "crop": list(crop), "elastic_samples": int(p["elastic_on"].sum()),
+                   "bias_samples": on["bias_on"], "coarse_samples": on["coarse_on"],
+                   "elastic_forced_on": forced, "sigma_px_max": None if p["sigma"] is None else float(p["sigma"].max()), "device_eager_ms": eager[0],
                    "device_eager_ms_min_max": [eager[1], eager[2]], "device_graph_replay_ms": replay[0],
                    "device_graph_replay_ms_min_max": [replay[1], replay[2]], "device_eager_wall_ms": wall_ms, "device_reps": args.device_reps,
                    "kernel_launches_per_batch": launches, "host_ms": host_ms, "host_ms_per_slice": host_ms / N, "host_reps": args.host_reps,
@@ -140,10 +161,10 @@ def main():
             print(json.dumps(rec), flush=True)
             rows.append(rec)
     out = {"what": "augment.BatchAugmenter.apply on one batch of 16 slices (ctl_aug_field 2 launches, ctl_aug_warp 2 or ctl_aug_warp_cubic 4, "
-                   "ctl_rescale_intensity 2): "
+                   "ctl_rescale_intensity 2; with --config v2 ctl_aug_bias 2 more, with --config coarse ctl_aug_coarse_field 1 in place of ctl_aug_field): "
                    "device time between HIP events (median, warm), eager and as a graph replay, vs augment.apply_host (fp64 numpy / scipy) on "
                    "the same batch and parameters, and as a share of the training step of the bench.py runs of the same session",
-           "launches": "6 per batch with an elastic policy (8 with interp cubic), whatever n is", "interp": list(interps), "steps": steps,
+           "launches": "6 per batch with an elastic policy (8 with interp cubic), whatever n is", "interp": list(interps), "config": args.config, "steps": steps,
            "device": torch.cuda.get_device_name(0), "arch": torch.cuda.get_device_properties(0).gcnArchName, "rocm": torch.version.hip,
            "torch": torch.__version__, "host_cpus_usable": len(os.sched_getaffinity(0)), "rows": rows}
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -98,7 +98,12 @@ int    ctl_conv_stats_blocks(const ctl_conv* d);
 
 /* Pack weights into MFMA-fragment order.  Element (co,ci,kh,kw) of the *effective* conv is read from
  * src[co*s_co + ci*s_ci + kh'*s_kh + kw'*s_kw] with (kh',kw') = flip ? (ks-1-kh, ks-1-kw) : (kh,kw).  Covers OIHW
- * forward weights, their dgrad transposes and both ConvTranspose2d uses. */
+ * forward weights, their dgrad transposes and both ConvTranspose2d uses.
+ * Destination contract of every pack entry point (this one and the *_batched forms below): the destination need NOT be zeroed.  A pack
+ * writes every element of its record's layout that a conv kernel reads, the zero padding of the cin / cout fragments up to whole
+ * 16-channel tiles and of an odd last tap included, and nothing outside [dst_off, dst_off + ctl_conv_wpack_floats(_x3)) (mode 4: + ceil(cout / 16) * 3 * 256): a repack after
+ * an optimizer step does not depend on what the buffer held.  The fp32 and X3 layouts fill that range completely; the bf16 layout fills
+ * its first ceil(taps / 2) / taps part and neither writes nor reads the rest (tests/test_pack_guard_gpu.py). */
 int ctl_pack_weights(const float* src, float* dst, int32_t cout, int32_t cin, int32_t ks,
                      int64_t s_co, int64_t s_ci, int64_t s_kh, int64_t s_kw, int32_t flip, ctl_stream stream);
 

@@ -701,3 +701,146 @@ def crop_or_pad(image: torch.Tensor, crop_size, label: Optional[torch.Tensor] = 
               "ctl_crop_or_pad")
         return out[0] if squeeze else out
     return one(image), (None if label is None else one(label))
+
+
+# ------------------------------------------------------------------------------------------------ volume preparation
+def percentile_index(n: int, q: float):
+    """np.percentile's 'linear' virtual index for n elements, on the host in fp64: v = (n - 1) * (q / 100) -> (k, k_upper, g) with
+    k = floor(v), g = v - k and the upper rank clamped to n - 1."""
+    q = float(q)
+    if not 0.0 <= q <= 100.0:
+        raise ValueError(f"percentile: q = {q} outside [0, 100]")
+    v = (int(n) - 1) * (q / 100.0)
+    k = int(np.floor(v))
+    return k, min(k + 1, int(n) - 1), v - k
+
+
+def resample_geometry(n: int, h: int, w: int, spacing, new_spacing):
+    """The host arithmetic of `resample_by_spacing` (dataset_utils.py:39-63) for a [n,h,w] array: spacing and new_spacing are (x, y, z)
+    as SimpleITK orders them, so entry 0 belongs to the WIDTH axis.  -> (new_h, new_w, r_h, r_w, identity): new sizes by numpy's round
+    (half to even), r = new_spacing / spacing in fp64, identity = the scalings sum to within 1e-4 of their count (upstream returns the
+    input then).  The slice axis is never resampled: new_spacing[2] must be negative, the only form the datasets use."""
+    new_spacing, spacing = [float(v) for v in new_spacing], [float(v) for v in spacing]
+    if len(spacing) != 3 or len(new_spacing) != 3:
+        raise ValueError("resample_inplane: spacing and new_spacing are (x, y, z) triples")
+    if new_spacing[2] >= 0:
+        raise NotImplementedError("resample_inplane: the slice axis is not resampled here; pass new_spacing[2] < 0 (keep_z_spacing)")
+    if min(spacing[:2]) <= 0 or min(new_spacing[:2]) <= 0:
+        raise ValueError("resample_inplane: in-plane spacings must be positive")
+    scaling = np.array(new_spacing, dtype=np.float64) / (1.0 * np.array(spacing, dtype=np.float64))
+    new_size = np.round(np.array([w, h, n]) / scaling).astype("int").tolist()
+    scaling[2] = 1
+    identity = bool(abs(np.sum(scaling) - len(scaling)) < 1e-4)
+    return int(new_size[1]), int(new_size[0]), float(scaling[1]), float(scaling[0]), identity
+
+
+def _segmented(x: torch.Tensor, segments: int, who: str):
+    """A float32 device tensor viewed as `segments` contiguous segments -> (contiguous tensor, segments, elements per segment)."""
+    require_gpu(x)
+    if x.dtype != torch.float32:
+        raise TypeError(f"{who}: expected a float32 tensor, got {x.dtype}")
+    segments = int(segments)
+    if segments < 1 or x.numel() == 0 or x.numel() % segments:
+        raise ValueError(f"{who}: {x.numel()} elements do not split into {segments} equal, non-empty segments")
+    return x.contiguous(), segments, x.numel() // segments
+
+
+def _order_stats(x: torch.Tensor, segments: int, seg_elems: int, ranks) -> torch.Tensor:
+    ranks = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
+    table = torch.empty((segments, ranks.size), dtype=torch.float32, device=x.device)
+    nbytes = lib.ctl_order_stats_ws_bytes(segments, int(ranks.size))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
+    check(lib.ctl_order_stats(ptr(x), segments, seg_elems, ranks.ctypes.data, int(ranks.size), ptr(table), ptr(ws), nbytes, stream_ptr()),
+          "ctl_order_stats")
+    return table
+
+
+def order_statistics(x: torch.Tensor, ranks, segments: int = 1) -> torch.Tensor:
+    """Exact order statistics of a float32 device tensor viewed as `segments` contiguous segments (1: the whole tensor; slices: every
+    slice on its own): float32 device tensor [segments, len(ranks)] = the element of each zero-based rank (1 to 8 of them, duplicates and
+    any order allowed) in the segment's ascending order, -0.0 before +0.0.  Inputs must be finite: a NaN gives unspecified elements and
+    is not checked.  Radix select, integer atomics only: identical bits on every call.  5 launches, no readback."""
+    x, segments, seg_elems = _segmented(x, segments, "order_statistics")
+    return _order_stats(x, segments, seg_elems, ranks)
+
+
+def _percentile_table(x: torch.Tensor, segments: int, seg_elems: int, q_lo: float, q_hi: float):
+    k0, k0u, g_lo = percentile_index(seg_elems, q_lo)
+    k1, k1u, g_hi = percentile_index(seg_elems, q_hi)
+    return _order_stats(x, segments, seg_elems, [k0, k0u, k1, k1u]), g_lo, g_hi
+
+
+def percentile(x: torch.Tensor, q, segments: int = 1) -> torch.Tensor:
+    """np.percentile(x.astype(float64), q) ('linear') per segment, rounded once to float32: float32 device tensor [segments, len(q)].
+    Exact order statistics, then numpy's _lerp in fp64 on the device.  6 launches per pair of percentiles, no readback."""
+    x, segments, seg_elems = _segmented(x, segments, "percentile")
+    q = [float(v) for v in np.asarray(q, dtype=np.float64).reshape(-1)]
+    if not q:
+        raise ValueError("percentile: q is empty")
+    out = torch.empty((segments, len(q)), dtype=torch.float32, device=x.device)
+    for i in range(0, len(q), 2):
+        pair = q[i:i + 2] if i + 1 < len(q) else [q[i], q[i]]
+        table, g_lo, g_hi = _percentile_table(x, segments, seg_elems, pair[0], pair[1])
+        bounds = torch.empty((segments, 2), dtype=torch.float32, device=x.device)
+        check(lib.ctl_percentile_apply(ptr(x), ptr(table), segments, seg_elems, g_lo, g_hi, 0, 0.0, 1.0, None, ptr(bounds), stream_ptr()),
+              "ctl_percentile_apply")
+        out[:, i:i + 2] = bounds[:, :len(q) - i]
+    return out
+
+
+PERCENTILE_FORMS = {"minmax": 0, "medic": 1}
+
+
+def percentile_normalize(x: torch.Tensor, q=(2.0, 98.0), form: str = "minmax", segments: int = 1, new_min: float = 0.0,
+                         new_max: float = 1.0, out: Optional[torch.Tensor] = None, want_bounds: bool = False):
+    """Clip to the (q[0], q[1]) percentiles of each segment and scale, in float32 with one rounding per operation.  form "minmax":
+    `normalize_minmax_data` (dataset_utils.py:15-36; upstream: q = (2, 98) over the whole volume), (clip(x) - lo) / ((1e-10 + hi) - lo);
+    form "medic": `MyNormalizeMedicPercentile` (intensity_transform.py:216-269; upstream: per slice), clip(x) * a + b with
+    a = (new_max - new_min) / ((hi - lo) + 1e-8), b = new_max - a * hi.  lo, hi: np.percentile of the float64 values, rounded to float32.
+    `out`: a contiguous float32 device tensor of x's shape, not x itself.  want_bounds: also the device tensor [segments, 2] of lo, hi.
+    6 launches, no readback."""
+    if form not in PERCENTILE_FORMS:
+        raise ValueError(f"percentile_normalize: form {form!r}, one of {sorted(PERCENTILE_FORMS)}")
+    shape = x.shape
+    x, segments, seg_elems = _segmented(x, segments, "percentile_normalize")
+    if len(q) != 2:
+        raise ValueError("percentile_normalize: q is a (low, high) pair of percentiles")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == tuple(shape) and out.is_contiguous()):
+        raise ValueError("percentile_normalize: `out` must be a contiguous float32 device tensor of x's shape")
+    elif out.data_ptr() == x.data_ptr():
+        raise ValueError("percentile_normalize: `out` must not be the input")
+    table, g_lo, g_hi = _percentile_table(x, segments, seg_elems, q[0], q[1])
+    bounds = torch.empty((segments, 2), dtype=torch.float32, device=x.device) if want_bounds else None
+    check(lib.ctl_percentile_apply(ptr(x), ptr(table), segments, seg_elems, g_lo, g_hi, PERCENTILE_FORMS[form], float(new_min), float(new_max),
+                                   ptr(out), ptr(bounds), stream_ptr()), "ctl_percentile_apply")
+    return (out, bounds) if want_bounds else out
+
+
+def resample_inplane(image: torch.Tensor, spacing, new_spacing, label: Optional[torch.Tensor] = None):
+    """`resample_by_spacing` with keep_z_spacing (dataset_utils.py:39-63) for device arrays [n,h,w]: image float32 (linear), label uint8
+    or int64 (nearest) -> (image, label, spacing_out).  spacing / new_spacing: (x, y, z) as SimpleITK orders them (entry 0 = width);
+    new_spacing[2] must be negative (the slice axis stays), anything else raises NotImplementedError.  Output index j reads source
+    coordinate j * new_spacing / spacing; 0 where that reaches size - 0.5.  When the scalings sum to within 1e-4 of their count the inputs
+    are returned unchanged, as upstream does.  One launch per array, no readback."""
+    require_gpu(image)
+    if image.dim() != 3 or image.dtype != torch.float32:
+        raise ValueError(f"resample_inplane: expected a float32 [n,h,w] image, got {image.dtype} {tuple(image.shape)}")
+    if label is not None:
+        require_gpu(label)
+        if label.dtype not in (torch.uint8, torch.int64) or tuple(label.shape) != tuple(image.shape):
+            raise ValueError(f"resample_inplane: expected a uint8 or int64 label of the image's shape, got {label.dtype} {tuple(label.shape)}")
+    n, h, w = (int(v) for v in image.shape)
+    new_h, new_w, r_h, r_w, identity = resample_geometry(n, h, w, spacing, new_spacing)
+    if identity:
+        return image, label, tuple(float(v) for v in spacing)
+    image = image.contiguous()
+    image_out = torch.empty((n, new_h, new_w), dtype=torch.float32, device=image.device)
+    label_out = None
+    if label is not None:
+        label = label.contiguous()
+        label_out = torch.empty((n, new_h, new_w), dtype=label.dtype, device=label.device)
+    check(lib.ctl_resample_inplane(ptr(image), ptr(label), 0 if label is None else label.element_size(), n, h, w, new_h, new_w, r_h, r_w,
+                                   ptr(image_out), ptr(label_out), stream_ptr()), "ctl_resample_inplane")
+    return image_out, label_out, (float(new_spacing[0]), float(new_spacing[1]), float(spacing[2]))

@@ -5,7 +5,8 @@ path: the volume is uploaded once, predicted in chunks of <= `maximum_batch_size
 and the per-patient voxel counts are taken on the device, and one 2*n^2-word readback per patient replaces the reference's two
 full-volume `.cpu().numpy()` copies per chunk.  The dataset only has to offer what the reference's tester reads from it:
 `patient_number`, `get_patient_data_for_testing(i, crop_size=)` -> {'image': [n,1,H,W], 'label': [n,H,W]}, `get_id()`,
-`get_voxel_spacing()` and `formalized_label_dict`.  Writing nrrd files (SimpleITK) is outside the path and not offered."""
+`get_voxel_spacing()` and `formalized_label_dict`.  The tensors of a pack may live on the host (uploaded once here) or already on the
+device (prepare.prepare_patient: no upload at all).  Writing nrrd files (SimpleITK) is outside the path and not offered."""
 import os
 
 import numpy as np
@@ -135,7 +136,8 @@ class TestSegmentationNetwork(object):
         result = None
         if soft is not None:
             soft_np = torch.cat(soft, 0).float().cpu().numpy()
-            result = {"image": image.numpy().reshape(-1, image.shape[-2], image.shape[-1]), "label": label.numpy(),
+            # a pack prepared on the device (prepare.prepare_patient) is copied back here, and only here: keep_results asks for host arrays
+            result = {"image": image.cpu().numpy().reshape(-1, image.shape[-2], image.shape[-1]), "label": label.cpu().numpy(),
                       "pred": pred_d.cpu().numpy(), "soft_pred": soft_np}
             if total == 1:
                 result = {k: v[0] for k, v in result.items()}

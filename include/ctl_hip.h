@@ -549,6 +549,46 @@ int ctl_aug_bias(const float* image, const float* bias, const float* noise, cons
                  float* out, void* workspace, size_t workspace_bytes, ctl_stream stream);
 int ctl_aug_coarse_field(const float* coarse, int32_t n, int32_t hp, int32_t wp, float* field, ctl_stream stream);
 
+/* ------------------------------------------------------------------------------------------------ volume preparation
+ * The per-volume host work of `load_img_label_from_path` (medseg/common_utils/basic_operations.py:337-365), which upstream runs once per
+ * patient in testing (cardiac_ACDC_dataset.py:204-232) and once per slice sample in training (:117-161): resample the in-plane spacing
+ * (`resample_by_spacing`, medseg/dataset_loader/dataset_utils.py:39-63), then np.percentile 2 / 98, clip, scale (`normalize_minmax_data`,
+ * dataset_utils.py:15-36); and the per-slice form with arbitrary percentiles, `MyNormalizeMedicPercentile`
+ * (medseg/dataset_loader/_utils/intensity_transform.py:216-269).
+ * ctl_order_stats: x = `segments` contiguous segments of `seg_elems` floats (1 = the whole volume, slices = per slice).  ranks = HOST array
+ *   of n_rank (1..8) zero-based ranks in [0, seg_elems), duplicates and any order allowed, read during the call.  out (float
+ *   [segments][n_rank]) = the element of that rank in the segment's ascending order.  Exact: a radix select over the order-preserving key
+ *   bits ^ (sign ? 0xFFFFFFFF : 0x80000000), most significant digit first, four 8-bit passes with per-block LDS histograms (equal digits
+ *   of a wave are counted together first) and integer atomics only, so every call gives the same bits.  -0.0 sorts before +0.0.  Inputs
+ *   must be finite: with a NaN in a segment the elements returned for it are unspecified, and this is NOT checked on the device.
+ *   5 launches whatever the sizes and the content, no readback, no synchronisation: the call can be captured in a graph.  The workspace
+ *   is caller-owned, needs no initialisation, 4-byte alignment and ctl_order_stats_ws_bytes(segments, n_rank) bytes (0 for counts the call
+ *   would refuse); at most 65535 segments.
+ * ctl_percentile_apply: one launch over x with the table [segments][4] of ctl_order_stats for the ranks {k_lo, k_lo + 1, k_hi, k_hi + 1}
+ *   (the upper ranks clamped to seg_elems - 1).  For q in percent the HOST computes v = (seg_elems - 1) * (q / 100) in fp64, k = floor(v),
+ *   g = v - k, and passes g_lo, g_hi by value.  The device forms each percentile as numpy's _lerp does, in fp64 without fused multiply-
+ *   add: d = B - A, A + d * g when g < 0.5, else B - d * (1 - g), and rounds it once to float32 (lo, hi).  Then, in float32 with one
+ *   rounding per operation and no contraction:
+ *     form 0 "minmax" (dataset_utils.py:29-34):           x < lo -> lo, x > hi -> hi, out = (x - lo) / ((1e-10f + hi) - lo)
+ *     form 1 "medic"  (intensity_transform.py:260-266):   x <= lo -> lo, x >= hi -> hi, a = (new_max - new_min) / ((hi - lo) + 1e-8f),
+ *                                                          b = new_max - a * hi, out = x * a + b (multiply, then add)
+ *   bounds (float [segments][2], may be NULL) receives lo, hi.  out must not overlap x; out == NULL with bounds: only lo, hi are written.
+ * ctl_resample_inplane: [n,h,w] -> [n,new_h,new_w], the slice axis is never resampled (keep_z_spacing, the only form the datasets use).
+ *   image (float) and / or label (label_bytes 1 = uint8, 8 = int64), one launch each; new_h, new_w and the ratios r = new_spacing /
+ *   old_spacing of the height and width axes come from the host (fp64).  Output index j reads source coordinate c = j * r, one fp64
+ *   multiply.  Image: linear in fp64 over the two neighbours per axis, row pairs first (v0 * (1 - t) + v1 * t), indices clamped to
+ *   [0, size - 1], rounded once to float32.  Label: the element at floor(c + 0.5).  Both are 0 where c >= size - 0.5 on either axis
+ *   (ITK's inside-buffer rule and default pixel).  SimpleITK itself maps through physical points, which can differ from j * r in the
+ *   last bit of c; this statement is the contract.
+ * Every tensor obeys the 32-bit byte-offset limit (below 2 GiB). */
+size_t ctl_order_stats_ws_bytes(int32_t segments, int32_t n_rank);
+int ctl_order_stats(const float* x, int32_t segments, int64_t seg_elems, const int64_t* ranks, int32_t n_rank, float* out,
+                    void* workspace, size_t workspace_bytes, ctl_stream stream);
+int ctl_percentile_apply(const float* x, const float* table, int32_t segments, int64_t seg_elems, double g_lo, double g_hi,
+                         int32_t form, float new_min, float new_max, float* out, float* bounds, ctl_stream stream);
+int ctl_resample_inplane(const float* image, const void* label, int32_t label_bytes, int32_t n, int32_t h, int32_t w, int32_t new_h,
+                         int32_t new_w, double r_h, double r_w, float* image_out, void* label_out, ctl_stream stream);
+
 /* ------------------------------------------------------------------------------------------------ optimizer
  * torch.optim.Adam defaults (model.py:774-785), one flat buffer: p,g,m,v [count].  step = 1-based step index.
  * grad_scale folds the 1/world_size of the data-parallel all-reduce. */

@@ -59,7 +59,7 @@ class _Lib:
                      "ctl_wgrad_bias_partial_floats", "ctl_latent_score_ws_floats", "ctl_latent_mask_apply_ws_floats",
                      "ctl_rescale_intensity_ws_floats", "ctl_sizeof_op", "ctl_sizeof_conv", "ctl_latent_mask_fused_ws_floats", "ctl_conv_wpack_floats_x3",
                      "ctl_surface_stats_ws_bytes", "ctl_surface_map_ws_bytes", "ctl_cc_ws_bytes", "ctl_aug_ws_bytes", "ctl_aug_warp_ws_bytes",
-                     "ctl_aug_spline_ws_bytes", "ctl_aug_warp_cubic_ws_bytes", "ctl_aug_bias_ws_bytes", "ctl_order_stats_ws_bytes"):
+                     "ctl_aug_spline_ws_bytes", "ctl_aug_warp_cubic_ws_bytes", "ctl_aug_bias_ws_bytes", "ctl_order_stats_ws_bytes", "ctl_corrupt_spike_ws_bytes"):
             getattr(lib, name).restype = C.c_size_t
         p, i32, i64, f32, u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64
         sig = {
@@ -138,6 +138,9 @@ class _Lib:
             "ctl_order_stats_ws_bytes": [i32, i32], "ctl_order_stats": [p, i32, i64, p, i32, p, p, C.c_size_t, p],
             "ctl_percentile_apply": [p, p, i32, i64, C.c_double, C.c_double, i32, f32, f32, p, p, p],
             "ctl_resample_inplane": [p, p, i32, i32, i32, i32, i32, i32, C.c_double, C.c_double, p, p, p],
+            "ctl_corrupt_bias": [p, p, i32, i32, i32, p, p], "ctl_corrupt_spike_ws_bytes": [i32] * 4,
+            "ctl_corrupt_spike": [p, i32, i32, i32, p, p, i32, C.c_double, p, p, C.c_size_t, p],
+            "ctl_corrupt_rigid3d": [p, i32, i32, i32, p, i32, p, p], "ctl_axis_operator": [p, p, i32, i32, i32, i32, i32, p, p, p],
         }
         for name, args in sig.items():
             getattr(lib, name).argtypes = args
@@ -173,7 +176,8 @@ EXPORTED = ["ctl_version", "ctl_last_error", "ctl_conv_wpack_floats", "ctl_conv_
             "ctl_surface_map", "ctl_cc_ws_bytes", "ctl_cc_label", "ctl_cc_keep_largest", "ctl_aug_ws_bytes", "ctl_aug_warp_ws_bytes", "ctl_aug_field",
             "ctl_aug_warp", "ctl_aug_spline_ws_bytes", "ctl_aug_warp_cubic_ws_bytes", "ctl_aug_spline_coeffs", "ctl_aug_warp_cubic",
             "ctl_aug_bias_ws_bytes", "ctl_aug_bias", "ctl_aug_coarse_field", "ctl_order_stats_ws_bytes", "ctl_order_stats",
-            "ctl_percentile_apply", "ctl_resample_inplane"]
+            "ctl_percentile_apply", "ctl_resample_inplane", "ctl_corrupt_bias", "ctl_corrupt_spike_ws_bytes", "ctl_corrupt_spike",
+            "ctl_corrupt_rigid3d", "ctl_axis_operator"]
 
 
 def prof_start(kernel_filter: str = "", every: int = 1) -> None:

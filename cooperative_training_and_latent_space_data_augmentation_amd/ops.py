@@ -844,3 +844,93 @@ def resample_inplane(image: torch.Tensor, spacing, new_spacing, label: Optional[
     check(lib.ctl_resample_inplane(ptr(image), ptr(label), 0 if label is None else label.element_size(), n, h, w, new_h, new_w, r_h, r_w,
                                    ptr(image_out), ptr(label_out), stream_ptr()), "ctl_resample_inplane")
     return image_out, label_out, (float(new_spacing[0]), float(new_spacing[1]), float(spacing[2]))
+
+
+# ------------------------------------------------------------------------------------------------ MR artefact corruption
+def _volume(x: torch.Tensor, who: str):
+    """A float32 device volume [D,H,W] (a tester pack [D,1,H,W] is viewed as one) -> (contiguous [D,H,W] tensor, d, h, w)."""
+    require_gpu(x)
+    if x.dim() == 4 and x.shape[1] == 1:
+        x = x[:, 0]
+    if x.dim() != 3 or x.dtype != torch.float32 or x.numel() == 0:
+        raise ValueError(f"{who}: expected a non-empty float32 [D,H,W] volume (or a [D,1,H,W] pack), got {x.dtype} {tuple(x.shape)}")
+    x = x.contiguous()
+    return (x,) + tuple(int(v) for v in x.shape)
+
+
+def _volume_out(out: Optional[torch.Tensor], shape, like: torch.Tensor, who: str) -> torch.Tensor:
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=like.device)
+    if not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == tuple(shape) and out.is_contiguous()):
+        raise ValueError(f"{who}: `out` must be a contiguous float32 device tensor of shape {tuple(shape)}")
+    return out
+
+
+def corrupt_bias_field(x: torch.Tensor, coefficients, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x * exp(cubic polynomial of the normalised voxel coordinates) in float32 (ctl_corrupt_bias): x [D,H,W], coefficients = 20 host
+    numbers in the loop order i, j, k of u^i v^j w^k (rounded to float32).  One launch."""
+    x, d, h, w = _volume(x, "corrupt_bias_field")
+    coef = np.ascontiguousarray(coefficients, dtype=np.float32).reshape(-1)
+    if coef.size != 20:
+        raise ValueError(f"corrupt_bias_field: {coef.size} coefficients, 20 expected (i + j + k <= 3)")
+    out = _volume_out(out, (d, h, w), x, "corrupt_bias_field")
+    check(lib.ctl_corrupt_bias(ptr(x), coef.ctypes.data, d, h, w, ptr(out), stream_ptr()), "ctl_corrupt_bias")
+    return out
+
+
+def corrupt_spike_workspace(shape, n_pairs: int, device) -> torch.Tensor:
+    """The workspace of corrupt_spike for a volume shape and a number of wave-vector pairs (needs no initialisation)."""
+    nbytes = lib.ctl_corrupt_spike_ws_bytes(int(shape[0]), int(shape[1]), int(shape[2]), int(n_pairs))
+    return torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=device)
+
+
+def corrupt_spike(x: torch.Tensor, k, mult, intensity: float, out: Optional[torch.Tensor] = None,
+                  workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The image-space form of setting the spectrum entries k[s] and -k[s] of x [D,H,W] to intensity * sum(x) (ctl_corrupt_spike): k = host
+    integers [n,3] with 0 <= k < shape, each pair {k, -k} once, mult[s] = 1 where k[s] == -k[s] modulo the shape, else 2.  fp64 on the
+    device, rounded once; x should be non-negative (then sum(x) is the peak of the spectrum).  Two launches, no readback."""
+    x, d, h, w = _volume(x, "corrupt_spike")
+    k = np.ascontiguousarray(k, dtype=np.int32).reshape(-1, 3)
+    mult = np.ascontiguousarray(mult, dtype=np.int32).reshape(-1)
+    if mult.size != k.shape[0]:
+        raise ValueError("corrupt_spike: one multiplicity per wave vector")
+    out = _volume_out(out, (d, h, w), x, "corrupt_spike")
+    ws = corrupt_spike_workspace((d, h, w), k.shape[0], x.device) if workspace is None else workspace
+    check(lib.ctl_corrupt_spike(ptr(x), d, h, w, k.ctypes.data, mult.ctypes.data, int(k.shape[0]), float(intensity), ptr(out), ptr(ws),
+                                ws.numel() * ws.element_size(), stream_ptr()), "ctl_corrupt_spike")
+    return out
+
+
+def corrupt_rigid3d(x: torch.Tensor, matrices, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """T copies [T,D,H,W] of x [D,H,W], copy t read at M_t p + o_t (matrices: host [T,3,4] in voxel space, rounded to float32), linear over
+    the volume extended by zeros, float32 coordinates (ctl_corrupt_rigid3d).  An identity matrix returns x bit for bit.  One launch."""
+    x, d, h, w = _volume(x, "corrupt_rigid3d")
+    m = np.ascontiguousarray(matrices, dtype=np.float32).reshape(-1, 12)
+    out = _volume_out(out, (m.shape[0], d, h, w), x, "corrupt_rigid3d")
+    check(lib.ctl_corrupt_rigid3d(ptr(x), d, h, w, m.ctypes.data, int(m.shape[0]), ptr(out), stream_ptr()), "ctl_corrupt_rigid3d")
+    return out
+
+
+def axis_operator(x: torch.Tensor, matrix: torch.Tensor, axis: int, stack: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[r, j] = sum_k matrix[j, k] * volume_(k // L)[r, k % L] along `axis` of x [D,H,W] (L = its size): matrix = float32 DEVICE tensor
+    [L, n L], volume 0 = x, volumes 1 .. n - 1 = stack [n - 1, D, H, W] (None: one volume).  float32, terms added in ascending k
+    (ctl_axis_operator).  One launch."""
+    x, d, h, w = _volume(x, "axis_operator")
+    axis = int(axis)
+    if axis not in (0, 1, 2):
+        raise ValueError(f"axis_operator: axis {axis} (0, 1 or 2)")
+    n_vol = 1
+    if stack is not None:
+        require_gpu(stack)
+        if stack.dim() != 4 or tuple(stack.shape[1:]) != (d, h, w) or stack.dtype != torch.float32 or stack.shape[0] < 1:
+            raise ValueError(f"axis_operator: expected a float32 stack [T,{d},{h},{w}], got {stack.dtype} {tuple(stack.shape)}")
+        stack = stack.contiguous()
+        n_vol += int(stack.shape[0])
+    length = (d, h, w)[axis]
+    require_gpu(matrix)
+    if matrix.dtype != torch.float32 or tuple(matrix.shape) != (length, n_vol * length) or not matrix.is_contiguous():
+        raise ValueError(f"axis_operator: expected a contiguous float32 matrix [{length}, {n_vol * length}], got {matrix.dtype} {tuple(matrix.shape)}")
+    out = _volume_out(out, (d, h, w), x, "axis_operator")
+    check(lib.ctl_axis_operator(ptr(x), ptr(stack), n_vol, d, h, w, axis, ptr(matrix), ptr(out), stream_ptr()), "ctl_axis_operator")
+    return out

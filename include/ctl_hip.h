@@ -589,6 +589,44 @@ int ctl_percentile_apply(const float* x, const float* table, int32_t segments, i
 int ctl_resample_inplane(const float* image, const void* label, int32_t label_bytes, int32_t n, int32_t h, int32_t w, int32_t new_h,
                          int32_t new_w, double r_h, double r_w, float* image_out, void* label_out, ctl_stream stream);
 
+/* ------------------------------------------------------------------------------------------------ MR artefact corruption (ACDC-C)
+ * The four corruptions of medseg/dataset_loader/generate_artefacted_data.py:56-83 (TorchIO's RandomBiasField, RandomSpike, RandomGhosting,
+ * RandomMotion) for one volume x [d][h][w] of floats, axes 0, 1, 2; N = d h w.  The host draws the random parameters and passes them by
+ * value or as small HOST arrays read during the call; nothing is read back, every call is a fixed launch sequence that can be captured
+ * in a graph, there are no floating-point atomics and every sum has a fixed order: identical bits on every call.  `out` never overlaps an
+ * input.  Every tensor obeys the 32-bit byte-offset limit (below 2 GiB).
+ * ctl_corrupt_bias: out = x * expf(p), p = sum of coefficients[n] u^i v^j w^k over i + j + k <= 3 in the loop order i, j, k (20 HOST floats),
+ *   in float32.  The coordinate of index t on an axis of size n is (t - h + 0.5) / (h - 0.5) with h = n / 2 (integer), 0 where h == 0.
+ *   One launch.
+ * ctl_corrupt_spike: out = x + (1 / N) sum_s mult[s] ((A - Re X[k_s]) cos th_s + Im X[k_s] sin th_s), the image-space form of setting the
+ *   spectrum entries k_s and -k_s to A = intensity * sum(x): X[k] = sum_r x[r] exp(-i th), th = 2 pi sum_a k_a r_a / size_a.  k: HOST int32
+ *   [n_spikes][3] with 0 <= k_a < size_a, mult: HOST int32 [n_spikes] = 1 where k == -k (mod size) on every axis, else 2 (checked); the
+ *   caller lists each pair {k, -k} once, 1..CTL_CORRUPT_MAX_SPIKES pairs.  (k_a r_a) mod size_a is reduced in integers, everything else
+ *   is fp64, the result is rounded once.  Two launches: a reduction into the workspace (per-block partials summed in block order), then
+ *   one element-wise pass.  The workspace is caller-owned, needs no initialisation, 8-byte alignment and
+ *   ctl_corrupt_spike_ws_bytes(d, h, w, n_spikes) = min(ceil(N / 2048), CTL_CORRUPT_RED_BLOCKS) * (1 + 2 n_spikes) * 8 bytes (0 for
+ *   arguments the call would refuse).
+ * ctl_corrupt_rigid3d: out [copies][d][h][w]; copy t at voxel p = (i0, i1, i2) is the volume, extended by zeros, interpolated linearly at
+ *   s_a = fma(m[4a+2], i2, fma(m[4a+1], i1, fma(m[4a], i0, m[4a+3]))) in float32, m = matrices[t] (HOST float [copies][12], row-major 3 x 4,
+ *   voxel space; the host composes rotation about the physical centre, spacing and translation in fp64).  Along each axis
+ *   v0 + f (v1 - v0), last axis first: an identity matrix returns x bit for bit.  1..CTL_CORRUPT_MAX_COPIES copies, one launch.
+ * ctl_axis_operator: out[r][j] = sum over v < n_volumes, k < L of matrix[j][v L + k] * volume_v[r][k] along `axis` (0, 1 or 2; L = its
+ *   size; r = the other two indices), terms added in ascending (v, k) with one float32 fused multiply-add each.  Volume 0 is x0, volumes
+ *   1.. are stacked in xs ([n_volumes - 1][d][h][w], NULL for one volume); matrix: DEVICE float [L][n_volumes L], row-major.  A spectrum
+ *   mask along one axis, real part of the inverse transform, is such a matrix (ghosting: one volume; motion: the original and its
+ *   rigid copies).  LDS-tiled, strided for axes 0 and 1: nothing is transposed in memory.  One launch. */
+#define CTL_CORRUPT_MAX_SPIKES 8
+#define CTL_CORRUPT_MAX_COPIES 8
+#define CTL_CORRUPT_RED_BLOCKS 256
+int ctl_corrupt_bias(const float* x, const float* coefficients, int32_t d, int32_t h, int32_t w, float* out, ctl_stream stream);
+size_t ctl_corrupt_spike_ws_bytes(int32_t d, int32_t h, int32_t w, int32_t n_spikes);
+int ctl_corrupt_spike(const float* x, int32_t d, int32_t h, int32_t w, const int32_t* k, const int32_t* mult, int32_t n_spikes,
+                      double intensity, float* out, void* workspace, size_t workspace_bytes, ctl_stream stream);
+int ctl_corrupt_rigid3d(const float* x, int32_t d, int32_t h, int32_t w, const float* matrices, int32_t copies, float* out,
+                        ctl_stream stream);
+int ctl_axis_operator(const float* x0, const float* xs, int32_t n_volumes, int32_t d, int32_t h, int32_t w, int32_t axis,
+                      const float* matrix, float* out, ctl_stream stream);
+
 /* ------------------------------------------------------------------------------------------------ optimizer
  * torch.optim.Adam defaults (model.py:774-785), one flat buffer: p,g,m,v [count].  step = 1-based step index.
  * grad_scale folds the 1/world_size of the data-parallel all-reduce. */

@@ -141,6 +141,8 @@ class _Lib:
             "ctl_corrupt_bias": [p, p, i32, i32, i32, p, p], "ctl_corrupt_spike_ws_bytes": [i32] * 4,
             "ctl_corrupt_spike": [p, i32, i32, i32, p, p, i32, C.c_double, p, p, C.c_size_t, p],
             "ctl_corrupt_rigid3d": [p, i32, i32, i32, p, i32, p, p], "ctl_axis_operator": [p, p, i32, i32, i32, i32, i32, p, p, p],
+            "ctl_slice_foreground": [p, p, i32, i64, p, p],
+            "ctl_batch_gather": [p, p, p, i32, i64, p, i32, p, i32, i32, p, p, i32, i32, p, p, p],
         }
         for name, args in sig.items():
             getattr(lib, name).argtypes = args
@@ -177,7 +179,7 @@ EXPORTED = ["ctl_version", "ctl_last_error", "ctl_conv_wpack_floats", "ctl_conv_
             "ctl_aug_warp", "ctl_aug_spline_ws_bytes", "ctl_aug_warp_cubic_ws_bytes", "ctl_aug_spline_coeffs", "ctl_aug_warp_cubic",
             "ctl_aug_bias_ws_bytes", "ctl_aug_bias", "ctl_aug_coarse_field", "ctl_order_stats_ws_bytes", "ctl_order_stats",
             "ctl_percentile_apply", "ctl_resample_inplane", "ctl_corrupt_bias", "ctl_corrupt_spike_ws_bytes", "ctl_corrupt_spike",
-            "ctl_corrupt_rigid3d", "ctl_axis_operator"]
+            "ctl_corrupt_rigid3d", "ctl_axis_operator", "ctl_slice_foreground", "ctl_batch_gather"]
 
 
 def prof_start(kernel_filter: str = "", every: int = 1) -> None:

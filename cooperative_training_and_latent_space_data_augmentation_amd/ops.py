@@ -934,3 +934,83 @@ def axis_operator(x: torch.Tensor, matrix: torch.Tensor, axis: int, stack: Optio
     out = _volume_out(out, (d, h, w), x, "axis_operator")
     check(lib.ctl_axis_operator(ptr(x), ptr(stack), n_vol, d, h, w, axis, ptr(matrix), ptr(out), stream_ptr()), "ctl_axis_operator")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ device-resident training set
+def _arenas(image_arena: torch.Tensor, label_arena: torch.Tensor, table: torch.Tensor, who: str):
+    """The packed slices of a training set: float32 and uint8 arenas of one layout, int64 table [S,3] of (element offset, h, w)."""
+    if image_arena is not None and (image_arena.dtype != torch.float32 or image_arena.dim() != 1 or not image_arena.is_contiguous()):
+        raise TypeError(f"{who}: the image arena is a flat contiguous float32 tensor, got {image_arena.dtype} {tuple(image_arena.shape)}")
+    if label_arena.dtype != torch.uint8 or label_arena.dim() != 1 or not label_arena.is_contiguous():
+        raise TypeError(f"{who}: the label arena is a flat contiguous uint8 tensor, got {label_arena.dtype} {tuple(label_arena.shape)}")
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 3 or table.shape[0] < 1 or not table.is_contiguous():
+        raise TypeError(f"{who}: the slice table is a contiguous int64 tensor [S,3] of (offset, h, w), got {table.dtype} {tuple(table.shape)}")
+    if label_arena.numel() < 1 or (image_arena is not None and image_arena.numel() != label_arena.numel()):
+        raise ValueError(f"{who}: the arenas hold the same, positive number of elements")
+    return int(table.shape[0]), int(label_arena.numel())
+
+
+def _dense_out(out: Optional[torch.Tensor], shape, dtype, device, who: str, name: str) -> torch.Tensor:
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if out.dtype != dtype or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise ValueError(f"{who}: `{name}` must be a contiguous {dtype} tensor of shape {tuple(shape)}, got {out.dtype} {tuple(out.shape)}")
+    return out
+
+
+def slice_foreground(label_arena: torch.Tensor, table: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int32 device tensor [S]: the number of non-zero raw label bytes of every slice of the packed uint8 arena (ctl_slice_foreground;
+    table: int64 [S,3] of element offset, h, w).  One launch, integer adds only, no readback."""
+    n_slices, elems = _arenas(None, label_arena, table, "slice_foreground")
+    out = _dense_out(out, (n_slices,), torch.int32, label_arena.device, "slice_foreground", "out")
+    require_gpu(label_arena, table, out)
+    check(lib.ctl_slice_foreground(ptr(label_arena), ptr(table), n_slices, elems, ptr(out), stream_ptr()), "ctl_slice_foreground")
+    return out
+
+
+def batch_gather(image_arena: torch.Tensor, label_arena: torch.Tensor, table: torch.Tensor, index, lut: torch.Tensor, canvas, crop=None,
+                 out=None, orig_out=None):
+    """The padded batch of the slices `index` names, and with `crop` upstream's original pair, in one launch (ctl_batch_gather).
+    index: int32 DEVICE tensor [n], read on the device (its range is the caller's contract; nothing is synchronised), or host integers
+    (numpy / list / CPU tensor), which are checked against [0, S) and uploaded.  lut: uint8 device tensor [256] (formulate_labels).
+    canvas = (H, W) -> image [n,1,H,W] float32, label [n,H,W] int64; crop = (Hc, Wc) -> also orig_image [n,1,Hc,Wc], orig_label [n,Hc,Wc].
+    out = (image, label), orig_out = (orig_image, orig_label): contiguous tensors to write into (views into a larger batch are fine).
+    -> (image, label) or (image, label, orig_image, orig_label)."""
+    who = "batch_gather"
+    n_slices, elems = _arenas(image_arena, label_arena, table, who)
+    if lut.dtype != torch.uint8 or tuple(lut.shape) != (256,) or not lut.is_contiguous():
+        raise TypeError(f"{who}: the lookup table is a contiguous uint8 tensor [256], got {lut.dtype} {tuple(lut.shape)}")
+    H, W = int(canvas[0]), int(canvas[1])
+    if crop is None and orig_out is not None:
+        raise ValueError(f"{who}: orig_out without a crop size")
+    host_index = not (torch.is_tensor(index) and index.is_cuda)
+    if host_index:
+        index_h = np.ascontiguousarray(index.numpy() if torch.is_tensor(index) else index)
+        if index_h.ndim != 1 or index_h.dtype.kind not in "iu":
+            raise TypeError(f"{who}: a host index is a 1-D integer array, got {index_h.dtype} {index_h.shape}")
+        n = int(index_h.size)
+    else:
+        if index.dtype != torch.int32 or index.dim() != 1 or not index.is_contiguous():
+            raise TypeError(f"{who}: a device index is a contiguous int32 tensor [n], got {index.dtype} {tuple(index.shape)}")
+        n = int(index.shape[0])
+    if n < 1:
+        raise ValueError(f"{who}: an empty index")
+    if out is not None and int(out[0].shape[0]) != n:
+        raise ValueError(f"{who}: an index of {n} entries for outputs of {int(out[0].shape[0])} samples")
+    if host_index and (int(index_h.min()) < 0 or int(index_h.max()) >= n_slices):
+        raise IndexError(f"{who}: host index outside [0, {n_slices}): min {int(index_h.min())}, max {int(index_h.max())}")
+    dev = image_arena.device
+    image = _dense_out(None if out is None else out[0], (n, 1, H, W), torch.float32, dev, who, "out[0]")
+    label = _dense_out(None if out is None else out[1], (n, H, W), torch.int64, dev, who, "out[1]")
+    oi = ol = None
+    Hc = Wc = 0
+    if crop is not None:
+        Hc, Wc = int(crop[0]), int(crop[1])
+        oi = _dense_out(None if orig_out is None else orig_out[0], (n, 1, Hc, Wc), torch.float32, dev, who, "orig_out[0]")
+        ol = _dense_out(None if orig_out is None else orig_out[1], (n, Hc, Wc), torch.int64, dev, who, "orig_out[1]")
+    require_gpu(image_arena, label_arena, table, lut, image, label, oi, ol)
+    if host_index:
+        index = torch.from_numpy(index_h.astype(np.int32)).pin_memory().to(dev, non_blocking=True)
+    check(lib.ctl_batch_gather(ptr(image_arena), ptr(label_arena), ptr(table), n_slices, elems, ptr(index), n, ptr(lut), H, W, ptr(image),
+                               ptr(label), Hc, Wc, ptr(oi), ptr(ol), stream_ptr()), "ctl_batch_gather")
+    return (image, label) if crop is None else (image, label, oi, ol)

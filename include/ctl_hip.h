@@ -627,6 +627,34 @@ int ctl_corrupt_rigid3d(const float* x, int32_t d, int32_t h, int32_t w, const f
 int ctl_axis_operator(const float* x0, const float* xs, int32_t n_volumes, int32_t d, int32_t h, int32_t w, int32_t axis,
                       const float* matrix, float* out, ctl_stream stream);
 
+/* ------------------------------------------------------------------------------------------------ device-resident training set
+ * What upstream's per-slice Dataset does on the host before the augmentation chain, for a batch picked by an index list:
+ * formulate_labels (medseg/dataset_loader/base_segmentation_dataset.py:190-202), PadNumpy (transform.py:46-97 builds the chain; the pad
+ * itself is torchsample's, defined here as: an axis shorter than the target gets ceil(d / 2) zeros in front and floor(d / 2) behind, a
+ * longer one is left alone) and the origin_image / origin_label pair of keep_orig_image_label_pair (base_segmentation_dataset.py:149-186),
+ * plus the "slice without objects" test of cardiac_ACDC_dataset.py:141-149.
+ * The training volumes are packed slice after slice into two arenas with the same element layout: `image` float32 and `label` uint8,
+ * arena_elems elements each.  table: DEVICE int64 [n_slices][3] = (element offset, h, w) of every slice; 64-bit offsets, an arena may
+ * pass 2^31 elements.
+ * ctl_slice_foreground: counts[s] = number of non-zero RAW label bytes of slice s (int32).  One launch over all slices, integer adds in
+ *   a fixed order: identical on every call.
+ * ctl_batch_gather: for b < n, slice s = index[b] (DEVICE int32 [n], read on the device: a captured launch replays with refreshed
+ *   indices) is placed on the canvas: image_out [n][1][H][W] float32 (a copy, bit for bit) and label_out [n][H][W] int64 =
+ *   lut[raw label] (lut: DEVICE uint8 [256], formulate_labels; values without an entry hold 0).  Placement per axis is upstream's
+ *   crop_or_pad rule: a slice axis of size a on a target of size A starts at target index ceil((A - a) / 2) when a < A, and is read from
+ *   source index (a - A) / 2 (floor) when a > A; everything else is 0 (the padding is 0 whatever lut[0] is: upstream pads after the
+ *   remap).  With orig_image / orig_label (both or neither) the same launch also places the RAW slice and its remapped label on
+ *   [n][1][Hc][Wc] / [n][Hc][Wc] by the same rule: upstream's origin pair for crop size (Hc, Wc).  Every element of every output is
+ *   written.  Outputs are dense, 4-byte (float) / 8-byte (int64) aligned and may sit at any such address, e.g. the second half of a
+ *   [2 n] batch tensor; rows are stored as 16-byte vectors wherever the address allows.  The range of a device-side index is the
+ *   caller's contract; as a guard, an index outside [0, n_slices) or a table row that leaves the arena yields an all-zero sample, never
+ *   a read outside the arenas.  1 <= n <= 65535, 1 <= H, W, Hc, Wc <= 32768.  One launch, no atomics, no readback. */
+int ctl_slice_foreground(const uint8_t* label, const int64_t* table, int32_t n_slices, int64_t arena_elems, int32_t* counts,
+                         ctl_stream stream);
+int ctl_batch_gather(const float* image, const uint8_t* label, const int64_t* table, int32_t n_slices, int64_t arena_elems,
+                     const int32_t* index, int32_t n, const uint8_t* lut, int32_t H, int32_t W, float* image_out, int64_t* label_out,
+                     int32_t Hc, int32_t Wc, float* orig_image, int64_t* orig_label, ctl_stream stream);
+
 /* ------------------------------------------------------------------------------------------------ optimizer
  * torch.optim.Adam defaults (model.py:774-785), one flat buffer: p,g,m,v [count].  step = 1-based step index.
  * grad_scale folds the 1/world_size of the data-parallel all-reduce. */

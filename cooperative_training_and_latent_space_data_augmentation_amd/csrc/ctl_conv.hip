@@ -1052,7 +1052,7 @@ extern "C" int ctl_conv_forward_ex(const ctl_conv* d, const float* x, const floa
         const int k = d->ks, s = d->stride, m = d->in_mode;
         CTL_REQUIRE((d->epi_flags & CTL_EPI_STATS) && res && res2 && !(d->epi_flags & (CTL_EPI_RES | CTL_EPI_BNBWD | CTL_EPI_BIAS)) &&
                     d->epi_act == CTL_ACT_NONE && d->cout % 16 == 0,
-                    "conv_forward: CTL_EPI_TAILBWD needs CTL_EPI_STATS + res (= the block output) + res2 (= the BatchNorm input), cout %% 16 == 0, nothing else but CTL_EPI_ACCUM");
+                    "conv_forward: CTL_EPI_TAILBWD needs CTL_EPI_STATS + res (= the block output) + res2 (= the BatchNorm input), cout %% 16 == 0, nothing else but CTL_EPI_ACCUM (got cout %d)", d->cout);
         CTL_REQUIRE((k == 1 && m == CTL_IN_PLAIN) || k == 2 || (k == 3 && s == 1 && m == CTL_IN_ZINS2),
                     "conv_forward: CTL_EPI_TAILBWD is built for the launches that write a block's output gradient (1x1, 2x2, zero-insert 3x3)");
         CTL_REQUIRE(d->epi_slope >= 0.f && d->epi_slope <= 1.f, "conv_forward: LeakyReLU slope must be in [0, 1]");
@@ -1061,7 +1061,7 @@ extern "C" int ctl_conv_forward_ex(const ctl_conv* d, const float* x, const floa
     CTL_REQUIRE(d->pro_affine != 1 || (pro_scale && pro_shift), "conv_forward: prologue without scale/shift");
     CTL_REQUIRE(d->pro_affine != 2 || (x2 && pro_scale && d->cin % 16 == 0 && d->in_mode == CTL_IN_PLAIN &&
                                        ((d->ks == 3 && d->stride == 1) || (d->ks == 4 && d->stride == 2)) && !(d->epi_flags & CTL_EPI_TAILBWD)),
-                "conv_forward: the BatchNorm-backward prologue (pro_affine 2) needs x2 + coefficients, cin %% 16 == 0 and a plain 3x3 stride-1 or 4x4 stride-2 conv");
+                "conv_forward: the BatchNorm-backward prologue (pro_affine 2) needs x2 + coefficients, cin %% 16 == 0 and a plain 3x3 stride-1 or 4x4 stride-2 conv (got cin %d)", d->cin);
     CTL_REQUIRE(!d->pro_affine || (d->groups > 1 ? d->groups : 1) * d->cin <= CTL_PRO_MAX, "conv_forward: groups * cin = %d prologue coefficients exceed %d", (d->groups > 1 ? d->groups : 1) * d->cin, CTL_PRO_MAX);
     CTL_REQUIRE(d->pro_affine != 1 || (d->pro_slope >= 0.f && d->pro_slope <= 1.f), "conv_forward: prologue slope must be in [0, 1]");
     CTL_REQUIRE(d->epi_act != CTL_ACT_LEAKY || (d->epi_slope >= 0.f && d->epi_slope <= 1.f), "conv_forward: LeakyReLU slope must be in [0, 1]");
@@ -1234,7 +1234,7 @@ extern "C" int ctl_conv_wgrad_ex(const ctl_conv* d, const float* x, const float*
     CTL_REQUIRE(d->pro_affine == 0 || d->pro_affine == 1, "conv_wgrad: pro_affine must be 0 or 1");
     CTL_REQUIRE(!dy2 || (dy_coef && d->ks == 3 && d->stride == 1 && d->cout % 16 == 0 &&
                          (d->groups > 1 ? d->groups : 1) * d->cout <= CTL_PRO_MAX),
-                "conv_wgrad: the two-tensor output gradient needs coefficients, a 3x3 stride-1 conv, cout %% 16 == 0 and groups * cout <= %d", CTL_PRO_MAX);
+                "conv_wgrad: the two-tensor output gradient needs coefficients, a 3x3 stride-1 conv, cout %% 16 == 0 and groups * cout <= %d (got cout %d)", CTL_PRO_MAX, d->cout);
     CTL_REQUIRE(!d->pro_affine || (pro_scale && pro_shift), "conv_wgrad: prologue without scale/shift");
     CTL_REQUIRE(!d->pro_affine || (d->groups > 1 ? d->groups : 1) * d->cin <= CTL_PRO_MAX, "conv_wgrad: groups * cin = %d prologue coefficients exceed %d", (d->groups > 1 ? d->groups : 1) * d->cin, CTL_PRO_MAX);
     CTL_REQUIRE(!d->pro_affine || (d->pro_slope >= 0.f && d->pro_slope <= 1.f), "conv_wgrad: prologue slope must be in [0, 1]");

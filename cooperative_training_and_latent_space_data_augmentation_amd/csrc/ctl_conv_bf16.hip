@@ -833,17 +833,17 @@ int ctl_conv_forward_bf16(const ctl_conv* d, const void* x, const void* x2, cons
                           float* stats_partial, void* pool, void* xout, ctl_stream stream) {
     if (d->epi_flags & CTL_EPI_TAILBWD) {
         CTL_REQUIRE((d->dt & CTL_DT_Y16) && (d->dt & CTL_DT_RES16) && d->cout % 16 == 0 && ((d->dt & CTL_DT_X16) ? d->cin % 16 == 0 : d->ks == 1),
-                    "conv_forward(bf16): CTL_EPI_TAILBWD needs bf16-stored y / res / res2 with whole 16-channel tiles (and a bf16-stored x, except for 1x1 convs)");
+                    "conv_forward(bf16): CTL_EPI_TAILBWD needs bf16-stored y / res / res2 with whole 16-channel tiles (and a bf16-stored x, except for 1x1 convs) (got cin %d, cout %d)", d->cin, d->cout);
     }
     if (d->pro_affine == 2) {
         const int e = d->epi_flags & (CTL_EPI_RES | CTL_EPI_ACCUM | CTL_EPI_BIAS);
         CTL_REQUIRE(x2 && pro_scale && (d->dt & CTL_DT_X16) && (d->dt & CTL_DT_Y16) && d->cin % 16 == 0 && d->cout % 16 == 0 && !e &&
                     d->epi_act == CTL_ACT_NONE && d->in_mode == CTL_IN_PLAIN && ((d->ks == 3 && d->stride == 1) || (d->ks == 4 && d->stride == 2)),
                     "conv_forward(bf16): the BatchNorm-backward prologue (pro_affine 2) needs x2 + coefficients, bf16-stored x / x2 / y with whole "
-                    "16-channel tiles, a plain 3x3 stride-1 or 4x4 stride-2 conv and no epilogue operand other than CTL_EPI_STATS / CTL_EPI_BNBWD");
+                    "16-channel tiles, a plain 3x3 stride-1 or 4x4 stride-2 conv and no epilogue operand other than CTL_EPI_STATS / CTL_EPI_BNBWD (got cin %d, cout %d)", d->cin, d->cout);
     }
     CTL_REQUIRE(!(d->epi_flags & CTL_EPI_BNBWD) || ((d->dt & CTL_DT_X16) && (d->dt & CTL_DT_Y16) && (d->dt & CTL_DT_RES16) && d->cin % 16 == 0 && d->cout % 16 == 0),
-                "conv_forward(bf16): CTL_EPI_BNBWD needs bf16-stored x, y and u with whole 16-channel tiles");
+                "conv_forward(bf16): CTL_EPI_BNBWD needs bf16-stored x, y and u with whole 16-channel tiles (got cin %d, cout %d)", d->cin, d->cout);
     CTL_REQUIRE(!(d->dt & CTL_DT_X16) || d->cin % 16 == 0, "conv_forward(bf16): bf16-stored inputs need cin %% 16 == 0 (got %d)", d->cin);
     CTL_REQUIRE(!(d->dt & (CTL_DT_Y16 | CTL_DT_RES16)) || d->cout % 4 == 0, "conv_forward(bf16): bf16-stored outputs need cout %% 4 == 0");
     conv16_call a = {};

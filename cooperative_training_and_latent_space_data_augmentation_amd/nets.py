@@ -73,6 +73,7 @@ FUSE_TAIL = True         # fp32: the residual tail's BatchNorm-backward reductio
                          # never materialised, the stand-alone reduction launch (read dOut, out, v; write dS) disappears
 CONV_WORDS = _ffi.CONV_DTYPE.itemsize // 4      # ctl_conv as int32 words at the head of ctl_op.i
 ALIGN_F = 64            # floats (256 B)
+PRO_MAX = 256           # CTL_PRO_MAX (csrc/ctl_conv_common.h): the [groups][cin] BatchNorm coefficients of a staged prologue sit in one LDS table
 
 T = namedtuple("T", "ref n h w c b16", defaults=(False,))     # tensor descriptor: ref = (slot, byte offset), NHWC dims, bf16 storage?
 
@@ -182,7 +183,7 @@ class ArenaPool:
 
 class Plan:
     __slots__ = ("ops", "n_ops", "act_bytes", "scr_bytes", "bscr_bytes", "rec", "out_shapes", "table_np", "table_dev", "groups", "bn_log",
-                 "replay", "main_ops", "tail_ops")
+                 "replay", "main_ops", "tail_ops", "pro_entries")
 
 
 # plan ops that only PRODUCE parameter gradients (nothing in a backward plan reads them): a split plan runs them as its tail, on another
@@ -271,6 +272,7 @@ class PlanBuilder:
         self.pending_wgrads: List[dict] = []  # deferred weight gradients (GROUP_WGRAD), emitted by flush_wgrad_groups
         self.table: Optional[np.ndarray] = None
         self.bn_log: List[tuple] = []         # (BNInfo, coefficient refs) of every training-mode BatchNorm of a forward plan, in order
+        self.pro_entries = 0                  # the largest groups * cin of a launch with the activation prologue (<= PRO_MAX or the launch is refused)
 
     # -- low level
     def op(self, kind: int) -> np.ndarray:
@@ -311,6 +313,8 @@ class PlanBuilder:
         if nsub == 4:
             d["out_h"], d["out_w"], d["out_sy"], d["out_sx"], d["nsub"], d["out_sub"] = 2 * hout, 2 * wout, 2, 2, 4, 1
         d["groups"] = self.groups
+        if pro:
+            self.pro_entries = max(self.pro_entries, self.groups * x.c)
         return d
 
     def conv(self, x: T, wp_ref, cout, ks, *, stride=1, in_mode=0, pro=None, bias_ref=None, stats=False, act=0,
@@ -653,6 +657,7 @@ class PlanBuilder:
         p.rec, p.out_shapes = rec, out_shapes
         p.groups = self.groups
         p.bn_log = self.bn_log
+        p.pro_entries = self.pro_entries
         return p
 
 
@@ -1086,6 +1091,8 @@ class CtlNet(nn.Module):
             return None
         if pb.b16 and not (rec["out"].b16 and rec["v"].b16):
             return None
+        if rec["out"].c % 16 != 0:      # CTL_EPI_TAILBWD reduces whole 16-channel cout tiles: a narrower block (reduce_factor 8 / 16) keeps the stand-alone passes
+            return None
         return (rec["out"], rec["v"], SLOPE, rec["pre"] == "nn")
 
     def _emit_block_bwd(self, pb: PlanBuilder, rec: dict, d_out: T, d_in: Optional[T], need_w: bool, affine: bool, *, pre_tail=None,
@@ -1269,6 +1276,13 @@ class CtlNet(nn.Module):
         n, h, w, c = shape
         return torch.empty((n, c, h, w), dtype=torch.float32, device=self.device, memory_format=torch.channels_last)
 
+    def _check_prologue_tables(self, plan: Plan):
+        """The launch-time refusal of ctl_conv_forward_ex / ctl_conv_wgrad_ex (groups * cin prologue coefficients > CTL_PRO_MAX), raised
+        from the compiled plan before anything of the pass is allocated or launched: a pass either runs whole or not at all."""
+        if plan.pro_entries > PRO_MAX:
+            raise _ffi.CtlError(f"{type(self).__name__}: a pass of {plan.groups} BatchNorm group(s) needs groups * cin = {plan.pro_entries} prologue coefficients in one "
+                                f"launch, the conv kernels stage at most {PRO_MAX} (CTL_PRO_MAX): run the {plan.groups} batches as passes of their own")
+
     def run_forward(self, x: torch.Tensor, mode: str, groups: int = 1, stack: Optional[PassStack] = None):
         """Returns (outputs tuple, act workspace tensor, plan).  x: logical NCHW, NHWC memory.  groups > 1: x stacks that many
         independent batches along n; BatchNorm treats each on its own (statistics, running-stat updates in order).
@@ -1287,6 +1301,7 @@ class CtlNet(nn.Module):
                 plan = self._plans[key] = self._compile_forward(n, h, w, mode)
             finally:
                 self._cur_groups, self._cur_pp = 1, (0, 1)
+        self._check_prologue_tables(plan)
         self.ensure_packed()
         if stack is None:
             act = self._arenas.acquire(plan.act_bytes, self.device)        # lease: lives as long as the autograd context of this pass
@@ -1458,6 +1473,7 @@ class CtlNet(nn.Module):
                 plan = self._plans[key] = self._compile_backward(fwd_plan, mode, mask, need_dx, need_w, affine)
             finally:
                 self._cur_groups = 1
+        self._check_prologue_tables(plan)
         lease = self._arenas.acquire(plan.bscr_bytes, self.device)
         bscr = lease.t
         self._dbg_last = (plan, bscr)          # lets tests inspect intermediate gradients (valid until the next pass on this stream:
@@ -1747,15 +1763,62 @@ class MyDecoder(CtlNet):
         return net_apply(self, x)[0]
 
 
+# ------------------------------------------------------------------------------------------------ the supported configurations
+LABEL_MAXC = 16          # the label-space kernels (softmax, cross-entropy, one-hot, argmax) keep a pixel's class row in registers: MAXC, csrc/ctl_elem.hip
+
+
+def conv_channels_ok(c: int) -> bool:
+    """A channel count the conv library serves on BOTH sides of a layer (ctl_conv_pick_cfg: cin 1, 4, 8, 12 or a multiple of 16; cout 1 or
+    a multiple of 4).  Every tensor of a network is the input of one conv and the output of another, forward or in the data gradient."""
+    return c in (1, 4, 8, 12) or (c >= 16 and c % 16 == 0)
+
+
+def _internal_widths(reduce_factor: int):
+    """the channel counts `reduce_factor` decides: every conv / BatchNorm width of the five networks but the image and label channels"""
+    specs = _init.network_specs(0, 0, reduce_factor)          # (0 marks the two external channel counts)
+    return sorted({c for spec in specs.values() for _, kind, a in spec for c in (a[:2] if kind != "bn" else a[:1])} - {0})
+
+
+def _reduce_factor_ok(rf: int, dtype: str) -> bool:
+    w = _internal_widths(rf)
+    return 64 // rf >= 1 and all(conv_channels_ok(c) and (dtype != "bf16" or c % 16 == 0) for c in w) and max(w) <= PRO_MAX
+
+
+def check_config(image_ch: int = 1, num_classes: int = 4, reduce_factor: int = 4, dtype: str = "fp32") -> None:
+    """Raise ValueError for a configuration the kernels cannot serve -- at construction, before any storage exists, instead of a CtlError
+    out of the first plan compilation.  Derived from the library's own rules, not from a list of configurations:
+      image_ch, num_classes   conv_channels_ok (they are a cin of a first layer and a cout of a last one); num_classes <= LABEL_MAXC
+      reduce_factor           every internal width (64 ... 512) // reduce_factor passes conv_channels_ok; dtype "bf16" stores the internal
+                              tensors as bf16, which the bf16 kernels take in whole 16-channel tiles only (width % 16 == 0); the widest
+                              BatchNorm must fit the PRO_MAX-entry coefficient table of the consumer conv that applies it while staging
+                              (a pass of g BatchNorm groups needs g * width entries: CtlNet._check_prologue_tables, per pass)"""
+    if dtype not in ("fp32", "bf16"):
+        raise ValueError(f"dtype {dtype!r}: 'fp32' (the reference's arithmetic) or 'bf16' (bf16 storage + MFMA, fp32 accumulate)")
+    chans = "1, 4, 8, 12 or a multiple of 16"
+    for name, v in (("image_ch", image_ch), ("num_classes", num_classes), ("reduce_factor", reduce_factor)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError(f"{name}={v!r}: a positive integer is needed")
+    if not conv_channels_ok(image_ch):
+        raise ValueError(f"image_ch={image_ch}: the conv kernels take {chans} image channels (pad the images with zero channels to use {image_ch})")
+    if not conv_channels_ok(num_classes) or num_classes > LABEL_MAXC:
+        ok = [c for c in range(1, LABEL_MAXC + 1) if conv_channels_ok(c)]
+        raise ValueError(f"num_classes={num_classes}: accepted are {ok} (conv kernels: {chans}; label-space kernels: at most {LABEL_MAXC} classes)")
+    if reduce_factor > 64 or not _reduce_factor_ok(reduce_factor, dtype):
+        ok = [r for r in range(1, 65) if _reduce_factor_ok(r, dtype)]
+        widths = _internal_widths(reduce_factor) if reduce_factor <= 64 else []
+        why = "stores the internal tensors as bf16, in whole 16-channel tiles" if dtype == "bf16" else f"takes internal widths of {chans}"
+        why += f", at most {PRO_MAX} wide (the staged BatchNorm coefficient table)"
+        raise ValueError(f"reduce_factor={reduce_factor} with dtype={dtype!r}: accepted are {ok} (internal widths {widths}; dtype {dtype!r} {why})")
+
+
 def build_networks(image_ch: int = 1, num_classes: int = 4, reduce_factor: int = 4, device="cuda",
                    state_dicts: Optional[dict] = None, dtype: str = "fp32", encoder_dropout: Optional[float] = None,
                    decoder_dropout: Optional[float] = None) -> Dict[str, CtlNet]:
     """`get_network('FCN_16_standard')` (model.py:76-149).  Without `state_dicts` the weights are drawn exactly like the
-    reference does for the current torch seed (see init.py)."""
+    reference does for the current torch seed (see init.py).  A configuration outside the supported set (check_config) is a ValueError."""
+    check_config(image_ch, num_classes, reduce_factor, dtype)
     z = 512 // reduce_factor
     sds = state_dicts if state_dicts is not None else _init.reference_init_state_dicts(image_ch, num_classes, reduce_factor)
-    if dtype not in ("fp32", "bf16"):
-        raise ValueError(f"dtype {dtype!r}: 'fp32' (the reference's arithmetic) or 'bf16' (bf16 storage + MFMA, fp32 accumulate)")
     b = dtype == "bf16"
     nets = {
         "image_encoder": Dual_Branch_Encoder(image_ch, z, z, reduce_factor, device=device, bf16=b),

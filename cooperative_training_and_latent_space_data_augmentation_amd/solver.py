@@ -24,7 +24,7 @@ from .autograd import cross_entropy_2D, net_apply, scaled_mse, softmax_t, split_
 from .metrics import runningScore
 from .model_util import (_disable_tracking_bn_stats, _draw_seed, mask_latent_code_channel_wise,
                          mask_latent_code_spatial_wise, set_grad)
-from .nets import build_networks
+from .nets import build_networks, check_config
 from .optim import FlatAdam
 
 _DEFAULT_IMG_CFG = {"loss_name": "mse", "mask_type": "random", "max_threshold": 0.5, "random_threshold": True, "if_soft": True}
@@ -63,6 +63,7 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
             raise NotImplementedError(network_type)
         if not use_gpu:
             raise RuntimeError("this engine runs on MI355X only (use_gpu=True); the CPU path is the oracle under oracle/")
+        check_config(image_ch, num_classes, 4, self.compute_dtype)      # ValueError before any storage is allocated
         self.network_type, self.image_ch, self.checkpoint_dir = network_type, image_ch, checkpoint_dir
         self.num_classes, self.learning_rate, self.n_iter = num_classes, learning_rate, n_iter
         self.encoder_dropout, self.decoder_dropout = encoder_dropout, decoder_dropout

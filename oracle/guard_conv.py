@@ -26,6 +26,16 @@ NARROW = [(2, 1, 16, 9, 7), (2, 4, 16, 20, 12), (2, 16, 4, 17, 23), (3, 16, 1, 9
 TILED = [(8, 16, 48, 30, 62), (8, 64, 64, 46, 62), (8, 16, 48, 58, 66)]
 TILED_UP = [(16, 16, 16, 32, 64), (12, 128, 128, 16, 16), (4, 16, 64, 64, 64)]      # in front of a nearest up-sampling (the output is 2h x 2w)
 FIRST = [(16, 1, 16, 64, 64), (3, 4, 32, 20, 12)]                                 # <= 4 input channels at the larger tiles
+# Channel counts off the 16-grid.  cin 8 / 12: the staging code pads the cin chunk to 16 lanes, and in NHWC the lanes past cin of a pixel
+# are the NEXT pixel's channels (a mask that is off by a quad reads real data and multiplies it by the pack's zero weights: only a poisoned,
+# exactly-sized buffer shows it).  cout 20 / 24 / 36 / 40: a whole 16-channel output tile plus a partial one, with one (cot odd) and two
+# (cot even) cout tiles per block; cout 8 / 12 next to cin 8 / 12; both at once.
+OFFGRID = [(2, 8, 16, 9, 7), (2, 12, 32, 17, 23), (3, 8, 8, 20, 12), (2, 12, 12, 9, 7),
+           (2, 16, 20, 9, 7), (2, 32, 24, 17, 23), (2, 16, 40, 9, 7), (2, 64, 36, 5, 6), (2, 16, 8, 9, 7),
+           (2, 8, 20, 9, 7), (2, 12, 24, 17, 23)]
+OFFGRID_EVEN = [(n, ci, co, h + h % 2, w + w % 2) for n, ci, co, h, w in OFFGRID]      # for the stride-2 forms that need even sizes
+# cin = 8 at the two larger pixel tiles (the rule above with one cout tile): 16 * 6 * 4 = 384 blocks of 8x16; 16 * 8 * 4 = 512 blocks of 8x32
+OFFGRID_TILED = [(16, 8, 8, 48, 64), (16, 8, 8, 64, 128)]
 FAMILIES = ["fp32", "x3", "bf16"]
 
 
@@ -155,6 +165,34 @@ def pack_phases(fam, wt, cout_eff, cin_eff, strides, mode):
 
 def x3_ok(cin, cout, ks):
     return ks >= 2 and cin % 16 == 0 and (cout % 16 == 0 or cout in (4, 8, 12))
+
+
+def chan_ok(cin, cout):
+    """the channel counts ctl_conv_pick_cfg serves: cin 1, 4, 8, 12 or a multiple of 16; cout 1 or a multiple of 4"""
+    return (cin in (1, 4, 8, 12) or (cin >= 16 and cin % 16 == 0)) and (cout == 1 or cout % 4 == 0)
+
+
+def refused(kw, names, two=False, wgrad=False):
+    """The library must refuse the descriptor before it launches anything: non-zero status and a ctl_last_error that names the channel
+    count (`names`: the substrings, e.g. "cin 8" or "got 20").  Every pointer is a buffer large enough for the problem all the same."""
+    d = _ffi.conv_desc(**kw)
+    dp = _ffi.desc_ptr(d)
+    n, cin, cout, ks = int(d["n"]), int(d["cin"]), int(d["cout"]), int(d["ks"])
+    px_in, px_out = n * int(d["hin"]) * int(d["win"]), n * int(d["out_h"]) * int(d["out_w"])
+    big = torch.zeros(max(px_in * cin, px_out * cout, 4 * ks * ks * (cin + 16) * (cout + 16), 4096) + 4096, device=DEV)
+    outs = [torch.zeros_like(big) for _ in range(3)]
+    p = big.data_ptr()
+    if wgrad:
+        rc = lib.ctl_conv_wgrad_ex(dp, p, p, p, p, p if two else None, p if two else None, outs[0].data_ptr(), outs[1].data_ptr(), ops.stream_ptr())
+    else:
+        rc = lib.ctl_conv_forward_ex(dp, p, p, p, p, p, p, p, p, p, p, outs[0].data_ptr(), outs[1].data_ptr(), None, outs[2].data_ptr() if int(d["pro_affine"]) == 2 else None,
+                                     ops.stream_ptr())
+    msg = (lib.ctl_last_error() or b"").decode()
+    torch.cuda.synchronize()
+    assert rc != 0, f"the library accepted {kw}"
+    assert all(not bool(o.any()) for o in outs), f"a refused call wrote to an output ({kw})"
+    assert any(s in msg for s in names), f"the refusal does not name the channel count {names}: {msg!r}"
+    return msg
 
 
 def fam_dt(fam, cin, cout, x16=True, y16=True, res16=True):

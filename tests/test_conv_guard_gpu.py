@@ -19,12 +19,13 @@ from cooperative_training_and_latent_space_data_augmentation_amd import _ffi, op
 from cooperative_training_and_latent_space_data_augmentation_amd._ffi import lib, check  # noqa: E402
 from oracle.guarded import Guarded  # noqa: E402
 
-from oracle.guard_conv import (BF, DEV, FAMILIES, FIRST, NARROW, PC, RAGGED, SLOPE, TILED, TILED_UP, close16, dev, f64, fam_dt, gen_for, group_index, judge,  # noqa: E402
-                               judge_sums, each_family, fam_cases, leaky, need, pack, pack_dgrad, pack_fwd, pack_phases, per_group, rb, ref_sums, run_conv, x3_ok)
+from oracle.guard_conv import (BF, DEV, FAMILIES, FIRST, NARROW, OFFGRID, OFFGRID_EVEN, OFFGRID_TILED, PC, RAGGED, SLOPE, TILED, TILED_UP, chan_ok, close16, dev,  # noqa: E402
+                               f64, fam_dt, gen_for, group_index, judge, judge_sums, each_family, fam_cases, leaky, need, pack, pack_dgrad, pack_fwd, pack_phases,
+                               per_group, rb, ref_sums, refused, run_conv, x3_ok)
 
 
 # ------------------------------------------------------------------------------------------------ 3x3 stride 1
-@pytest.mark.parametrize("n,cin,cout,h,w,fam", fam_cases(RAGGED + PC + NARROW + TILED + FIRST + [(8, 128, 128, 32, 32)], 3))
+@pytest.mark.parametrize("n,cin,cout,h,w,fam", fam_cases(RAGGED + PC + NARROW + TILED + FIRST + [(8, 128, 128, 32, 32)] + OFFGRID + OFFGRID_TILED, 3))
 def test_conv3x3_s1_bias_stats_prologue_groups(n, cin, cout, h, w, fam):
     """bias + CTL_EPI_STATS; the pro_affine = 1 prologue; both again with two BatchNorm groups on the even-n cases.  bf16 family: the
     storage combinations of tests/test_bf16_gpu.py (x / y as bf16 or fp32)."""
@@ -77,7 +78,7 @@ def test_conv3x3_s1_bias_stats_prologue_groups(n, cin, cout, h, w, fam):
 
 
 # ------------------------------------------------------------------------------------------------ stride 2, zero insertion, up-sampling
-@pytest.mark.parametrize("n,cin,cout,h,w,fam", fam_cases(RAGGED + PC + NARROW + [(2, 16, 32, 32, 32), (16, 16, 32, 96, 128)], 3))
+@pytest.mark.parametrize("n,cin,cout,h,w,fam", fam_cases(RAGGED + PC + NARROW + [(2, 16, 32, 32, 32), (16, 16, 32, 96, 128)] + OFFGRID + [(16, 8, 8, 96, 128)], 3))
 def test_conv3x3_s2_and_zero_insert_data_gradient(n, cin, cout, h, w, fam):
     """3x3 stride 2 on odd sizes, and its data gradient as a 3x3 conv over the zero-inserted dy (CTL_IN_ZINS2; X3: even sizes, as in
     tests/test_x3_gpu.py)."""
@@ -102,6 +103,9 @@ def test_conv3x3_s2_and_zero_insert_data_gradient(n, cin, cout, h, w, fam):
         # data gradient: conv over the zero-inserted dy with flipped / transposed weights: [n, cout, ho, wo] -> [n, cin, h, w]
         if cin == 1 or (fam == "x3" and (h % 2 or w % 2 or not x3_ok(cout, cin, 3))):
             continue
+        if not chan_ok(cout, cin):                              # cout 20 / 24 / 36 / 40 is no input channel count: the data gradient is refused
+            refused(dict(n=n, hin=ho, win=wo, cin=cout, hout=h, wout=w, cout=cin, ks=3, in_mode=_ffi.IN_ZINS2, dt=fam_dt(f, 16, cin)[0]), [f"got {cout}"])
+            continue
         dtz, dy16, dx16, _ = fam_dt(f, cout, cin)
         dy = dy0.to(torch.bfloat16).float() if dy16 else dy0
         kwz = dict(n=n, hin=ho, win=wo, cin=cout, hout=h, wout=w, cout=cin, ks=3, in_mode=_ffi.IN_ZINS2, dt=dtz)
@@ -112,7 +116,7 @@ def test_conv3x3_s2_and_zero_insert_data_gradient(n, cin, cout, h, w, fam):
             res["dx"] = oz["y"]
 
 
-@pytest.mark.parametrize("n,cin,cout,h,w,fam", fam_cases(RAGGED + PC + NARROW[2:] + TILED_UP, 3))
+@pytest.mark.parametrize("n,cin,cout,h,w,fam", fam_cases(RAGGED + PC + NARROW[2:] + TILED_UP + OFFGRID, 3))
 def test_conv3x3_on_nearest_upsampled_input(n, cin, cout, h, w, fam):
     """CTL_IN_UP2 3x3 with the residual + LeakyReLU epilogue (X3, bf16) or plain (all)"""
     fams = need(fam, cin, cout, 3)
@@ -141,7 +145,7 @@ def test_conv3x3_on_nearest_upsampled_input(n, cin, cout, h, w, fam):
 # ------------------------------------------------------------------------------------------------ 1x1 and the scattered forms
 @pytest.mark.parametrize("fam", ["fp32", "bf16"])
 @pytest.mark.parametrize("up", [0, 1])
-@pytest.mark.parametrize("n,cin,cout,h,w", RAGGED + PC + NARROW[2:] + [(16, 16, 16, 32, 64), (8, 16, 32, 48, 64)])
+@pytest.mark.parametrize("n,cin,cout,h,w", RAGGED + PC + NARROW[2:] + [(16, 16, 16, 32, 64), (8, 16, 32, 48, 64)] + OFFGRID + OFFGRID_TILED[:1])
 def test_conv1x1_residual_leaky_and_accumulate(n, cin, cout, h, w, up, fam):
     g = gen_for(n, cin, cout, h, w, 4 + up)
     ho, wo = (2 * h, 2 * w) if up else (h, w)
@@ -172,7 +176,7 @@ def test_conv1x1_residual_leaky_and_accumulate(n, cin, cout, h, w, up, fam):
 
 
 @pytest.mark.parametrize("fam", ["fp32", "bf16"])
-@pytest.mark.parametrize("n,cin,cout,h,w", RAGGED + PC + [(8, 16, 16, 64, 64)])
+@pytest.mark.parametrize("n,cin,cout,h,w", RAGGED + PC + [(8, 16, 16, 64, 64)] + [s for s in OFFGRID if 8 in s[1:3]])
 def test_conv_transpose2x2_scatter(n, cin, cout, h, w, fam):
     """ConvTranspose2d k2 s2 as four scattered 1x1 problems (nsub = 4): every output pixel belongs to exactly one of them"""
     g = gen_for(n, cin, cout, h, w, 6)
@@ -203,7 +207,7 @@ def _phase_reference(x, wt, b, q, n, cin, cout, h, w):
     return ref
 
 
-@pytest.mark.parametrize("n,cin,cout,h,w,fam", fam_cases(RAGGED + PC + [(8, 16, 16, 64, 64)], 2))
+@pytest.mark.parametrize("n,cin,cout,h,w,fam", fam_cases(RAGGED + PC + [(8, 16, 16, 64, 64)] + OFFGRID, 2))
 def test_phase_convs_pad2_and_pad0(n, cin, cout, h, w, fam):
     """the four 2x2 phase problems (nsub = 4): pad code 2 = conv3x3 on a nearest-upsampled input, with bias and statistics; pad code 0 =
     the data gradient of a stride-2 3x3 conv"""
@@ -235,6 +239,10 @@ def test_phase_convs_pad2_and_pad0(n, cin, cout, h, w, fam):
         # epilogue (dx is dL/da of a = leaky(BN(u)): the partials hold (sum g, sum g*u))
         if f == "x3" and not x3_ok(cout, cin, 2):
             continue
+        if not chan_ok(cout, cin):                              # (cout 20 / 24 / 36 / 40 is no input channel count)
+            refused(dict(n=n, hin=h, win=w, cin=cout, hout=h, wout=w, cout=cin, ks=2, stride=1, pad=0, nsub=4, out_h=2 * h, out_w=2 * w, out_sy=2, out_sx=2,
+                         out_sub=1, dt=fam_dt(f, 16, cin)[0]), [f"got {cout}"])
+            continue
         dt2, dy16, dx16, r16 = fam_dt(f, cout, cin)
         rnd = (lambda t: t.to(torch.bfloat16).float()) if f == "bf16" else (lambda t: t)
         dy = rnd(dy0) if dy16 else dy0
@@ -245,7 +253,9 @@ def test_phase_convs_pad2_and_pad0(n, cin, cout, h, w, fam):
         ref2 = F.conv_transpose2d(q(dy), q(ws), stride=2, padding=1, output_padding=1)
         judge(f, o2["y"], ref2, f"{f} phase data gradient of conv3x3 s2", b16out=dx16, got32=res.get("dx"))
         o3 = None
-        if cin % 16 == 0:
+        if cin % 16 == 0 and f == "bf16" and cout % 16 != 0:      # (bf16 family: CTL_EPI_BNBWD takes bf16-stored tensors, whole 16-channel tiles on both sides)
+            refused(dict(kw2, epi_flags=_ffi.EPI_BNBWD | _ffi.EPI_STATS, epi_slope=SLOPE), [f"cin {cout}"])
+        elif cin % 16 == 0:
             gu = torch.Generator().manual_seed(cin + h)
             u = torch.randn(n, cin, 2 * h, 2 * w, generator=gu)
             u = rnd(u) if r16 else u
@@ -259,7 +269,7 @@ def test_phase_convs_pad2_and_pad0(n, cin, cout, h, w, fam):
             res["dx"], res["dx3"] = o2["y"], None if o3 is None else o3["y"]
 
 
-@pytest.mark.parametrize("n,cin,cout,h,w,fam", fam_cases([(2, 64, 32, 24, 20), (8, 128, 64, 20, 28), (6, 64, 96, 36, 52), (2, 16, 16, 10, 6), (2, 32, 48, 18, 22), (2, 16, 4, 18, 22), (16, 16, 16, 96, 128), (16, 16, 32, 96, 128)], 4))
+@pytest.mark.parametrize("n,cin,cout,h,w,fam", fam_cases([(2, 64, 32, 24, 20), (8, 128, 64, 20, 28), (6, 64, 96, 36, 52), (2, 16, 16, 10, 6), (2, 32, 48, 18, 22), (2, 16, 4, 18, 22), (16, 16, 16, 96, 128), (16, 16, 32, 96, 128)] + OFFGRID_EVEN, 4))
 def test_conv4x4_s2_and_conv2x2_s2_on_even_sizes(n, cin, cout, h, w, fam):
     fams = need(fam, cin, cout, 4)
     g = gen_for(n, cin, cout, h, w, 8)
@@ -422,6 +432,67 @@ def test_tail_backward_epilogue_with_res2_and_pool(form, n, cin, cout, h, w, fam
             assert float((part[k, 1] - r1).abs().max()) <= 5e-4 * float((gref[sel] * v[sel].double()).abs().sum((0, 2, 3)).max()) + 1e-3, what + " sum g*v"
         if f == "fp32":
             res["y"], res["pool"] = o["y"], o.get("pool")
+
+
+# ------------------------------------------------------------------------------------------------ the channel-pad lanes read nothing
+@pytest.mark.parametrize("n,cin,cout,h,w,fam", fam_cases(OFFGRID[:4] + OFFGRID[-2:] + OFFGRID_TILED[:1] + NARROW[1:2], 3, ["fp32", "bf16"]))
+def test_a_poisoned_pixel_reaches_exactly_its_receptive_field(n, cin, cout, h, w, fam):
+    """cin 4 / 8 / 12: the staging pads a pixel's channels to 16 lanes, and in NHWC the lanes past cin are the NEXT pixel's channels.  A
+    channel mask that lets one quad too many through multiplies real, finite data by the pack's zero rows: invisible in every comparison
+    above.  With one pixel of x set to NaN it is not: the NaN must arrive in the 3x3 neighbourhood of that pixel and nowhere else, while a
+    quad read across the pixel boundary carries it (0 * NaN) into the outputs around the pixel BEFORE it in memory -- the left neighbour,
+    or, for the first pixel of a row, the last pixel of the row above.  Everything else is held to the reference by the family's rule."""
+    g = gen_for(n, cin, cout, h, w, 77)
+    x0 = torch.randn(n, cin, h, w, generator=g)
+    wt = torch.randn(cout, cin, 3, 3, generator=g) * 0.2 + 0.05      # (no weight is 0: every output channel of the neighbourhood sees the NaN)
+    dt, x16, y16, _ = fam_dt(fam, cin, cout)
+    assert not x16
+    q = rb if fam == "bf16" else f64
+    wp = pack_fwd(fam, wt)
+    ref = F.conv2d(q(x0), q(wt), padding=1)
+    for h0, w0 in [(h // 2, w // 2), (h // 2, 0), (h - 1, w - 1)]:
+        x = x0.clone()
+        x[0, :, h0, w0] = float("nan")
+        kw = dict(n=n, hin=h, win=w, cin=cin, hout=h, wout=w, cout=cout, ks=3, dt=dt)
+        got = run_conv(kw, dev(x), wp, (n, cout, h, w), y16)["y"].float()
+        hit = torch.zeros(n, 1, h, w, dtype=torch.bool)
+        hit[0, 0, max(h0 - 1, 0):h0 + 2, max(w0 - 1, 0):w0 + 2] = True
+        hit = hit.expand(n, cout, h, w)
+        what = f"{fam} conv3x3 with x[0, :, {h0}, {w0}] = NaN"
+        assert bool(torch.isnan(got[hit]).all()), f"{what}: an output of the pixel's 3x3 neighbourhood did not see it"
+        stray = torch.nonzero(~torch.isfinite(got) & ~hit)
+        assert stray.numel() == 0, f"{what}: {stray.shape[0]} outputs outside its receptive field are not finite, first (n, c, h, w) = {stray[0].tolist()}"
+        if fam == "bf16":
+            judge(fam, torch.where(hit, ref.float(), got), ref, what, b16out=y16)
+        else:
+            judge(fam, torch.where(hit, ref.float(), got), ref, what)
+
+
+# ------------------------------------------------------------------------------------------------ forms with no off-grid variant
+REFUSED_FORMS = {      # form -> (families, the OFFGRID shapes it is refused for)
+    "bn_backward_prologue": (("fp32", "bf16"), lambda cin, cout: cin % 16 != 0),
+    "tail_epilogue": (("fp32", "bf16"), lambda cin, cout: cout % 16 != 0),
+    "bnbwd_epilogue": (("bf16",), lambda cin, cout: cin % 16 != 0 or cout % 16 != 0),
+    "x3": (("x3",), lambda cin, cout: not x3_ok(cin, cout, 3)),
+}
+
+
+@pytest.mark.parametrize("form,n,cin,cout,h,w,fam", [pytest.param(form, *s, f, id=f"{form}-" + "-".join(map(str, s)) + f"-{f}")
+                                                     for form, (fams, bad) in REFUSED_FORMS.items() for s in OFFGRID for f in fams if bad(s[1], s[2])])
+def test_offgrid_forms_are_refused_by_name(form, n, cin, cout, h, w, fam):
+    """The fused backward forms are built on whole 16-channel tiles (the prologue's coefficient quads, the epilogues' row reductions), and
+    the X3 family on whole cin chunks: at an off-grid channel count the call returns an error that names the count and writes nothing.
+    nets.py keeps these layers on the unfused passes instead (tests/test_config_contract_cpu.py)."""
+    dt = _ffi.DT_X3 if fam == "x3" else fam_dt(fam, cin, cout)[0]
+    kw = dict(n=n, hin=h, win=w, cin=cin, hout=h, wout=w, cout=cout, ks=3, dt=dt)
+    if form == "bn_backward_prologue":
+        refused(dict(kw, pro_affine=2, epi_flags=_ffi.EPI_STATS), [f"cin {cin}"])
+    elif form == "tail_epilogue":
+        refused(dict(kw, ks=1, pad=0, epi_flags=_ffi.EPI_TAILBWD | _ffi.EPI_STATS, epi_slope=SLOPE), [f"cout {cout}"])
+    elif form == "bnbwd_epilogue":
+        refused(dict(kw, epi_flags=_ffi.EPI_BNBWD | _ffi.EPI_STATS, epi_slope=SLOPE), [f"cin {cin}", f"cout {cout}"])
+    else:
+        refused(kw, [f"cin {cin}, cout {cout}"])
 
 
 # ------------------------------------------------------------------------------------------------ the checks bite on the device too

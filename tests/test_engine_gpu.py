@@ -66,15 +66,24 @@ def min_preactivation(onet, x):
     return min(vals)
 
 
-def make_pair(name, golden_sd):
-    onet = O.build_networks(init=False)[name]
+def make_pair(name, golden_sd, cfg=()):
+    """cfg: (image_ch, num_classes, reduce_factor) of both builders (tests/test_config_engine_gpu.py); () = the shipped model"""
+    onet = O.build_networks(*cfg, init=False)[name]
     onet.load_state_dict(golden_sd[name])
-    hnet = nets.build_networks(device=DEV, state_dicts={name: golden_sd[name]})[name]
+    hnet = nets.build_networks(*cfg, device=DEV, state_dicts={name: golden_sd[name]})[name]
     return onet, hnet
 
 
 NET_INPUT = {"image_encoder": (1, 64, 48), "shape_encoder": (4, 48, 64), "segmentation_decoder": (128, 4, 3),
              "shape_decoder": (128, 3, 4), "image_decoder": (128, 4, 4)}
+
+
+def net_input(name, cfg=()):
+    """NET_INPUT with the channel counts of a configuration (image_ch, num_classes, reduce_factor)"""
+    c, h, w = NET_INPUT[name]
+    if cfg:
+        c = {"image_encoder": cfg[0], "shape_encoder": cfg[1]}.get(name, 512 // cfg[2])
+    return c, h, w
 
 
 # plan-compiler switches of the fp32 backward (nets.py): the default (tail reduction in the launch that writes dOut, tail apply staged in
@@ -101,11 +110,11 @@ def test_network_forward_backward_vs_oracle(name, mode, switches, golden_sd):
             setattr(nets, k, v)
 
 
-def _network_forward_backward_vs_oracle(name, mode, golden_sd):
-    onet, hnet = make_pair(name, golden_sd)
+def _network_forward_backward_vs_oracle(name, mode, golden_sd, cfg=()):
+    onet, hnet = make_pair(name, golden_sd, cfg)
     onet.train()
     hnet.train()
-    c, h, w = NET_INPUT[name]
+    c, h, w = net_input(name, cfg)
     for seed in range(64):                 # first input without an activation tie (see grads_close_robust)
         g = torch.Generator().manual_seed(seed)
         x = torch.rand(3, c, h, w, generator=g)
@@ -158,15 +167,19 @@ def _network_forward_backward_vs_oracle(name, mode, golden_sd):
 def test_grouped_pass_equals_consecutive_passes(name, n, mode, golden_sd):
     """One pass over two stacked batches with BatchNorm groups (ctl_conv.groups = 2) == the two passes one after the other:
     outputs, input gradients, accumulated parameter gradients, running statistics (updated in call order)."""
+    _grouped_pass_equals_consecutive_passes(name, n, mode, golden_sd)
+
+
+def _grouped_pass_equals_consecutive_passes(name, n, mode, golden_sd, cfg=()):
     from cooperative_training_and_latent_space_data_augmentation_amd.autograd import net_apply
-    c, h, w = NET_INPUT[name]
+    c, h, w = net_input(name, cfg)
     if name == "image_encoder":
         h, w = 96, 80                       # several tiles per image and 16 images: blocks walk across the group boundary
     if "decoder" in name:
         h, w = 4 * h, 4 * w                 # enough pixels per BatchNorm group for a well-conditioned backward
     g = torch.Generator().manual_seed(11)
     xa, xb = torch.rand(n, c, h, w, generator=g), torch.rand(n, c, h, w, generator=g) * 1.7 - 0.2
-    nets_ = [nets.build_networks(device=DEV, state_dicts={name: golden_sd[name]})[name] for _ in range(2)]
+    nets_ = [nets.build_networks(*cfg, device=DEV, state_dicts={name: golden_sd[name]})[name] for _ in range(2)]
     res = []
     for net, grouped in zip(nets_, (False, True)):
         net.train()
@@ -206,8 +219,12 @@ def test_grouped_pass_equals_consecutive_passes(name, n, mode, golden_sd):
 
 @pytest.mark.parametrize("name", list(NET_INPUT))
 def test_network_eval_mode_vs_oracle(name, golden_sd):
-    onet, hnet = make_pair(name, golden_sd)
-    c, h, w = NET_INPUT[name]
+    _network_eval_mode_vs_oracle(name, golden_sd)
+
+
+def _network_eval_mode_vs_oracle(name, golden_sd, cfg=()):
+    onet, hnet = make_pair(name, golden_sd, cfg)
+    c, h, w = net_input(name, cfg)
     g = torch.Generator().manual_seed(7)
     x = torch.rand(2, c, h, w, generator=g)
     with torch.no_grad():

@@ -16,9 +16,11 @@ pytestmark = pytest.mark.gpu
 from cooperative_training_and_latent_space_data_augmentation_amd import _ffi, ops  # noqa: E402
 from cooperative_training_and_latent_space_data_augmentation_amd._ffi import lib, check  # noqa: E402
 from oracle.guarded import GuardedCall  # noqa: E402
-from oracle.guard_conv import DEV, FAMILIES, dev, each_family, f64, fam_dt, gen_for, judge, rb, run_conv, x3_ok  # noqa: E402
+from oracle.guard_conv import DEV, FAMILIES, chan_ok, dev, each_family, f64, fam_dt, gen_for, judge, rb, refused, run_conv, x3_ok  # noqa: E402
 
 SHAPES = [(16, 16, 3), (48, 32, 3), (4, 16, 3), (1, 16, 1), (16, 1, 3), (16, 4, 3), (12, 16, 3), (32, 16, 2), (16, 16, 4), (64, 128, 1)]      # cout, cin, ks
+# cin 8 / 12: the padded cin chunk the conv kernels read as zeros; cout 20 / 24: a whole cout tile and a partial one
+SHAPES += [(16, 8, 3), (8, 16, 3), (8, 8, 3), (16, 12, 3), (12, 12, 3), (20, 16, 3), (24, 32, 3), (8, 8, 2), (8, 8, 4), (8, 16, 1), (20, 8, 3)]
 N, H, W = 2, 9, 7
 GAP = 64                                                      # poisoned floats between two records of one destination
 PACK_FN = {"fp32": "ctl_pack_weights_batched", "x3": "ctl_pack_weights_x3_batched", "bf16": "ctl_pack_weights_bf16_batched"}
@@ -145,7 +147,9 @@ def test_pack_mode0_single_and_three_records(cout, cin, ks, fam):
             if f == "fp32":
                 y32[k] = y
     # the data-gradient orientation (flip, transposed strides): cout_eff = cin, cin_eff = cout
-    if ks == 3 and fam_ok(fam, cin, cout, ks) and cin > 1:
+    if ks == 3 and cin > 1 and not chan_ok(cout, cin):          # (cout 20 / 24 is no input channel count: no conv takes such a pack)
+        refused(conv_kw(cin, cout, ks, 0), [f"got {cout}"])
+    elif ks == 3 and fam_ok(fam, cin, cout, ks) and cin > 1:
         xg = torch.randn(N, cout, H, W, generator=g)
         yd = None
         for f in each_family(("fp32", "x3") if fam == "x3" else (fam,), fam):
@@ -170,7 +174,7 @@ def test_pack_weights_single_entry_point(cout, cin, ks):
     consume("fp32", _At(dst, 0), cout, cin, ks, x0, wt, "ctl_pack_weights")
 
 
-@pytest.mark.parametrize("cout,cin,fam", pack_cases([(16, 16), (48, 32), (4, 16), (12, 16), (64, 128)], 4))
+@pytest.mark.parametrize("cout,cin,fam", pack_cases([(16, 16), (48, 32), (4, 16), (12, 16), (64, 128), (16, 8), (20, 16)], 4))
 def test_pack_mode1_pooled_4x4_from_3x3(cout, cin, fam):
     """mode 1: the 4x4 stride-2 kernel of sumpool2(conv3x3^T(.)), K[u] = sum of the 3x3 taps W[a + 2 - u] over a in {0, 1} per axis,
     formed inside the pack from a 3x3 source read with the record's strides"""
@@ -192,7 +196,7 @@ def test_pack_mode1_pooled_4x4_from_3x3(cout, cin, fam):
 
 
 @pytest.mark.parametrize("mode", [2, 3])
-@pytest.mark.parametrize("cout,cin,fam", pack_cases([(16, 16), (32, 16), (48, 32), (4, 16)], 2))
+@pytest.mark.parametrize("cout,cin,fam", pack_cases([(16, 16), (32, 16), (48, 32), (4, 16), (16, 8), (20, 16)], 2))
 def test_pack_modes_2_and_3_phase_records(cout, cin, fam, mode):
     """modes 2 / 3: the four 2x2 phase kernels of a 3x3 conv on a nearest-upsampled input / of the data gradient of a stride-2 3x3 conv,
     four records back to back (the conv takes them as its four sub-problems)"""

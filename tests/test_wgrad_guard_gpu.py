@@ -19,8 +19,8 @@ pytestmark = pytest.mark.gpu
 from cooperative_training_and_latent_space_data_augmentation_amd import _ffi, ops  # noqa: E402
 from cooperative_training_and_latent_space_data_augmentation_amd._ffi import lib, check  # noqa: E402
 from oracle.guarded import Guarded, GuardedCall  # noqa: E402
-from oracle.guard_conv import (DEV, FAMILIES, NARROW, PC, RAGGED, SLOPE, close16, close32, dev, errs, f64, fam_dt, gen_for, group_index, leaky,  # noqa: E402
-                               per_group, rb)
+from oracle.guard_conv import (DEV, FAMILIES, NARROW, OFFGRID, PC, RAGGED, SLOPE, close16, close32, dev, errs, f64, fam_dt, gen_for, group_index, leaky,  # noqa: E402
+                               per_group, rb, refused)
 
 NEIGHBOURS = (37, 129, 5)                                    # floats of the foreign ranges before, between and behind dW and db
 
@@ -102,7 +102,8 @@ def wgrad_cases(shapes, forms):
             if wgrad_ok(f, s[1], s[2], FORMS[form][0])]
 
 
-@pytest.mark.parametrize("form,n,cin,cout,h,w,fam", wgrad_cases(RAGGED + PC, list(FORMS)) + wgrad_cases(NARROW[2:4], ["3x3", "1x1", "1x1_up2"]))
+@pytest.mark.parametrize("form,n,cin,cout,h,w,fam", wgrad_cases(RAGGED + PC, list(FORMS)) + wgrad_cases(NARROW[2:4], ["3x3", "1x1", "1x1_up2"])
+                         + wgrad_cases(OFFGRID, list(FORMS)))
 def test_wgrad_partials_and_strided_reduce(form, n, cin, cout, h, w, fam):
     """kernel sizes 1, 2, 3; stride 2; nearest-up-sampled input; every form plain and with the activation prologue; accumulate 0 and 1
     on the plain launch (the reduction is the same kernel either way), and on the prologue launch of the 3x3 stride-1 form as well"""
@@ -145,10 +146,13 @@ def test_wgrad_partials_and_strided_reduce(form, n, cin, cout, h, w, fam):
                     res["w", pro, acc], res["b", pro, acc] = oihw(dw, cout, cin, ks), db
 
 
-@pytest.mark.parametrize("n,cin,cout,h,w", NARROW[:2] + [(3, 4, 32, 20, 12)])
-@pytest.mark.parametrize("c4", [0, 1])
+SMALL_CIN = [(c4, *s) for s in NARROW[:2] + [(3, 4, 32, 20, 12)] for c4 in (0, 1)] + [(0, *s) for s in OFFGRID[:4] + OFFGRID[-2:]]
+
+
+@pytest.mark.parametrize("c4,n,cin,cout,h,w", SMALL_CIN, ids=["-".join(map(str, s)) for s in SMALL_CIN])
 def test_wgrad_small_cin_plain_and_k_packed(n, cin, cout, h, w, c4):
-    """the <= 4-channel first layers: the plain path and the row-packed CTL_IN_C4 form (fp32 family), padded cin fragment"""
+    """the <= 4-channel first layers: the plain path and the row-packed CTL_IN_C4 form (fp32 family), padded cin fragment; cin 8 and 12
+    (a padded cin fragment too) on the plain path, between foreign gradient ranges and with accumulate 0 / 1"""
     g = gen_for(n, cin, cout, h, w, 40 + c4)
     x, dy = torch.randn(n, cin, h, w, generator=g), torch.randn(n, cout, h, w, generator=g)
     wref = torch.zeros(cout, cin, 3, 3, dtype=torch.float64, requires_grad=True)
@@ -209,6 +213,13 @@ def test_wgrad_virtual_output_gradient(form, n, cin, cout, h, w, fam):
             judge_w(f, db, bref.grad, what + " db", 1e-3, res.get("b"))
             if f == "fp32":
                 res["w"], res["b"] = dw.view(cin, cout, 3, 3).transpose(0, 1), db
+
+
+@pytest.mark.parametrize("fam", ["fp32", "bf16"])
+@pytest.mark.parametrize("n,cin,cout,h,w", [s for s in OFFGRID if s[2] % 16])
+def test_wgrad_virtual_output_gradient_is_refused_off_grid(n, cin, cout, h, w, fam):
+    """the two-tensor output gradient stages its coefficients per whole 16-channel cout tile: refused by name at cout 8 / 12 / 20 / 24 / 36 / 40"""
+    refused(dict(n=n, hin=h, win=w, cin=cin, hout=h, wout=w, cout=cout, ks=3, dt=fam_dt(fam, cin, cout)[0]), [f"cout {cout}"], two=True, wgrad=True)
 
 
 def test_wgrad_without_a_bias_partial_leaves_db_alone():

@@ -59,6 +59,7 @@ class _Lib:
                      "ctl_wgrad_bias_partial_floats", "ctl_latent_score_ws_floats", "ctl_latent_mask_apply_ws_floats",
                      "ctl_rescale_intensity_ws_floats", "ctl_sizeof_op", "ctl_sizeof_conv", "ctl_latent_mask_fused_ws_floats", "ctl_conv_wpack_floats_x3",
                      "ctl_surface_stats_ws_bytes", "ctl_surface_map_ws_bytes", "ctl_cc_ws_bytes", "ctl_aug_ws_bytes", "ctl_aug_warp_ws_bytes",
+                     "ctl_surface_quantiles_ws_bytes",
                      "ctl_aug_spline_ws_bytes", "ctl_aug_warp_cubic_ws_bytes", "ctl_aug_bias_ws_bytes", "ctl_order_stats_ws_bytes", "ctl_corrupt_spike_ws_bytes"):
             getattr(lib, name).restype = C.c_size_t
         p, i32, i64, f32, u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64
@@ -125,6 +126,8 @@ class _Lib:
             "ctl_surface_stats_rows": [i32, i32, i32, i32], "ctl_surface_stats_ws_bytes": [i32] * 6,
             "ctl_surface_stats": [p, p, i32, i32, i32, i32, i32, i32, i32, p, p, p, C.c_size_t, p],
             "ctl_surface_map_ws_bytes": [i32] * 4,
+            "ctl_surface_quantiles_ws_bytes": [i32] * 7,
+            "ctl_surface_quantiles": [p, p, i32, i32, i32, i32, i32, i32, i32, p, p, i32, p, p, p, C.c_size_t, p],
             "ctl_surface_map": [p, i32, i32, i32, i32, i32, p, p, p, p, C.c_size_t, p],
             "ctl_cc_ws_bytes": [i32] * 5, "ctl_cc_label": [p, i32, i32, i32, i32, i32, i32, p, p],
             "ctl_cc_keep_largest": [p, i32, i32, i32, i32, i32, i32, p, p, p, C.c_size_t, p],
@@ -179,7 +182,8 @@ EXPORTED = ["ctl_version", "ctl_last_error", "ctl_conv_wpack_floats", "ctl_conv_
             "ctl_aug_warp", "ctl_aug_spline_ws_bytes", "ctl_aug_warp_cubic_ws_bytes", "ctl_aug_spline_coeffs", "ctl_aug_warp_cubic",
             "ctl_aug_bias_ws_bytes", "ctl_aug_bias", "ctl_aug_coarse_field", "ctl_order_stats_ws_bytes", "ctl_order_stats",
             "ctl_percentile_apply", "ctl_resample_inplane", "ctl_corrupt_bias", "ctl_corrupt_spike_ws_bytes", "ctl_corrupt_spike",
-            "ctl_corrupt_rigid3d", "ctl_axis_operator", "ctl_slice_foreground", "ctl_batch_gather"]
+            "ctl_corrupt_rigid3d", "ctl_axis_operator", "ctl_slice_foreground", "ctl_batch_gather", "ctl_surface_quantiles_ws_bytes",
+            "ctl_surface_quantiles"]
 
 
 def prof_start(kernel_filter: str = "", every: int = 1) -> None:

@@ -154,6 +154,95 @@ def asd(result, reference, voxelspacing=None, connectivity=1) -> float:
     return 1e100
 
 
+def _percentile_ranks(n: int, q: float):
+    """numpy's default ('linear') percentile of n sorted values sits between ranks k and min(k + 1, n - 1) at fraction g:
+    v = (n - 1) * (q / 100), k = floor(v), g = v - k, all in float64.  -> (k, min(k + 1, n - 1), g)."""
+    if not 0.0 <= q <= 100.0:                              # also refuses NaN
+        raise ValueError("Percentiles must be in the range [0, 100]")
+    v = np.float64(n - 1) * (np.float64(q) / np.float64(100.0))
+    k = int(np.floor(v))
+    return k, min(k + 1, n - 1), np.float64(v - np.float64(k))
+
+
+def _percentile_from_ranks(a, b, g) -> float:
+    """numpy's `_lerp` between the distances a (rank k) and b (rank k + 1) at fraction g: the ONE place where a percentile of surface
+    distances is finished, for the host lists and for the two squared order statistics the device returns alike."""
+    a, b, g = np.float64(a), np.float64(b), np.float64(g)
+    d = b - a
+    return float(a + d * g if g < 0.5 else b - d * (1 - g))
+
+
+def _percentile_from_table(e, q: float) -> float:
+    """e: one host entry (d^2 of rank k, d^2 of rank k + 1, n, flag) of ops.surface_quantiles, flag 0."""
+    return _percentile_from_ranks(np.sqrt(e[0]), np.sqrt(e[1]), _percentile_ranks(int(e[2]), q)[2])
+
+
+def _device_quantiles(result, reference, q, spacing, connectivity, per_slice):
+    """ops.surface_quantiles (with the statistics table) of two binary device objects, read back in one copy ->
+    (q entries [slices or 1, 4], statistics [2, slices or 1, 4])."""
+    import torch
+    from . import ops
+    if result.dim() not in (2, 3) or tuple(result.shape) != tuple(reference.shape) or (per_slice and result.dim() != 3):
+        raise ValueError(f"device surface distances need two [H,W] or [D,H,W] tensors of one shape, got {tuple(result.shape)} and "
+                         f"{tuple(reference.shape)}")
+    vol = (-1,) + tuple(result.shape[-2:])
+    qt, st = ops.surface_quantiles((result != 0).reshape(vol), (reference != 0).reshape(vol), 2, (q,), spacing, connectivity,
+                                   "2d" if (per_slice or result.dim() == 2) else "3d", foreground_only=True, want_stats=True)
+    flat = torch.cat([qt.reshape(-1), st.reshape(-1)]).cpu().numpy()
+    return flat[:qt.numel()].reshape(tuple(qt.shape))[0, :, 0], flat[qt.numel():].reshape(tuple(st.shape))[0]
+
+
+def surface_distance_percentile(result, reference, q, voxelspacing=None, connectivity=1) -> float:
+    """The q-th percentile (0 <= q <= 100, numpy's default linear method on float64) of the surface distances of BOTH directions pooled
+    into one list: np.percentile(np.hstack((surface_distances(result, reference), surface_distances(reference, result))), q).
+    q = 100 is `hd`, q = 0 the smallest pooled distance.  Two CUDA tensors ([H,W] or [D,H,W]): one ops.surface_quantiles call (exact
+    rank selection on the device) and one small readback."""
+    _percentile_ranks(2, q)                                # the range check, before any work
+    if _on_device(result, reference):
+        e, st = _device_quantiles(result, reference, q, voxelspacing, connectivity, per_slice=False)
+        _raise_if_empty(st[1, 0, 2] == 0, st[0, 0, 2] == 0)
+        return _percentile_from_table(e[0], q)
+    pooled = np.sort(np.hstack((surface_distances(result, reference, voxelspacing, connectivity),
+                                surface_distances(reference, result, voxelspacing, connectivity))))
+    k, k1, g = _percentile_ranks(pooled.size, q)
+    return _percentile_from_ranks(pooled[k], pooled[k1], g)
+
+
+def hd95(result, reference, voxelspacing=None, connectivity=1) -> float:
+    """95th-percentile Hausdorff distance as medpy >= 0.4 documents it: np.percentile(np.hstack((d(result -> reference),
+    d(reference -> result))), 95).  RuntimeError on an empty mask, as `hd`."""
+    return surface_distance_percentile(result, reference, 95.0, voxelspacing, connectivity)
+
+
+def hd95_2D_stack(result, reference, pixelspacing=None, connectivity=1) -> float:
+    """Mean in-plane `hd95` over the slices where both masks are non-empty; -1 when there is none (the form of `hd_2D_stack`,
+    measure.py:381-399).  Two CUDA [D,H,W] tensors: every slice in one ops.surface_quantiles call."""
+    if _on_device(result, reference):
+        e, _ = _device_quantiles(result, reference, 95.0, pixelspacing, connectivity, per_slice=True)
+        return _hd95_stack_from_table(e)
+    vals = [hd95(r, g, pixelspacing, connectivity) for r, g in zip(result, reference) if r.sum() > 0 and g.sum() > 0]
+    return sum(vals) / len(vals) if vals else -1
+
+
+def _hd95_stack_from_table(e) -> float:
+    """e: host entries [slices, 4] of one class in the per-slice form at q = 95 -> `hd95_2D_stack`."""
+    vals = [_percentile_from_table(e[z], 95.0) for z in range(e.shape[0]) if e[z, 3] == 0]
+    return sum(vals) / len(vals) if vals else -1
+
+
+def assd(result, reference, voxelspacing=None, connectivity=1) -> float:
+    """Average symmetric surface distance (measure.py:402-455): the mean of `asd` in both directions; 1e100 when either mask is empty,
+    as `asd`.  Two CUDA tensors: both directions are rows of ONE ops.surface_stats table."""
+    if _on_device(result, reference):
+        return _assd_from_table(_device_table(result, reference, voxelspacing, connectivity, per_slice=False)[0, :, 0].cpu().numpy())
+    return float(np.mean((asd(result, reference, voxelspacing, connectivity), asd(reference, result, voxelspacing, connectivity))))
+
+
+def _assd_from_table(t) -> float:
+    """t: host table [2, 4] of one class in the whole-volume form -> `assd` (side 1 = result -> reference, side 0 = the reverse)."""
+    return float(np.mean((t[1, 1] / t[1, 2], t[0, 1] / t[0, 2]))) if t[1, 3] == 0 else 1e100
+
+
 class runningMySegmentationScore(object):
     """Patient-wise scores of 3-D predictions (metrics.py:139-291): one row per patient, one column per (foreground class, metric).
 
@@ -161,8 +250,11 @@ class runningMySegmentationScore(object):
     those come from the confusion-matrix kernel (one launch pair and one 2*n^2-word readback per patient instead of 2*(n-1)
     full-volume host copies and masks).  The surface-distance metrics 'HD' and 'ASD' (measure.py:333-548) are, for device tensors,
     one `ops.surface_stats` call each (exact fp64 distance transform of every class and both directions in 4 / 5 launches) and one
-    readback of their small tables per patient: no label volume leaves the device.  numpy inputs run scipy on the host, as upstream."""
-    SUPPORTED = ("Dice", "VolError", "VolSim", "HD", "ASD")
+    readback of their small tables per patient: no label volume leaves the device.  numpy inputs run scipy on the host, as upstream.
+    'HD95' (`hd95_2D_stack`, with the conventions of 'HD') and 'ASSD' (`assd`, with those of 'ASD') are this project's additions to the
+    table: 'HD95' comes from `ops.surface_quantiles`, in the same launches as 'HD' when both are asked for, 'ASSD' from the table of
+    'ASD'."""
+    SUPPORTED = ("Dice", "VolError", "VolSim", "HD", "ASD", "HD95", "ASSD")
 
     def __init__(self, n_classes, idx2cls_dict=None, metrics_list=("Dice",), foreground_only=False):
         self.n_classes, self.metrics, self.foreground_only = n_classes, list(metrics_list), foreground_only
@@ -205,16 +297,23 @@ class runningMySegmentationScore(object):
         return pc, gc, ic
 
     def _surface_tables(self, preds, gts, surf, voxel_spacing):
-        """{'HD': host table [classes, 2, slices, 4], 'ASD': [classes, 2, 1, 4]} of one patient from ops.surface_stats (same masks,
-        8- / 18-neighbourhood surfaces and spacing convention as the host branch of `update`); both tables come back in one copy."""
+        """{'HD': host table [classes, 2, slices, 4], 'ASD': [classes, 2, 1, 4], 'HD95': [classes, slices, 1, 4]} of one patient from
+        ops.surface_stats / ops.surface_quantiles (same masks, 8- / 18-neighbourhood surfaces and spacing convention as the host branch
+        of `update`); all tables come back in one copy.  'HD' with 'HD95' is ONE surface_quantiles call that also writes the statistics
+        table (3 launches more than surface_stats alone, against a second full set of distance passes); 'ASSD' reads the 'ASD' table."""
         import torch
         from . import ops
         if any(c >= self.n_classes for c in self.idx2cls_dict):
             raise ValueError("idx2cls_dict names a class outside [0, n_classes): pass host arrays")
         tabs = {}
-        if "HD" in surf:
+        if "HD95" in surf and "HD" in surf:
+            tabs["HD95"], tabs["HD"] = ops.surface_quantiles(preds, gts, self.n_classes, (95.0,), voxel_spacing[:2], 2, "2d",
+                                                             self.foreground_only, want_stats=True)
+        elif "HD95" in surf:
+            tabs["HD95"] = ops.surface_quantiles(preds, gts, self.n_classes, (95.0,), voxel_spacing[:2], 2, "2d", self.foreground_only)
+        elif "HD" in surf:
             tabs["HD"] = ops.surface_stats(preds, gts, self.n_classes, voxel_spacing[:2], 2, "2d", self.foreground_only)
-        if "ASD" in surf:
+        if "ASD" in surf or "ASSD" in surf:
             tabs["ASD"] = ops.surface_stats(preds, gts, self.n_classes, voxel_spacing, 2, "3d", self.foreground_only)
         flat = torch.cat([t.reshape(-1) for t in tabs.values()]).cpu().numpy()
         out, lo = {}, 0
@@ -230,11 +329,11 @@ class runningMySegmentationScore(object):
         if voxel_spacing is not None and len(voxel_spacing) != 3:
             raise AssertionError(f"check voxel spacing, {voxel_spacing}")
         pc, gc, ic = self._counts(preds, gts)
-        surf = [m for m in self.metrics if m in ("HD", "ASD")]
+        surf = [m for m in self.metrics if m in ("HD", "ASD", "HD95", "ASSD")]
         if surf:
             if voxel_spacing is None:
-                raise ValueError("'HD' / 'ASD' need the voxel spacing (x, y, z) of the volume")
-            if "HD" in surf:      # metrics.py:225-229: the in-plane pair is voxel_spacing[:2]; upstream's own guard on the axis order
+                raise ValueError("'HD' / 'ASD' / 'HD95' / 'ASSD' need the voxel spacing (x, y, z) of the volume")
+            if "HD" in surf or "HD95" in surf:      # metrics.py:225-229: the in-plane pair is voxel_spacing[:2]; upstream's own guard on the axis order
                 assert voxel_spacing[0] >= voxel_spacing[2], "z spacing should be in last dim in the cardiac imaging"
             if _on_device(preds, gts):                     # one fused launch sequence per metric, ONE readback of the small tables
                 dev_tab = self._surface_tables(preds, gts, surf, voxel_spacing)
@@ -253,11 +352,18 @@ class runningMySegmentationScore(object):
                 elif m in ("HD", "ASD") and dev_tab is not None:
                     t = dev_tab[m][0 if self.foreground_only else c - 1]
                     score = float(_hd_stack_from_table(t) if m == "HD" else _asd_from_table(t[:, 0]))
-                elif m in ("HD", "ASD"):
+                elif m in ("HD95", "ASSD") and dev_tab is not None:
+                    ci = 0 if self.foreground_only else c - 1
+                    score = float(_hd95_stack_from_table(dev_tab["HD95"][ci][:, 0]) if m == "HD95" else _assd_from_table(dev_tab["ASD"][ci][:, 0]))
+                elif m in ("HD", "ASD", "HD95", "ASSD"):
                     pm = (p_h > 0) if self.foreground_only else (p_h == c)
                     gm = (g_h > 0) if self.foreground_only else (g_h == c)
                     if m == "HD":                          # 2-D stack, 8-neighbourhood surfaces (metrics.py:224-230)
                         score = hd_2D_stack(pm, gm, pixelspacing=voxel_spacing[:2], connectivity=2)
+                    elif m == "HD95":                      # the same conventions as 'HD'
+                        score = hd95_2D_stack(pm, gm, pixelspacing=voxel_spacing[:2], connectivity=2)
+                    elif m == "ASSD":                      # the same conventions as 'ASD'
+                        score = assd(pm, gm, voxelspacing=voxel_spacing, connectivity=2)
                     else:
                         score = asd(pm, gm, voxelspacing=voxel_spacing, connectivity=2)
                     score = float(score)

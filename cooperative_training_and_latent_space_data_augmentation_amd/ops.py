@@ -392,6 +392,36 @@ def surface_stats(pred: torch.Tensor, gt: torch.Tensor, n_class: int, sampling=N
     return table.view(-1, 2, d if mode == 2 else 1, 4)
 
 
+def surface_quantiles(pred: torch.Tensor, gt: torch.Tensor, n_class: int, q=(95.0,), sampling=None, connectivity: int = 1, mode="3d",
+                      foreground_only: bool = False, want_stats: bool = False):
+    """Order statistics of the pooled surface distances (both directions in one list) of every foreground class of one patient: what
+    `metrics.hd95` / `surface_distance_percentile` need.  `q`: 1 to 4 percentages in [0, 100].  -> fp64 device table
+    [classes, D if mode == '2d' else 1, len(q), 4]; with n pooled distances and k = floor((n - 1) * q / 100) an entry is (d^2 of rank k,
+    d^2 of rank min(k + 1, n - 1), n, 1.0 if either mask is empty); an entry with the flag set is (inf, inf, 0, 1).
+    `metrics._percentile_from_ranks` finishes numpy's percentile from it.  want_stats: -> (that table, the table `surface_stats` returns
+    for the same arguments, same bits) from the same launches.  3 launches more than `surface_stats`."""
+    require_gpu(pred, gt)
+    mode = _surface_mode(mode)
+    if pred.dim() != 3 or tuple(pred.shape) != tuple(gt.shape):
+        raise ValueError(f"surface_quantiles: expected two [D,H,W] volumes of one shape, got {tuple(pred.shape)} and {tuple(gt.shape)}")
+    qs = [float(v) for v in np.atleast_1d(np.asarray(q, dtype=np.float64))]
+    p, g = pred.to(torch.uint8).contiguous(), gt.long().contiguous()
+    d, h, w = (int(v) for v in p.shape)
+    samp = _surface_sampling(sampling, mode)
+    nbytes = lib.ctl_surface_quantiles_ws_bytes(d, h, w, n_class, int(foreground_only), mode, len(qs))
+    rows = lib.ctl_surface_stats_rows(d, n_class, int(foreground_only), mode) if nbytes else 0
+    groups = max(rows, 0) // 2
+    q_table = torch.empty((groups, max(len(qs), 1), 4), dtype=torch.float64, device=p.device)
+    stats = torch.empty((max(rows, 0), 4), dtype=torch.float64, device=p.device) if want_stats else None
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=p.device)
+    check(lib.ctl_surface_quantiles(ptr(p), ptr(g), d, h, w, n_class, int(foreground_only), mode, int(connectivity), samp,
+                                    (C.c_double * max(len(qs), 1))(*qs), len(qs), ptr(stats) if want_stats else None, ptr(q_table), ptr(ws),
+                                    nbytes, stream_ptr()), "ctl_surface_quantiles")
+    gpm = d if mode == 2 else 1
+    q_table = q_table.view(-1, gpm, len(qs), 4)
+    return (q_table, stats.view(-1, 2, gpm, 4)) if want_stats else q_table
+
+
 def _surface_map(mask: torch.Tensor, sampling, connectivity: int, per_slice: bool, want_d2: bool):
     require_gpu(mask)
     if mask.dim() not in (2, 3) or (per_slice and mask.dim() != 3):

@@ -403,13 +403,39 @@ int ctl_crop_or_pad(const void* src, void* dst, int32_t elem_bytes, int32_t n, i
  * ctl_surface_map: the same passes for ONE mask (uint8, non-zero = inside): d2_out (fp64 [D,H,W], may be NULL) = squared distance of
  *   every voxel to the nearest surface voxel of the mask (+inf when there is none), surface_out (uint8 [D,H,W] of 0 / 1, may be NULL) =
  *   the surface map itself; 1 to 4 launches.  The workspace is needed only with d2_out.
+ * ctl_surface_quantiles: order statistics of the POOLED surface distances of a class, i.e. of both directions in ONE list, which is what
+ *   the 95th-percentile Hausdorff distance needs ('HD95': medpy >= 0.4 `hd95` = np.percentile(np.hstack((d(result -> reference),
+ *   d(reference -> result))), 95); in the score table per slice and averaged, by analogy with 'HD' of
+ *   medseg/common_utils/metrics.py:226-233).  The average symmetric surface distance ('ASSD', measure.py:402-455) needs no selection: it
+ *   is the mean of sum / number of rows (c, 0) and (c, 1) of the 3-D statistics table.
+ *   Masks, surfaces, mode, connectivity, sampling, the axis limit and the workspace alignment are those of ctl_surface_stats.
+ *   q         HOST array of n_q (1..4) percentages, each finite and in [0, 100], read during the call; the call passes q[j] / 100.0
+ *             (one fp64 division on the host) to the device by value.
+ *   q_table   fp64 [classes][G][n_q][4], G = D in mode 2 and 1 in mode 3, classes as in ctl_surface_stats (class_index = c - 1).  A
+ *             group (class, slice in mode 2) pools the n sampled squared distances of both sides; with k = floor((n - 1) * q / 100)
+ *             (one fp64 multiply on the device) the entry is {d^2 of rank k, d^2 of rank min(k + 1, n - 1), n, flag} in ascending
+ *             order, from which the host finishes numpy's linear-interpolation percentile of the distances exactly (sqrt is monotone).
+ *             flag = 1.0 when either mask of the group is empty; the entry is then {+inf, +inf, 0, 1}.
+ *   stats_table  NULL, or the table ctl_surface_stats writes for the same arguments: the same rows, reduction order and bits.
+ *   launches  those of ctl_surface_stats (4 / 5; the last one is left out when stats_table is NULL) plus exactly 3: surface-voxel counts
+ *             per (side, slice, class), their scan into key-list offsets, and the selection.  The number does not depend on D, H, W,
+ *             n_class, n_q or the content; there is no readback and no synchronisation.  Selection is an exact most-significant-digit-
+ *             first radix selection over the 64 bits of the squared distances with integer atomics only; the order in which keys land in
+ *             the workspace differs from call to call, every output is the same bits on every call.
  * Workspaces are caller-owned, sized by the *_ws_bytes queries (0 for arguments the call itself would refuse) and need 256-byte
- * alignment.  Every axis is limited to 65534 elements. */
+ * alignment.  Every axis is limited to 65534 elements.  Every argument error of ctl_surface_quantiles returns CTL_EINVAL with a
+ * message that names surface_quantiles, before anything is launched. */
 int32_t ctl_surface_stats_rows(int32_t d, int32_t n_class, int32_t foreground_only, int32_t mode);
 size_t ctl_surface_stats_ws_bytes(int32_t d, int32_t h, int32_t w, int32_t n_class, int32_t foreground_only, int32_t mode);
 int ctl_surface_stats(const uint8_t* pred, const int64_t* gt, int32_t d, int32_t h, int32_t w, int32_t n_class,
                       int32_t foreground_only, int32_t mode, int32_t connectivity, const double* sampling, double* table,
                       void* workspace, size_t workspace_bytes, ctl_stream stream);
+size_t ctl_surface_quantiles_ws_bytes(int32_t d, int32_t h, int32_t w, int32_t n_class, int32_t foreground_only, int32_t mode,
+                                      int32_t n_q);
+int ctl_surface_quantiles(const uint8_t* pred, const int64_t* gt, int32_t d, int32_t h, int32_t w, int32_t n_class,
+                          int32_t foreground_only, int32_t mode, int32_t connectivity, const double* sampling, const double* q,
+                          int32_t n_q, double* stats_table, double* q_table, void* workspace, size_t workspace_bytes,
+                          ctl_stream stream);
 size_t ctl_surface_map_ws_bytes(int32_t d, int32_t h, int32_t w, int32_t mode);
 int ctl_surface_map(const uint8_t* mask, int32_t d, int32_t h, int32_t w, int32_t mode, int32_t connectivity,
                     const double* sampling, double* d2_out, uint8_t* surface_out, void* workspace, size_t workspace_bytes,

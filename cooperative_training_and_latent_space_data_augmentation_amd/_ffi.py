@@ -141,6 +141,8 @@ class _Lib:
             "ctl_order_stats_ws_bytes": [i32, i32], "ctl_order_stats": [p, i32, i64, p, i32, p, p, C.c_size_t, p],
             "ctl_percentile_apply": [p, p, i32, i64, C.c_double, C.c_double, i32, f32, f32, p, p, p],
             "ctl_resample_inplane": [p, p, i32, i32, i32, i32, i32, i32, C.c_double, C.c_double, p, p, p],
+            "ctl_restore_scores": [p, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.c_double, C.c_double, i32, p, p, p],
+            "ctl_restore_labels": [p, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.c_double, C.c_double, p, p],
             "ctl_corrupt_bias": [p, p, i32, i32, i32, p, p], "ctl_corrupt_spike_ws_bytes": [i32] * 4,
             "ctl_corrupt_spike": [p, i32, i32, i32, p, p, i32, C.c_double, p, p, C.c_size_t, p],
             "ctl_corrupt_rigid3d": [p, i32, i32, i32, p, i32, p, p], "ctl_axis_operator": [p, p, i32, i32, i32, i32, i32, p, p, p],
@@ -183,7 +185,7 @@ EXPORTED = ["ctl_version", "ctl_last_error", "ctl_conv_wpack_floats", "ctl_conv_
             "ctl_aug_bias_ws_bytes", "ctl_aug_bias", "ctl_aug_coarse_field", "ctl_order_stats_ws_bytes", "ctl_order_stats",
             "ctl_percentile_apply", "ctl_resample_inplane", "ctl_corrupt_bias", "ctl_corrupt_spike_ws_bytes", "ctl_corrupt_spike",
             "ctl_corrupt_rigid3d", "ctl_axis_operator", "ctl_slice_foreground", "ctl_batch_gather", "ctl_surface_quantiles_ws_bytes",
-            "ctl_surface_quantiles"]
+            "ctl_surface_quantiles", "ctl_restore_scores", "ctl_restore_labels"]
 
 
 def prof_start(kernel_filter: str = "", every: int = 1) -> None:

@@ -876,6 +876,63 @@ def resample_inplane(image: torch.Tensor, spacing, new_spacing, label: Optional[
     return image_out, label_out, (float(new_spacing[0]), float(new_spacing[1]), float(spacing[2]))
 
 
+# ------------------------------------------------------------------------------------------------ native-grid restoration
+RESTORE_MODES = {"logit": 0, "prob": 1}
+
+
+def _restore_args(geometry, n: int, window, who: str):
+    """The scalars of a prepare.Geometry as ctl_restore_* takes them, after checking the window of the input against the record."""
+    (h, w), (rh, rw), (hc, wc) = geometry.native_hw, geometry.resampled_hw, geometry.window_hw
+    if tuple(int(v) for v in window) != (int(hc), int(wc)):
+        raise ValueError(f"{who}: the input's window {tuple(int(v) for v in window)} is not the geometry's {(int(hc), int(wc))}")
+    return (int(n), int(hc), int(wc), int(h), int(w), int(rh), int(rw), int(geometry.offset[0]), int(geometry.offset[1]),
+            float(geometry.q[0]), float(geometry.q[1]))
+
+
+def _restore_out(out: Optional[torch.Tensor], shape, device, who: str) -> torch.Tensor:
+    if out is None:
+        return torch.empty(shape, dtype=torch.uint8, device=device)
+    if not (out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == tuple(shape) and out.is_contiguous()):
+        raise ValueError(f"{who}: `out` must be a contiguous uint8 device tensor of shape {tuple(shape)}")
+    return out
+
+
+def restore_scores(scores: torch.Tensor, geometry, mode: str = "logit", want_soft: bool = False, out: Optional[torch.Tensor] = None):
+    """Window-grid class scores [n,C,Hc,Wc] (float32, what `predict` returns; 1 <= C <= 16) -> the uint8 label volume [n,h,w] on the
+    native grid of `geometry` (prepare.Geometry), or (label, soft) with want_soft: soft float32 [n,C,h,w], plain contiguous planes.
+    Bilinear in fp64 over the logits (mode "logit") or over each pixel's softmax (mode "prob"), arg-max on the fp64 values; outside the
+    window or the resampled extent the label is 0 (ctl_restore_scores).  `out`: a contiguous uint8 device tensor [n,h,w], e.g. a slice
+    [lo:hi] of a patient's volume.  One launch, no readback."""
+    if mode not in RESTORE_MODES:
+        raise ValueError(f"restore_scores: mode {mode!r}, one of {sorted(RESTORE_MODES)}")
+    if scores.dim() != 4 or scores.dtype != torch.float32:
+        raise ValueError(f"restore_scores: expected float32 scores [n,C,Hc,Wc], got {scores.dtype} {tuple(scores.shape)}")
+    n, c = int(scores.shape[0]), int(scores.shape[1])
+    args = _restore_args(geometry, n, scores.shape[2:], "restore_scores")
+    require_gpu(scores, out)
+    scores = as_nhwc(scores)
+    h, w = args[3], args[4]
+    label = _restore_out(out, (n, h, w), scores.device, "restore_scores")
+    soft = torch.empty((n, c, h, w), dtype=torch.float32, device=scores.device) if want_soft else None
+    check(lib.ctl_restore_scores(ptr(scores), args[0], c, *args[1:], RESTORE_MODES[mode], ptr(label), ptr(soft), stream_ptr()),
+          "ctl_restore_scores")
+    return (label, soft) if want_soft else label
+
+
+def restore_labels(labels: torch.Tensor, geometry, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Window-grid uint8 labels [n,Hc,Wc] -> uint8 [n,h,w] on the native grid of `geometry`: the nearest window pixel, 0 outside
+    (ctl_restore_labels).  `out` as in restore_scores.  One launch, no readback."""
+    if labels.dim() != 3 or labels.dtype != torch.uint8:
+        raise ValueError(f"restore_labels: expected uint8 labels [n,Hc,Wc], got {labels.dtype} {tuple(labels.shape)}")
+    n = int(labels.shape[0])
+    args = _restore_args(geometry, n, labels.shape[1:], "restore_labels")
+    require_gpu(labels, out)
+    labels = labels.contiguous()
+    res = _restore_out(out, (n, args[3], args[4]), labels.device, "restore_labels")
+    check(lib.ctl_restore_labels(ptr(labels), *args, ptr(res), stream_ptr()), "ctl_restore_labels")
+    return res
+
+
 # ------------------------------------------------------------------------------------------------ MR artefact corruption
 def _volume(x: torch.Tensor, who: str):
     """A float32 device volume [D,H,W] (a tester pack [D,1,H,W] is viewed as one) -> (contiguous [D,H,W] tensor, d, h, w)."""

@@ -8,7 +8,13 @@ per-slice min-max rescale.  A numpy input is uploaded once; everything after tha
 
 The `*_host` functions are the same statements as plain numpy (fp64 where the device computes in fp64, float32 with one rounding per
 operation where it computes in float32).  They are what the device results are tested against; scipy appears only in the tests that
-cross-check them."""
+cross-check them.
+
+The way back is recorded too: `geometry` keeps what the forward trip did to the in-plane grid (resampling ratios, sizes, crop offset),
+and `restore_prediction` puts a window-grid prediction back on the patient's native grid with it (ops.restore_scores /
+ops.restore_labels; `restore_scores_host` / `restore_labels_host` are the numpy statements)."""
+import collections
+
 import numpy as np
 import torch
 
@@ -48,10 +54,46 @@ def load_volume(image, label=None, spacing=None, new_spacing=None, normalize=Fal
     return image_d, label_d, spacing_out
 
 
-def prepare_patient(image, label, spacing=None, new_spacing=None, normalize=False, crop_size=None, normalize_2D=True):
+class Geometry(collections.namedtuple("Geometry", "native_hw resampled_hw window_hw offset q spacing")):
+    """What the forward trip (ops.resample_inplane, then ops.crop_or_pad) did to the in-plane grid of one patient, immutable:
+    native_hw (h, w); resampled_hw (h', w'); window_hw (Hc, Wc); offset (dy, dx) = floor((resampled - window) / 2), negative when the
+    window was padded; q (q_h, q_w) = native spacing / new spacing, exactly (1.0, 1.0) when nothing was resampled; spacing = the native
+    (x, y, z) or None.  Native index i sits at resampled-grid coordinate i * q and at window coordinate i * q - offset."""
+    __slots__ = ()
+
+
+def geometry(n, h, w, spacing=None, new_spacing=None, crop_size=None):
+    """The Geometry of a [n,h,w] volume prepared with (spacing, new_spacing, crop_size), from ops.resample_geometry: sizes by upstream's
+    rounding, q = spacing / new_spacing per axis (one fp64 division each; entry 0 of a spacing is the WIDTH axis), identity when no
+    new_spacing is given or upstream's sum rule says so.  crop_size None: the window is the resampled size."""
+    h, w = int(h), int(w)
+    rh, rw, q = h, w, (1.0, 1.0)
+    if new_spacing is not None:
+        if spacing is None:
+            raise ValueError("geometry: new_spacing needs the spacing of the input")
+        new_h, new_w, _, _, identity = ops.resample_geometry(n, h, w, spacing, new_spacing)
+        if not identity:
+            rh, rw = new_h, new_w
+            q = (float(spacing[1]) / float(new_spacing[1]), float(spacing[0]) / float(new_spacing[0]))
+    hc, wc = (rh, rw) if crop_size is None else (int(crop_size[0]), int(crop_size[1]))
+    return Geometry((h, w), (rh, rw), (hc, wc), ((rh - hc) // 2, (rw - wc) // 2), q,
+                    None if spacing is None else tuple(float(v) for v in spacing))
+
+
+def prepare_patient(image, label, spacing=None, new_spacing=None, normalize=False, crop_size=None, normalize_2D=True, want_geometry=False):
     """`get_patient_data_for_testing` (cardiac_ACDC_dataset.py:204-232) on the device: load_volume, then ops.crop_or_pad to crop_size
     ([H', W'], None: the size stays), then ops.rescale_intensity per slice (normalize_2D).
-    -> {'image': float32 [n,1,H',W'], 'label': int64 [n,H',W']} on the device, what TestSegmentationNetwork.evaluate takes."""
+    -> {'image': float32 [n,1,H',W'], 'label': int64 [n,H',W']} on the device, what TestSegmentationNetwork.evaluate takes.
+    want_geometry adds 'geometry' (the Geometry of the trip) and 'native_label' (the label as uploaded, before resampling): what
+    TestSegmentationNetwork(native_grid=True) and restore_prediction need."""
+    if want_geometry:
+        keep = (label.dtype == np.uint8) if isinstance(label, np.ndarray) else (label.dtype == torch.uint8)
+        native = _upload(label, torch.uint8 if keep else torch.int64)                  # load_volume's upload, done once here
+        geo = geometry(*native.shape, spacing=spacing, new_spacing=new_spacing, crop_size=crop_size)
+        pack = prepare_patient(image, native, spacing=spacing, new_spacing=new_spacing, normalize=normalize, crop_size=crop_size,
+                               normalize_2D=normalize_2D)
+        pack.update(geometry=geo, native_label=native)
+        return pack
     image_d, label_d, _ = load_volume(image, label, spacing=spacing, new_spacing=new_spacing, normalize=normalize)
     if crop_size is not None:
         image_d, label_d = ops.crop_or_pad(image_d, crop_size, label=label_d)
@@ -59,6 +101,19 @@ def prepare_patient(image, label, spacing=None, new_spacing=None, normalize=Fals
     if normalize_2D:
         image_d = ops.rescale_intensity(image_d, 0.0, 1.0)
     return {"image": image_d, "label": label_d.long()}
+
+
+def restore_prediction(scores_or_labels, geometry, mode="logit", want_soft=False):
+    """A window-grid prediction back on the native grid of `geometry`, on the device: float32 [n,C,Hc,Wc] scores go through
+    ops.restore_scores (-> uint8 label [n,h,w], or (label, soft) with want_soft), uint8 [n,Hc,Wc] labels through ops.restore_labels."""
+    t = scores_or_labels
+    if t.dtype == torch.float32 and t.dim() == 4:
+        return ops.restore_scores(t, geometry, mode=mode, want_soft=want_soft)
+    if t.dtype == torch.uint8 and t.dim() == 3:
+        if want_soft:
+            raise ValueError("restore_prediction: a label volume has no soft prediction")
+        return ops.restore_labels(t, geometry)
+    raise ValueError(f"restore_prediction: expected float32 [n,C,Hc,Wc] scores or uint8 [n,Hc,Wc] labels, got {t.dtype} {tuple(t.shape)}")
 
 
 # ------------------------------------------------------------------------------------------------ host statements
@@ -165,3 +220,65 @@ def prepare_patient_host(image, label, spacing=None, new_spacing=None, normalize
         with np.errstate(all="ignore"):
             image = ((image - mn) / ((mx - mn) + F32(1e-20))) * F32(1.0) + F32(0.0)
     return {"image": np.ascontiguousarray(image[:, None], dtype=F32), "label": label.astype(np.int64)}
+
+
+def restore_coordinates_host(geometry):
+    """Per axis of the native grid: the window coordinates u = i * q - offset (fp64) and which native voxels are inside
+    (i * q < resampled - 0.5 and -0.5 <= u < window - 0.5 on both axes).  -> (u_y [h], u_x [w], inside [h,w])."""
+    out = []
+    for a in (0, 1):
+        c = np.arange(geometry.native_hw[a], dtype=np.float64) * np.float64(geometry.q[a])
+        u = c - np.float64(geometry.offset[a])
+        out.append((u, (c < geometry.resampled_hw[a] - 0.5) & (u >= -0.5) & (u < geometry.window_hw[a] - 0.5)))
+    return out[0][0], out[1][0], out[0][1][:, None] & out[1][1][None, :]
+
+
+def restore_values_host(scores, geometry, mode="logit"):
+    """The fp64 values ctl_restore_scores takes its arg-max over: scores float32 [n,C,Hc,Wc] -> (v float64 [n,C,h,w], inside [h,w]).
+    Tap value = the score (mode "logit") or the pixel's softmax exp(x - max) / sum (mode "prob", summed in ascending class order);
+    f = floor(u), t = u - f, taps clamp(f) and clamp(f + 1) separately; top = s00 (1 - tx) + s01 tx, bot likewise, v = top (1 - ty) +
+    bot ty.  Outside voxels hold 0 (logit) or (1, 0, ..., 0) (prob)."""
+    if mode not in ops.RESTORE_MODES:
+        raise ValueError(f"mode {mode!r}")
+    s = np.asarray(scores, dtype=F32).astype(np.float64)
+    n, c, hc, wc = s.shape
+    if (hc, wc) != tuple(geometry.window_hw):
+        raise ValueError(f"the scores' window {(hc, wc)} is not the geometry's {tuple(geometry.window_hw)}")
+    if mode == "prob":
+        e = np.exp(s - s.max(axis=1, keepdims=True))
+        z = e[:, 0]
+        for k in range(1, c):
+            z = z + e[:, k]
+        s = e / z[:, None]
+    uy, ux, inside = restore_coordinates_host(geometry)
+    fy, fx = np.floor(uy), np.floor(ux)
+    ty, tx = (uy - fy)[None, None, :, None], (ux - fx)[None, None, None, :]
+    y0, x0 = np.clip(fy.astype(np.int64), 0, hc - 1), np.clip(fx.astype(np.int64), 0, wc - 1)
+    y1, x1 = np.clip(fy.astype(np.int64) + 1, 0, hc - 1), np.clip(fx.astype(np.int64) + 1, 0, wc - 1)
+    top = s[:, :, y0][:, :, :, x0] * (1.0 - tx) + s[:, :, y0][:, :, :, x1] * tx
+    bot = s[:, :, y1][:, :, :, x0] * (1.0 - tx) + s[:, :, y1][:, :, :, x1] * tx
+    v = top * (1.0 - ty) + bot * ty
+    outside = np.zeros(c, dtype=np.float64)
+    if mode == "prob":
+        outside[0] = 1.0
+    return np.where(inside[None, None], v, outside[None, :, None, None]), inside
+
+
+def restore_scores_host(scores, geometry, mode="logit", want_soft=False):
+    """ops.restore_scores in numpy: label uint8 [n,h,w] = the lowest class with the largest fp64 value (0 outside), and with want_soft
+    the values rounded once to float32 [n,C,h,w]."""
+    v, inside = restore_values_host(scores, geometry, mode)
+    label = np.where(inside[None], np.argmax(v, axis=1), 0).astype(np.uint8)
+    return (label, v.astype(F32)) if want_soft else label
+
+
+def restore_labels_host(labels, geometry):
+    """ops.restore_labels in numpy: the window pixel at clamp(floor(u + 0.5), 0, size - 1) per axis, 0 outside."""
+    labels = np.asarray(labels)
+    n, hc, wc = labels.shape
+    if (hc, wc) != tuple(geometry.window_hw):
+        raise ValueError(f"the labels' window {(hc, wc)} is not the geometry's {tuple(geometry.window_hw)}")
+    uy, ux, inside = restore_coordinates_host(geometry)
+    yn = np.clip(np.floor(uy + 0.5).astype(np.int64), 0, hc - 1)
+    xn = np.clip(np.floor(ux + 0.5).astype(np.int64), 0, wc - 1)
+    return np.where(inside[None], labels[:, yn][:, :, xn], 0).astype(labels.dtype)

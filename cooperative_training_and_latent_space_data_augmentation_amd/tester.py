@@ -6,7 +6,10 @@ and the per-patient voxel counts are taken on the device, and one 2*n^2-word rea
 full-volume `.cpu().numpy()` copies per chunk.  The dataset only has to offer what the reference's tester reads from it:
 `patient_number`, `get_patient_data_for_testing(i, crop_size=)` -> {'image': [n,1,H,W], 'label': [n,H,W]}, `get_id()`,
 `get_voxel_spacing()` and `formalized_label_dict`.  The tensors of a pack may live on the host (uploaded once here) or already on the
-device (prepare.prepare_patient: no upload at all).  Writing nrrd files (SimpleITK) is outside the path and not offered."""
+device (prepare.prepare_patient: no upload at all).  Writing nrrd files (SimpleITK) is outside the path and not offered.
+With native_grid=True (a project addition, off by default) the logits are put back on the patient's native grid on the device
+(ops.restore_scores) and post-processing and the metrics run there; the packs then carry 'geometry' and 'native_label'
+(prepare.prepare_patient(want_geometry=True))."""
 import os
 
 import numpy as np
@@ -65,12 +68,14 @@ class TestSegmentationNetwork(object):
 
     def __init__(self, test_dataset, crop_size, segmentation_model, use_gpu=True, save_path="", summary_report_file_name="result.csv",
                  detailed_report_file_name="details.csv", patient_wise=True, metrics_list=("Dice", "HD"), foreground_only=False,
-                 save_soft_prediction=False, keep_results=True, post_process=None):
+                 save_soft_prediction=False, keep_results=True, post_process=None, native_grid=False, restore_mode="logit"):
         if not use_gpu:
             raise ValueError("this build has no CPU path")
         if post_process not in POST_PROCESS:
             raise ValueError("post_process {!r}: one of {}".format(post_process, sorted(POST_PROCESS, key=str)))
-        self.post_process = post_process
+        if restore_mode not in ops.RESTORE_MODES:
+            raise ValueError("restore_mode {!r}: one of {}".format(restore_mode, sorted(ops.RESTORE_MODES)))
+        self.post_process, self.native_grid, self.restore_mode = post_process, bool(native_grid), restore_mode
         self.test_dataset, self.crop_size, self.segmentation_model = test_dataset, crop_size, segmentation_model
         self.num_classes = segmentation_model.num_classes
         self.segmentation_metric = runningMySegmentationScore(n_classes=self.num_classes,
@@ -104,7 +109,11 @@ class TestSegmentationNetwork(object):
         of ops.surface_stats), so with keep_results=False and save_soft_prediction=False a patient is scored without any full-volume
         device-to-host copy.  That also holds with `post_process` ("largest_cc": the volume as one 3-D object, "largest_cc_2d": every slice
         on its own), which is applied on the device between the arg-max and the metric update; 'pred' of the result is then the
-        post-processed volume."""
+        post-processed volume.
+        native_grid: the pack carries 'geometry' (prepare.Geometry) and 'native_label' [n,h,w]; every chunk's logits are restored into one
+        native uint8 volume (ops.restore_scores, mode `restore_mode`: one more launch per chunk), `post_process` and the metric update
+        take that volume and the native label, and get_voxel_spacing() is then the native spacing.  The four keys of the result keep
+        their meaning (window grid); 'native_pred' and 'native_label' are added."""
         dev = torch.device("cuda", torch.cuda.current_device())
         image = data_tensor_pack["image"]
         if image.dim() == 5:                              # DataLoader(batch_size=1) adds a leading axis upstream
@@ -121,24 +130,42 @@ class TestSegmentationNetwork(object):
         label_d = label.to(dev, dtype=torch.int64, non_blocking=True)
         pid = self.test_dataset.get_id()
         total = image_d.size(0)
+        geo = native_d = native_label_d = None
+        if self.native_grid:
+            if "geometry" not in data_tensor_pack or "native_label" not in data_tensor_pack:
+                raise ValueError("native_grid=True needs a pack with 'geometry' and 'native_label' (prepare.prepare_patient(want_geometry=True))")
+            geo = data_tensor_pack["geometry"]
+            native_label_d = torch.as_tensor(data_tensor_pack["native_label"]).reshape(-1, *geo.native_hw).to(dev, dtype=torch.int64, non_blocking=True)
+            if native_label_d.size(0) != total:
+                raise ValueError("native_grid=True: 'native_label' has {} slices, the image {}".format(native_label_d.size(0), total))
+            native_d = torch.empty((total,) + tuple(geo.native_hw), dtype=torch.uint8, device=dev)
         pred_d = torch.empty((total, image_d.shape[-2], image_d.shape[-1]), dtype=torch.uint8, device=dev)
         soft = [] if (self.save_soft_prediction or self.keep_results) else None
         for lo in range(0, total, maximum_batch_size):
             hi = min(total, lo + maximum_batch_size)
             logit = self.segmentation_model.predict(input=image_d[lo:hi], softmax=False)
-            pred_d[lo:hi] = ops.argmax_c(logit)
+            if native_d is not None:
+                ops.restore_scores(logit, geo, mode=self.restore_mode, out=native_d[lo:hi])
+            if native_d is None or soft is not None:      # native grid: the window arg-max is only a kept result
+                pred_d[lo:hi] = ops.argmax_c(logit)
             if soft is not None:
                 soft.append(logit)
+        scored_d, scored_label_d = (pred_d, label_d) if native_d is None else (native_d, native_label_d)
         if self.post_process is not None:                 # largest component of every class (post_process.py:5-22), in place on the device
-            ops.keep_largest_components(pred_d, self.num_classes, per_slice=POST_PROCESS[self.post_process], out=pred_d)
+            per_slice = POST_PROCESS[self.post_process]
+            ops.keep_largest_components(scored_d, self.num_classes, per_slice=per_slice, out=scored_d)
+            if native_d is not None and soft is not None:
+                ops.keep_largest_components(pred_d, self.num_classes, per_slice=per_slice, out=pred_d)
         spacing = self.test_dataset.get_voxel_spacing() if hasattr(self.test_dataset, "get_voxel_spacing") else None
-        self.segmentation_metric.update(pid=pid, preds=pred_d, gts=label_d, voxel_spacing=spacing)
+        self.segmentation_metric.update(pid=pid, preds=scored_d, gts=scored_label_d, voxel_spacing=spacing)
         result = None
         if soft is not None:
             soft_np = torch.cat(soft, 0).float().cpu().numpy()
             # a pack prepared on the device (prepare.prepare_patient) is copied back here, and only here: keep_results asks for host arrays
             result = {"image": image.cpu().numpy().reshape(-1, image.shape[-2], image.shape[-1]), "label": label.cpu().numpy(),
                       "pred": pred_d.cpu().numpy(), "soft_pred": soft_np}
+            if native_d is not None:
+                result["native_pred"], result["native_label"] = native_d.cpu().numpy(), native_label_d.cpu().numpy()
             if total == 1:
                 result = {k: v[0] for k, v in result.items()}
         if self.save_soft_prediction and self.save_path:

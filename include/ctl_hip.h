@@ -615,6 +615,35 @@ int ctl_percentile_apply(const float* x, const float* table, int32_t segments, i
 int ctl_resample_inplane(const float* image, const void* label, int32_t label_bytes, int32_t n, int32_t h, int32_t w, int32_t new_h,
                          int32_t new_w, double r_h, double r_w, float* image_out, void* label_out, ctl_stream stream);
 
+/* ------------------------------------------------------------------------------------------------ native-grid restoration
+ * The inverse of the forward trip ctl_resample_inplane -> ctl_crop_or_pad: a prediction made on the network window is put back on the
+ * patient's native [n,h,w] grid.  Upstream has no counterpart (it scores on the prepared grid).  The geometry is passed as scalars:
+ *   h, w            native size                       res_h, res_w   size after the forward resampling (== h, w without one)
+ *   win_h, win_w    network window                    off_y, off_x   floor((res - win) / 2), negative when the window was padded (the
+ *   q_h, q_w        native spacing / new spacing                     number ctl_crop_or_pad uses)
+ *                   (fp64, from the host; exactly 1 when nothing was resampled)
+ * Per axis: native index i has resampled-grid coordinate c = i * q, ONE fp64 multiply that is never contracted into what follows (the
+ * corner-aligned convention of ctl_resample_inplane), and window coordinate u = c - off.  The voxel is INSIDE iff on both axes
+ * c < res - 0.5 and -0.5 <= u < win - 0.5 (half a voxel beyond the last sample centre, as the forward statement).
+ * ctl_restore_scores: scores float [n][win_h][win_w][c] (NHWC, what `predict` returns), 1 <= c <= 16.  Tap value s of a window pixel:
+ *   mode 0 "logit" the score as fp64; mode 1 "prob" exp(x_k - max_j x_j) / sum_j exp(x_j - max_j x_j) of that pixel in fp64 (sum in
+ *   ascending j).  Taps per axis: f = floor(u), t = u - f, i0 = clamp(f, 0, win - 1), i1 = clamp(f + 1, 0, win - 1), clamped SEPARATELY
+ *   (u in [-0.5, 0) reads pixel 0 twice).  Per class, in fp64, every operation rounded on its own, in the order of ctl_resample_inplane:
+ *   top = s00 (1 - tx) + s01 tx, bot = s10 (1 - tx) + s11 tx, v = top (1 - ty) + bot ty.  label (uint8 [n][h][w]) = the lowest class
+ *   index with maximal v, decided on the fp64 values by a strict > scan as ctl_argmax_c does.  soft (float [n][c][h][w], plain contiguous
+ *   planes, may be NULL) = v rounded once.  Outside voxels: label 0; soft all 0 in mode 0, (1, 0, ..., 0) in mode 1.  With q == 1 on both
+ *   axes t is exactly 0, so inside the window mode 0 returns the bits of ctl_argmax_c and of the scores.  One launch, no workspace, no
+ *   atomics, no readback; for c == 4 and a 16-byte aligned `scores` a tap is one 16-byte load.
+ * ctl_restore_labels: labels uint8 [n][win_h][win_w] -> out uint8 [n][h][w]: the element at clamp(floor(u + 0.5), 0, win - 1) per axis
+ *   for inside voxels, 0 outside.  One launch.
+ * Every element of every output is written.  Null pointers, non-positive sizes, c outside 1..16, a non-finite or non-positive q, an
+ * unknown mode and a tensor at or past the 2 GiB limit are refused with CTL_EINVAL before any launch. */
+int ctl_restore_scores(const float* scores, int32_t n, int32_t c, int32_t win_h, int32_t win_w, int32_t h, int32_t w, int32_t res_h,
+                       int32_t res_w, int32_t off_y, int32_t off_x, double q_h, double q_w, int32_t mode, uint8_t* label, float* soft,
+                       ctl_stream stream);
+int ctl_restore_labels(const uint8_t* labels, int32_t n, int32_t win_h, int32_t win_w, int32_t h, int32_t w, int32_t res_h, int32_t res_w,
+                       int32_t off_y, int32_t off_x, double q_h, double q_w, uint8_t* out, ctl_stream stream);
+
 /* ------------------------------------------------------------------------------------------------ MR artefact corruption (ACDC-C)
  * The four corruptions of medseg/dataset_loader/generate_artefacted_data.py:56-83 (TorchIO's RandomBiasField, RandomSpike, RandomGhosting,
  * RandomMotion) for one volume x [d][h][w] of floats, axes 0, 1, 2; N = d h w.  The host draws the random parameters and passes them by

@@ -29,6 +29,7 @@ CONV_DTYPE = np.dtype([
     ("out_sy", "<i4"), ("out_sx", "<i4"), ("nsub", "<i4"), ("out_sub", "<i4"), ("groups", "<i4"), ("dt", "<i4")])
 DT_BF16, DT_X16, DT_Y16, DT_RES16, DT_X3 = 1, 2, 4, 8, 16
 PACK_X3 = 16                         # or-ed into the mode word of a pack record (CTL_PACK_X3)
+LOSS_WCE, LOSS_FOCAL, LOSS_DICE, LOSS_FG_DICE = 0, 1, 2, 3      # CTL_LOSS_* kinds of ctl_seg_loss_fwd / ctl_seg_loss_bwd
 OP_DTYPE = np.dtype([("kind", "<i4"), ("i", "<i4", (27,)), ("f", "<f4", (4,)), ("slot", "<i4", (OP_MAX_T,)),
                      ("off", "<i8", (OP_MAX_T,)), ("l", "<i8", (4,))], align=True)
 
@@ -60,7 +61,8 @@ class _Lib:
                      "ctl_rescale_intensity_ws_floats", "ctl_sizeof_op", "ctl_sizeof_conv", "ctl_latent_mask_fused_ws_floats", "ctl_conv_wpack_floats_x3",
                      "ctl_surface_stats_ws_bytes", "ctl_surface_map_ws_bytes", "ctl_cc_ws_bytes", "ctl_aug_ws_bytes", "ctl_aug_warp_ws_bytes",
                      "ctl_surface_quantiles_ws_bytes",
-                     "ctl_aug_spline_ws_bytes", "ctl_aug_warp_cubic_ws_bytes", "ctl_aug_bias_ws_bytes", "ctl_order_stats_ws_bytes", "ctl_corrupt_spike_ws_bytes"):
+                     "ctl_aug_spline_ws_bytes", "ctl_aug_warp_cubic_ws_bytes", "ctl_aug_bias_ws_bytes", "ctl_order_stats_ws_bytes", "ctl_corrupt_spike_ws_bytes",
+                     "ctl_seg_loss_ws_doubles"):
             getattr(lib, name).restype = C.c_size_t
         p, i32, i64, f32, u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64
         sig = {
@@ -148,6 +150,9 @@ class _Lib:
             "ctl_corrupt_rigid3d": [p, i32, i32, i32, p, i32, p, p], "ctl_axis_operator": [p, p, i32, i32, i32, i32, i32, p, p, p],
             "ctl_slice_foreground": [p, p, i32, i64, p, p],
             "ctl_batch_gather": [p, p, p, i32, i64, p, i32, p, i32, i32, p, p, i32, i32, p, p, p],
+            "ctl_seg_loss_blocks": [i32, i64], "ctl_seg_loss_ws_doubles": [i32, i32, i64, i32],
+            "ctl_seg_loss_fwd": [i32, p, p, p, f32, i32, i64, i32, p, p, p],
+            "ctl_seg_loss_bwd": [i32, p, p, p, f32, p, p, i32, i64, i32, p, p],
         }
         for name, args in sig.items():
             getattr(lib, name).argtypes = args
@@ -185,7 +190,8 @@ EXPORTED = ["ctl_version", "ctl_last_error", "ctl_conv_wpack_floats", "ctl_conv_
             "ctl_aug_bias_ws_bytes", "ctl_aug_bias", "ctl_aug_coarse_field", "ctl_order_stats_ws_bytes", "ctl_order_stats",
             "ctl_percentile_apply", "ctl_resample_inplane", "ctl_corrupt_bias", "ctl_corrupt_spike_ws_bytes", "ctl_corrupt_spike",
             "ctl_corrupt_rigid3d", "ctl_axis_operator", "ctl_slice_foreground", "ctl_batch_gather", "ctl_surface_quantiles_ws_bytes",
-            "ctl_surface_quantiles", "ctl_restore_scores", "ctl_restore_labels"]
+            "ctl_surface_quantiles", "ctl_restore_scores", "ctl_restore_labels", "ctl_seg_loss_blocks", "ctl_seg_loss_ws_doubles",
+            "ctl_seg_loss_fwd", "ctl_seg_loss_bwd"]
 
 
 def prof_start(kernel_filter: str = "", every: int = 1) -> None:

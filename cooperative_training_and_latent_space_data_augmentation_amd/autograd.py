@@ -147,6 +147,43 @@ class _CrossEntropy2D(torch.autograd.Function):
         return ops.ce2d_bwd(logit, label, g.float().contiguous()), None
 
 
+class _PointwiseSegLoss(torch.autograd.Function):
+    """'weighted cross entropy' and 'focal' (custom_loss.py:720-740, :222-255): a pixel's loss term depends on its own row only."""
+
+    @staticmethod
+    def forward(ctx, logit, label, kind, class_weights, gamma):
+        logit = _nhwc(logit)
+        label = label.long().contiguous()
+        ctx.save_for_backward(logit, label)
+        ctx.args = (kind, class_weights, gamma)
+        return ops.seg_loss_fwd(logit, label, kind, class_weights, gamma)[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        logit, label = ctx.saved_tensors
+        kind, class_weights, gamma = ctx.args
+        return ops.seg_loss_bwd(logit, label, kind, g.float().contiguous(), None, class_weights, gamma), None, None, None, None
+
+
+class _DiceSegLoss(torch.autograd.Function):
+    """'dice' / 'weighted dice' / 'foreground dice' (custom_loss.py:356-396, :434-471): the forward leaves the per-(sample, class)
+    coefficient table of the gradient in its scratch, the backward streams once over the logits with it."""
+
+    @staticmethod
+    def forward(ctx, logit, label, kind):
+        logit = _nhwc(logit)
+        label = label.long().contiguous()
+        loss, ws = ops.seg_loss_fwd(logit, label, kind)
+        ctx.save_for_backward(logit, label, ws)
+        ctx.kind = kind
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logit, label, ws = ctx.saved_tensors
+        return ops.seg_loss_bwd(logit, label, ctx.kind, g.float().contiguous(), ws), None, None
+
+
 class _ScaledMSE(torch.autograd.Function):
     """scale * mean((a-b)^2)"""
 
@@ -182,6 +219,19 @@ class _SoftmaxT(torch.autograd.Function):
 def cross_entropy_2D(logit, label):
     ops.require_gpu(logit, label)
     return _CrossEntropy2D.apply(logit, label)
+
+
+def segmentation_loss(logit, label, kind, class_weights=None, gamma=2.0):
+    """One of the fused segmentation losses of ops.LOSS_KINDS on logits [B,C,H,W] and a label map [B,H,W].  `class_weights`: a host
+    sequence of C numbers, used by 'weighted cross entropy' only ('weighted dice' ignores it, as upstream does); `gamma`: 'focal' only."""
+    if kind not in ops.LOSS_KINDS:
+        raise NotImplementedError(f"segmentation loss {kind!r} (one of {', '.join(ops.LOSS_KINDS)})")
+    ops.require_gpu(logit, label)
+    if ops.LOSS_KINDS[kind] in (ops._ffi.LOSS_DICE, ops._ffi.LOSS_FG_DICE):
+        return _DiceSegLoss.apply(logit, label, kind)
+    if class_weights is not None:
+        class_weights = tuple(float(v) for v in class_weights)
+    return _PointwiseSegLoss.apply(logit, label, kind, class_weights, float(gamma))
 
 
 def scaled_mse(a, b, scale=1.0):

@@ -1,0 +1,339 @@
+// Segmentation losses next to ce2d (ctl_elem.hip): class-weighted cross-entropy, focal, soft Dice and foreground soft Dice of fp32 NHWC
+// logits against an int64 label map (medseg/models/custom_loss.py: cross_entropy_2D :706-740, FocalLoss :222-255, SoftDiceLoss :356-396,
+// SelectiveSoftDiceLoss :434-471).  HBM-bound streaming kernels: a pixel's channel row lives in registers, its softmax is recomputed by
+// the backward instead of being stored.  Sums are two-stage and ordered (per-block fp64 partials, one finalize block): no float atomics,
+// the same bits on every call.  Nothing is read back; no launch argument changes from step to step.
+//
+// A label outside 0..c-1 is no class: one-hot 0 for every k, weight 0.  Labels are only ever compared with a class index.
+#include <cmath>
+#include "ctl_common.h"
+
+#define EB 256               // threads per block
+#define MAXC 16
+#define LOSS_MAX_STREAM_BLOCKS 2048
+#define S_ (hipStream_t) stream
+
+struct ctl_w16 { float v[MAXC]; };      // normalised class weights, a launch argument (constant from step to step)
+
+// Channel rows.  CT = 4: one 16-byte load / store per pixel; CT = 0: runtime channel count, the loops still unrolled over MAXC with the
+// tail switched off (everything stays in registers).  The arithmetic and its order are the same in both; contraction is off in every
+// function below so that neither form turns a product and a sum into an fma the other one keeps apart.
+template <int CT> __device__ __forceinline__ void lrow_load(const float* __restrict__ base, int64_t i, int c, float* v) {
+    if (CT == 4) {
+        const f32x4 t = *reinterpret_cast<const f32x4*>(base + i * 4);
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < MAXC; ++k) if (k < c) v[k] = base[i * c + k];
+    }
+}
+template <int CT> __device__ __forceinline__ void lrow_store(float* __restrict__ base, int64_t i, int c, const float* v) {
+    if (CT == 4) {
+        *reinterpret_cast<f32x4*>(base + i * 4) = f32x4{v[0], v[1], v[2], v[3]};
+    } else {
+#pragma unroll
+        for (int k = 0; k < MAXC; ++k) if (k < c) base[i * c + k] = v[k];
+    }
+}
+// v <- exp(v - max v); returns the row maximum, `s` = the sum of the exponentials
+template <int CT> __device__ __forceinline__ float lrow_exp(float* v, int c, float& s) {
+#pragma clang fp contract(off)
+    constexpr int NC = CT ? CT : MAXC;
+    float m = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < NC; ++k) if (k < c) m = fmaxf(m, v[k]);
+    s = 0.f;
+#pragma unroll
+    for (int k = 0; k < NC; ++k) if (k < c) { v[k] = expf(v[k] - m); s += v[k]; }
+    return m;
+}
+__device__ __forceinline__ double loss_block_sum(double v, double* sm) {      // valid on thread 0; fixed order
+    v = wave_sum_double(v);
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double r = 0.0;
+    if (threadIdx.x == 0) for (int i = 0; i < EB / 64; ++i) r += sm[i];
+    return r;
+}
+
+// ------------------------------------------------------------------------------------------------ point-wise kinds
+// pixel term of the loss and the factor f of its gradient f * (p_k - t_k):
+//   weighted cross-entropy: -w[y] log p_y,           f = w[y]
+//   focal:                  -(1 - p_y)^gamma log p_y, f = (1 - p_y)^gamma    (upstream detaches p_y, custom_loss.py:243)
+// 1 - p_y is formed as (sum of the other exponentials) / s: no cancellation where p_y is close to 1.
+template <int CT>
+__device__ __forceinline__ float pw_factor(int kind, const float* e, float s, int c, int64_t l, const ctl_w16& w, float gamma) {
+#pragma clang fp contract(off)
+    constexpr int NC = CT ? CT : MAXC;
+    if (kind == CTL_LOSS_WCE) {
+        float wl = 0.f;
+#pragma unroll
+        for (int k = 0; k < NC; ++k) if (k < c) wl = (l == (int64_t)k) ? w.v[k] : wl;
+        return wl;
+    }
+    float so = 0.f;
+    bool valid = false;
+#pragma unroll
+    for (int k = 0; k < NC; ++k) if (k < c) { const bool hit = l == (int64_t)k; so += hit ? 0.f : e[k]; valid = valid || hit; }
+    return valid ? powf(so / s, gamma) : 0.f;
+}
+template <int CT>
+__global__ __launch_bounds__(EB) void seg_pw_partial_kernel(const float* __restrict__ logit, const int64_t* __restrict__ label,
+                                                             int64_t pixels, int c_rt, int kind, ctl_w16 w, float gamma,
+                                                             double* __restrict__ partial) {
+#pragma clang fp contract(off)
+    constexpr int NC = CT ? CT : MAXC;
+    __shared__ double sm[EB / 64];
+    const int c = CT ? CT : c_rt;
+    const int64_t stride = (int64_t)gridDim.x * EB;
+    double acc = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x; i < pixels; i += stride) {
+        float v[NC], x[NC];
+        lrow_load<CT>(logit, i, c, v);
+#pragma unroll
+        for (int k = 0; k < NC; ++k) if (k < c) x[k] = v[k];
+        float s;
+        const float m = lrow_exp<CT>(v, c, s);
+        const int64_t l = label[i];
+        float xl = m;      // (no class: log p = -log s, times the factor 0)
+#pragma unroll
+        for (int k = 0; k < NC; ++k) if (k < c) xl = (l == (int64_t)k) ? x[k] : xl;
+        const float f = pw_factor<CT>(kind, v, s, c, l, w, gamma);
+        acc += (double)(-(f * (xl - m - logf(s))));
+    }
+    acc = loss_block_sum(acc, sm);
+    if (threadIdx.x == 0) partial[blockIdx.x] = acc;
+}
+__global__ __launch_bounds__(EB) void seg_pw_finalize_kernel(const double* __restrict__ partial, int blocks, double mul,
+                                                              float* __restrict__ out) {
+    __shared__ double sm[EB / 64];
+    double s = 0.0;
+    for (int b = threadIdx.x; b < blocks; b += EB) s += partial[b];
+    s = loss_block_sum(s, sm);
+    if (threadIdx.x == 0) out[0] = (float)(s * mul);
+}
+
+// ------------------------------------------------------------------------------------------------ Dice kinds, forward
+// pass 1: grid (blocks of a sample, sample); partial[b][block][k][3] = sum p_k, sum p_k t_k, count of y == k over the block's pixels
+template <int CT>
+__global__ __launch_bounds__(EB) void dice_partial_kernel(const float* __restrict__ logit, const int64_t* __restrict__ label, int64_t hw,
+                                                           int c_rt, double* __restrict__ partial) {
+#pragma clang fp contract(off)
+    constexpr int NC = CT ? CT : MAXC;
+    __shared__ double sm[EB / 64][3 * MAXC];
+    const int c = CT ? CT : c_rt;
+    const int64_t b = blockIdx.y;
+    const float* __restrict__ x = logit + b * hw * c;
+    const int64_t* __restrict__ y = label + b * hw;
+    double sp[NC], spt[NC];
+    int cnt[NC];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) { sp[k] = 0.0; spt[k] = 0.0; cnt[k] = 0; }
+    const int64_t stride = (int64_t)gridDim.x * EB;
+    for (int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x; i < hw; i += stride) {
+        float v[NC];
+        lrow_load<CT>(x, i, c, v);
+        float s;
+        lrow_exp<CT>(v, c, s);
+        const float r = 1.f / s;
+        const int64_t l = y[i];
+#pragma unroll
+        for (int k = 0; k < NC; ++k) if (k < c) {
+            const double p = (double)(v[k] * r);
+            const bool hit = l == (int64_t)k;
+            sp[k] += p;
+            spt[k] += hit ? p : 0.0;
+            cnt[k] += hit ? 1 : 0;
+        }
+    }
+    const int wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < NC; ++k) if (k < c) {
+        const double a = wave_sum_double(sp[k]), t = wave_sum_double(spt[k]), n = wave_sum_double((double)cnt[k]);
+        if ((threadIdx.x & 63) == 0) { sm[wv][3 * k] = a; sm[wv][3 * k + 1] = t; sm[wv][3 * k + 2] = n; }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < 3 * c) {
+        double r = 0.0;
+        for (int i = 0; i < EB / 64; ++i) r += sm[i][threadIdx.x];
+        partial[((b * gridDim.x + blockIdx.x) * c) * 3 + threadIdx.x] = r;
+    }
+}
+// pass 2, one block: a group of 16 lanes sums the `nb` block rows of one (sample, class) in a fixed order, the group's first lane forms
+// the Dice term and the two coefficients of the backward:  g_k = dL/dp_k = coef[b][k][0] * t_k + coef[b][k][1]
+//   term = num / U,  U = sum p + count + s,  num = 2 (sum p t + s)   ['dice']   or   2 sum p t + s   ['foreground dice', classes >= 1]
+//   loss = 1 - (sum of the terms) / div;   coef[0] = -(2 / U) / div,  coef[1] = (num / U^2) / div;   0 for a class that is not selected
+__global__ __launch_bounds__(EB) void dice_finalize_kernel(const double* __restrict__ partial, int items, int nb, int c, int fg, double div,
+                                                            double* __restrict__ coef, float* __restrict__ loss) {
+#pragma clang fp contract(off)
+    __shared__ double sm[EB / 64];
+    const double smooth = 0.01;
+    const int lane = threadIdx.x & 15, grp = threadIdx.x >> 4;
+    double acc = 0.0;
+    for (int base = 0; base < items; base += EB / 16) {
+        const int it = base + grp;
+        const bool ok = it < items;
+        const int64_t b = ok ? it / c : 0;
+        const int k = ok ? it % c : 0;
+        double sp = 0.0, spt = 0.0, n = 0.0;
+        if (ok) {
+            for (int j = lane; j < nb; j += 16) {
+                const double* __restrict__ q = partial + ((b * nb + j) * c + k) * 3;
+                sp += q[0]; spt += q[1]; n += q[2];
+            }
+        }
+        for (int o = 8; o > 0; o >>= 1) { sp += __shfl_xor(sp, o); spt += __shfl_xor(spt, o); n += __shfl_xor(n, o); }
+        if (ok && lane == 0) {
+            const bool sel = !fg || k >= 1;
+            const double U = sp + n + smooth;
+            const double num = fg ? 2.0 * spt + smooth : 2.0 * (spt + smooth);
+            coef[(int64_t)it * 2] = sel ? -(2.0 / U) / div : 0.0;
+            coef[(int64_t)it * 2 + 1] = sel ? (num / (U * U)) / div : 0.0;
+            acc += sel ? num / U : 0.0;
+        }
+    }
+    acc = loss_block_sum(acc, sm);
+    if (threadIdx.x == 0) loss[0] = (float)(1.0 - acc / div);
+}
+
+// ------------------------------------------------------------------------------------------------ backward of every kind
+// grid (blocks of a sample, sample).  point-wise kinds: dlogit_k = gout / pixels * f * (p_k - t_k).  Dice kinds: with g_k from the
+// coefficient table, dlogit_j = gout * p_j * sum_k p_k (g_j - g_k), formed in fp64 (it cancels where the row is confident).
+template <int CT>
+__global__ __launch_bounds__(EB) void seg_loss_bwd_kernel(const float* __restrict__ logit, const int64_t* __restrict__ label,
+                                                           const float* __restrict__ gout, const double* __restrict__ coef, int64_t hw,
+                                                           int c_rt, int kind, ctl_w16 w, float gamma, float pixels_f,
+                                                           float* __restrict__ dlogit) {
+#pragma clang fp contract(off)
+    constexpr int NC = CT ? CT : MAXC;
+    const int c = CT ? CT : c_rt;
+    const int64_t b = blockIdx.y;
+    const float* __restrict__ x = logit + b * hw * c;
+    const int64_t* __restrict__ y = label + b * hw;
+    float* __restrict__ dx = dlogit + b * hw * c;
+    const bool dice = kind == CTL_LOSS_DICE || kind == CTL_LOSS_FG_DICE;
+    const float go = gout[0];
+    const float gs = go / pixels_f;
+    double ca[NC], cb[NC];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+        const bool on = dice && k < c;
+        ca[k] = on ? coef[(b * c + k) * 2] : 0.0;
+        cb[k] = on ? coef[(b * c + k) * 2 + 1] : 0.0;
+    }
+    const int64_t stride = (int64_t)gridDim.x * EB;
+    for (int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x; i < hw; i += stride) {
+        float v[NC];
+        lrow_load<CT>(x, i, c, v);
+        float s;
+        lrow_exp<CT>(v, c, s);
+        const float r = 1.f / s;
+        const int64_t l = y[i];
+        if (dice) {
+            // sum_k p_k (g_j - g_k) = g_j S - dot with S the sum of the ROUNDED p_k (1 only up to 1e-7): every p_k enters with its own
+            // relative accuracy, so a confident row's small gradient keeps its relative accuracy too
+            double g[NC], dot = 0.0, S = 0.0;
+#pragma unroll
+            for (int k = 0; k < NC; ++k) if (k < c) {
+                v[k] = v[k] * r;
+                g[k] = (l == (int64_t)k) ? ca[k] + cb[k] : cb[k];
+                dot += (double)v[k] * g[k];
+                S += (double)v[k];
+            }
+#pragma unroll
+            for (int k = 0; k < NC; ++k) if (k < c) v[k] = (float)((double)go * ((double)v[k] * (g[k] * S - dot)));
+        } else {
+            const float gf = gs * pw_factor<CT>(kind, v, s, c, l, w, gamma);
+            float so = 0.f;      // p_y - 1 = -(sum of the other exponentials) / s: no cancellation where p_y is close to 1
+#pragma unroll
+            for (int k = 0; k < NC; ++k) if (k < c) so += (l == (int64_t)k) ? 0.f : v[k];
+#pragma unroll
+            for (int k = 0; k < NC; ++k) if (k < c) v[k] = gf * ((l == (int64_t)k) ? -(so * r) : v[k] * r);
+        }
+        lrow_store<CT>(dx, i, c, v);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ launchers
+static inline bool loss_vec4(int c, const void* a, const void* b = nullptr) {
+    return c == 4 && (((uintptr_t)a | (uintptr_t)b) & 15) == 0;      // 16-byte rows need 16-byte aligned tensors
+}
+static inline bool kind_is_dice(int kind) { return kind == CTL_LOSS_DICE || kind == CTL_LOSS_FG_DICE; }
+// blocks per sample of the two-dimensional grids: at most `cap` blocks over all samples (one per sample where b exceeds the cap)
+static inline int sample_blocks(int64_t b, int64_t hw, int cap) {
+    int64_t nb = ctl_cdiv64(hw, EB), lim = cap / b;
+    if (lim < 1) lim = 1;
+    return (int)(nb < lim ? nb : lim);
+}
+// the checks every entry shares; the message names the entry
+static int seg_loss_check(const char* who, int kind, int64_t b, int64_t hw, int c) {
+    CTL_REQUIRE(kind >= CTL_LOSS_WCE && kind <= CTL_LOSS_FG_DICE, "%s: unknown loss kind %d", who, kind);
+    CTL_REQUIRE(b > 0 && hw > 0, "%s: sizes must be positive (batch %lld, pixels per sample %lld)", who, (long long)b, (long long)hw);
+    CTL_REQUIRE(c >= 1 && c <= MAXC, "%s: %d classes (1 .. %d)", who, c, MAXC);
+    CTL_REQUIRE(kind != CTL_LOSS_FG_DICE || c >= 2, "%s: foreground dice needs at least 2 classes (got %d)", who, c);
+    CTL_REQUIRE(b <= 65535, "%s: batch %lld (at most 65535 samples)", who, (long long)b);
+    const int64_t row_bytes = c * 4 > 8 ? c * 4 : 8;      // logits: c floats per pixel, labels: 8 bytes per pixel
+    CTL_REQUIRE(hw < ((int64_t)1 << 31) && b * hw < ((int64_t)1 << 31) / row_bytes,
+                "%s: %lld x %lld pixels of %d classes reach the 2 GiB tensor limit", who, (long long)b, (long long)hw, c);
+    return CTL_OK;
+}
+// w' = w / sum(w) * c in fp64, handed to the kernels as fp32 (custom_loss.py:733-734); NULL = upstream's uniform 1/c, i.e. all ones
+static int seg_loss_weights(const char* who, int kind, int c, const double* class_weights, float gamma, ctl_w16* w) {
+    for (int k = 0; k < MAXC; ++k) w->v[k] = k < c ? 1.f : 0.f;
+    if (kind == CTL_LOSS_WCE && class_weights) {
+        double sum = 0.0;
+        for (int k = 0; k < c; ++k) sum += class_weights[k];
+        CTL_REQUIRE(std::isfinite(sum) && sum > 0.0, "%s: the class weights sum to %g (a finite, positive sum is needed)", who, sum);
+        for (int k = 0; k < c; ++k) w->v[k] = (float)(class_weights[k] / sum * (double)c);
+    }
+    CTL_REQUIRE(kind != CTL_LOSS_FOCAL || (std::isfinite(gamma) && gamma >= 0.f), "%s: focal gamma %g (finite, >= 0)", who, (double)gamma);
+    return CTL_OK;
+}
+
+extern "C" int32_t ctl_seg_loss_blocks(int32_t b, int64_t hw) {
+    return (b > 0 && hw > 0) ? sample_blocks(b, hw, CTL_RED_BLOCKS) : 0;
+}
+extern "C" size_t ctl_seg_loss_ws_doubles(int32_t kind, int32_t b, int64_t hw, int32_t c) {
+    if (seg_loss_check("seg_loss_ws_doubles", kind, b, hw, c) != CTL_OK) return 0;
+    if (!kind_is_dice(kind)) return CTL_RED_BLOCKS;
+    return (size_t)b * sample_blocks(b, hw, CTL_RED_BLOCKS) * c * 3 + (size_t)b * c * 2;
+}
+extern "C" int ctl_seg_loss_fwd(int32_t kind, const float* logit, const int64_t* label, const double* class_weights, float gamma,
+                                int32_t b, int64_t hw, int32_t c, double* ws, float* loss, ctl_stream stream) {
+    CTL_REQUIRE(logit && label && ws && loss, "seg_loss_fwd: null pointer");
+    if (int rc = seg_loss_check("seg_loss_fwd", kind, b, hw, c)) return rc;
+    ctl_w16 w;
+    if (int rc = seg_loss_weights("seg_loss_fwd", kind, c, class_weights, gamma, &w)) return rc;
+    const bool v4 = loss_vec4(c, logit);
+    if (kind_is_dice(kind)) {
+        const int nb = sample_blocks(b, hw, CTL_RED_BLOCKS);
+        double* coef = ws + (size_t)b * nb * c * 3;
+        const int fg = kind == CTL_LOSS_FG_DICE;
+        if (v4) dice_partial_kernel<4><<<dim3(nb, b), dim3(EB), 0, S_>>>(logit, label, hw, c, ws);
+        else dice_partial_kernel<0><<<dim3(nb, b), dim3(EB), 0, S_>>>(logit, label, hw, c, ws);
+        dice_finalize_kernel<<<dim3(1), dim3(EB), 0, S_>>>(ws, b * c, nb, c, fg, (double)b * (double)(fg ? c - 1 : c), coef, loss);
+    } else {
+        const int64_t pixels = (int64_t)b * hw;
+        if (v4) seg_pw_partial_kernel<4><<<dim3(CTL_RED_BLOCKS), dim3(EB), 0, S_>>>(logit, label, pixels, c, kind, w, gamma, ws);
+        else seg_pw_partial_kernel<0><<<dim3(CTL_RED_BLOCKS), dim3(EB), 0, S_>>>(logit, label, pixels, c, kind, w, gamma, ws);
+        seg_pw_finalize_kernel<<<dim3(1), dim3(EB), 0, S_>>>(ws, CTL_RED_BLOCKS, 1.0 / (double)pixels, loss);
+    }
+    ctl_count_launches(1);      // partial + finalize
+    CTL_LAUNCH_CHECK("seg_loss_fwd");
+    return CTL_OK;
+}
+extern "C" int ctl_seg_loss_bwd(int32_t kind, const float* logit, const int64_t* label, const double* class_weights, float gamma,
+                                const float* gout, const double* ws, int32_t b, int64_t hw, int32_t c, float* dlogit, ctl_stream stream) {
+    CTL_REQUIRE(logit && label && gout && dlogit, "seg_loss_bwd: null pointer");
+    if (int rc = seg_loss_check("seg_loss_bwd", kind, b, hw, c)) return rc;
+    CTL_REQUIRE(!kind_is_dice(kind) || ws, "seg_loss_bwd: null pointer (the Dice kinds read the coefficient table of the forward from ws)");
+    ctl_w16 w;
+    if (int rc = seg_loss_weights("seg_loss_bwd", kind, c, class_weights, gamma, &w)) return rc;
+    const double* coef = kind_is_dice(kind) ? ws + (size_t)b * sample_blocks(b, hw, CTL_RED_BLOCKS) * c * 3 : nullptr;
+    const dim3 grid(sample_blocks(b, hw, LOSS_MAX_STREAM_BLOCKS), b);
+    const float pixels_f = (float)((int64_t)b * hw);
+    if (loss_vec4(c, logit, dlogit)) seg_loss_bwd_kernel<4><<<grid, dim3(EB), 0, S_>>>(logit, label, gout, coef, hw, c, kind, w, gamma, pixels_f, dlogit);
+    else seg_loss_bwd_kernel<0><<<grid, dim3(EB), 0, S_>>>(logit, label, gout, coef, hw, c, kind, w, gamma, pixels_f, dlogit);
+    CTL_LAUNCH_CHECK("seg_loss_bwd");
+    return CTL_OK;
+}

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .autograd import cross_entropy_2D as _ce2d, scaled_mse as _mse
+from .autograd import cross_entropy_2D as _ce2d, scaled_mse as _mse, segmentation_loss as _seg_loss
 
 
 def set_grad(module, requires_grad=False):
@@ -41,8 +41,10 @@ def make_one_hot(y, num_classes=4):
 
 
 def cross_entropy_2D(input, target, weight=None, size_average=True):
-    if weight is not None or not size_average or target.dim() != 3:
-        raise NotImplementedError("only the un-weighted, averaged, label-map form is on the hot path")
+    if not size_average or target.dim() != 3:
+        raise NotImplementedError("only the averaged, label-map form is on the hot path")
+    if weight is not None:      # custom_loss.py:732-736; the weights are launch constants: keep them on the host (a device tensor is read back)
+        return _seg_loss(input, target, "weighted cross entropy", weight.tolist() if hasattr(weight, "tolist") else weight)
     return _ce2d(input, target)
 
 

@@ -215,6 +215,48 @@ def ce2d_bwd(logit, label, gout):
     return d
 
 
+# loss names of basic_loss_fn (custom_loss.py:8-40) -> CTL_LOSS_* kind; upstream's 'weighted dice' never uses its weights: it is 'dice'
+LOSS_KINDS = {"weighted cross entropy": _ffi.LOSS_WCE, "focal": _ffi.LOSS_FOCAL, "dice": _ffi.LOSS_DICE, "weighted dice": _ffi.LOSS_DICE,
+              "foreground dice": _ffi.LOSS_FG_DICE}
+
+
+def _loss_args(logit, label, kind, class_weights):
+    if kind not in LOSS_KINDS:
+        raise NotImplementedError(f"segmentation loss {kind!r} (one of {', '.join(LOSS_KINDS)})")
+    require_gpu(logit, label)
+    if logit.dim() != 4 or logit.dtype != torch.float32 or label.dtype != torch.int64 or \
+            tuple(label.shape) != (logit.shape[0], logit.shape[2], logit.shape[3]):
+        raise ValueError("segmentation loss: expected fp32 logits [B,C,H,W] and an int64 label map [B,H,W]")
+    n, c, h, w = logit.shape
+    if not (logit.permute(0, 2, 3, 1).is_contiguous() and label.is_contiguous()):
+        raise ValueError("segmentation loss: the logits must be NHWC in memory (channels_last) and the label map contiguous")
+    wts = None
+    if class_weights is not None and LOSS_KINDS[kind] == _ffi.LOSS_WCE:      # a host sequence: the library normalises it in fp64
+        vals = [float(v) for v in class_weights]
+        if len(vals) != c:
+            raise ValueError(f"each class must have a weight: expected {c} weights, got {len(vals)}")
+        wts = (C.c_double * c)(*vals)
+    return LOSS_KINDS[kind], n, h * w, c, wts
+
+
+def seg_loss_fwd(logit, label, kind, class_weights=None, gamma=2.0):
+    """(loss, ws): `ws` holds the block sums and, for the Dice kinds, the coefficient table seg_loss_bwd reads."""
+    k, n, hw, c, wts = _loss_args(logit, label, kind, class_weights)
+    ws = torch.empty(max(1, lib.ctl_seg_loss_ws_doubles(k, n, hw, c)), dtype=torch.float64, device=logit.device)
+    loss = torch.empty((), dtype=torch.float32, device=logit.device)
+    check(lib.ctl_seg_loss_fwd(k, ptr(logit), ptr(label), wts, gamma, n, hw, c, ptr(ws), ptr(loss), stream_ptr()), "ctl_seg_loss_fwd")
+    return loss, ws
+
+
+def seg_loss_bwd(logit, label, kind, gout, ws=None, class_weights=None, gamma=2.0):
+    """gout: 0-d fp32 device tensor; ws: what seg_loss_fwd returned (the Dice kinds need it)."""
+    k, n, hw, c, wts = _loss_args(logit, label, kind, class_weights)
+    require_gpu(gout, ws)
+    d = torch.empty_like(logit)
+    check(lib.ctl_seg_loss_bwd(k, ptr(logit), ptr(label), wts, gamma, ptr(gout), ptr(ws), n, hw, c, ptr(d), stream_ptr()), "ctl_seg_loss_bwd")
+    return d
+
+
 def mse_fwd(a, b, scale):
     partial = torch.empty(_ffi.RED_BLOCKS, dtype=torch.float64, device=a.device)
     loss = torch.empty((), dtype=torch.float32, device=a.device)

@@ -20,7 +20,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .autograd import cross_entropy_2D, net_apply, scaled_mse, softmax_t, split_halves
+from .autograd import cross_entropy_2D, net_apply, scaled_mse, segmentation_loss, softmax_t, split_halves
+from .losses import parse_loss_type
 from .metrics import runningScore
 from .model_util import (_disable_tracking_bn_stats, _draw_seed, mask_latent_code_channel_wise,
                          mask_latent_code_spatial_wise, set_grad)
@@ -31,11 +32,21 @@ _DEFAULT_IMG_CFG = {"loss_name": "mse", "mask_type": "random", "max_threshold": 
 _DEFAULT_SEG_CFG = {"loss_name": "ce", "mask_type": "random", "max_threshold": 0.5, "random_threshold": True, "if_soft": True}
 
 
-def basic_loss_fn(pred, target, loss_type="cross entropy"):
-    """custom_loss.py:8-19 -- the solver only ever asks for 'cross entropy'."""
-    if loss_type != "cross entropy":
-        raise NotImplementedError(loss_type)
-    return cross_entropy_2D(pred, target)
+def basic_loss_fn(pred, target, loss_type="cross entropy", class_weights=None, use_gpu=True):
+    """custom_loss.py:8-40 with upstream's names: 'cross entropy', 'weighted cross entropy', 'dice', 'weighted dice' (its weights are
+    ignored, as upstream ignores them), 'foreground dice', 'focal' (gamma 2, upstream's detached gradient); 'contour_smooth' and unknown
+    names raise NotImplementedError.  `loss_type` may also be a mapping {name: weight}: sum of weight * L_name (no upstream counterpart).
+    `class_weights=None` is upstream's uniform 1/C.  Names and weights are checked before the tensors are looked at; the definitions
+    are stated in losses.py."""
+    if loss_type == "cross entropy" and class_weights is None:
+        return cross_entropy_2D(pred, target)
+    terms, class_weights = parse_loss_type(loss_type, class_weights, pred.size(1))
+    total = None
+    for name, weight in terms:
+        l = cross_entropy_2D(pred, target) if name == "cross entropy" else segmentation_loss(pred, target, name, class_weights)
+        l = l if weight == 1.0 else l * weight
+        total = l if total is None else total + l
+    return total
 
 
 SPLIT_BACKWARD = True       # one backward() sweep per launch chain, the standard branch first (see _cooperative_step)
@@ -53,10 +64,14 @@ SPLIT_WGRAD_TAIL = True     # a stacked backward runs its weight-gradient family
 
 class AdvancedTripletReconSegmentationModel(nn.Module):
     def __init__(self, network_type="FCN_16_standard", image_ch=1, learning_rate=1e-4, encoder_dropout=None,
-                 decoder_dropout=None, num_classes=4, n_iter=1, checkpoint_dir=None, use_gpu=True, debug=False, *, compute_dtype=None):
+                 decoder_dropout=None, num_classes=4, n_iter=1, checkpoint_dir=None, use_gpu=True, debug=False, *, compute_dtype=None,
+                 seg_loss_type="cross entropy", class_weights=None):
         """`compute_dtype` (keyword-only, no upstream counterpart): "fp32" = the reference's arithmetic (default, BASELINE config 2);
         "bf16" = BASELINE config 3: network-internal activations / gradients stored as bf16, convolutions on bf16 MFMA with fp32
-        accumulation, fp32 master weights / BatchNorm statistics / losses."""
+        accumulation, fp32 master weights / BatchNorm statistics / losses.
+        `seg_loss_type` / `class_weights` (keyword-only, no upstream counterpart): the `loss_type` and `class_weights` of every
+        `basic_loss_fn` call that compares logits with `label_l` in standard_training and hard_example_training -- a name or a
+        {name: weight} mapping.  The saliency loss of hard_example_generation (`loss_name` of the DA configs) is not affected."""
         super().__init__()
         self.compute_dtype = compute_dtype or "fp32"
         if network_type not in ("FCN_16_standard", "FCN_16_standard_w_o_filter", "FCN_16_standard_share_code"):
@@ -64,6 +79,9 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
         if not use_gpu:
             raise RuntimeError("this engine runs on MI355X only (use_gpu=True); the CPU path is the oracle under oracle/")
         check_config(image_ch, num_classes, 4, self.compute_dtype)      # ValueError before any storage is allocated
+        _, class_weights = parse_loss_type(seg_loss_type, class_weights, num_classes)      # (NotImplementedError / ValueError likewise)
+        self.seg_loss_type = dict(seg_loss_type) if isinstance(seg_loss_type, dict) else seg_loss_type
+        self.class_weights = class_weights
         self.network_type, self.image_ch, self.checkpoint_dir = network_type, image_ch, checkpoint_dir
         self.num_classes, self.learning_rate, self.n_iter = num_classes, learning_rate, n_iter
         self.encoder_dropout, self.decoder_dropout = encoder_dropout, decoder_dropout
@@ -417,7 +435,7 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
             image_recon_loss = None
         if update_latent:
             self.z_i, self.z_s = z_i, z_s
-        standard_supervised_loss = basic_loss_fn(y_0, label_l.detach(), "cross entropy")
+        standard_supervised_loss = basic_loss_fn(y_0, label_l.detach(), self.seg_loss_type, self.class_weights)
         if image_recon_loss is None and _pre is None:
             image_recon = self.decode_image(z_i)                       # always BN mode A, as upstream (model.py:444)
             image_recon_loss = scaled_mse(image_recon, clean_image_l, 0.5)
@@ -425,15 +443,15 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
         if compute_gt_recon and self.group_stn_passes and not disable_track_bn_stats and self.training:
             # the two STN passes are independent and share the BatchNorm mode: one grouped pass (same order: gt, then p)
             gt_recon, p_recon = self.recon_shape_pair(label_l.detach(), True, y_0_new, False)
-            gt_shape_recon_loss = basic_loss_fn(gt_recon, label_l, "cross entropy")
+            gt_shape_recon_loss = basic_loss_fn(gt_recon, label_l, self.seg_loss_type, self.class_weights)
         else:
             if compute_gt_recon:
                 gt_recon = self.recon_shape(label_l.detach(), is_label_map=True)
-                gt_shape_recon_loss = basic_loss_fn(gt_recon, label_l, "cross entropy")
+                gt_shape_recon_loss = basic_loss_fn(gt_recon, label_l, self.seg_loss_type, self.class_weights)
             else:
                 gt_shape_recon_loss = zero
             p_recon = self.recon_shape(y_0_new, is_label_map=False, disable_track_bn_stats=disable_track_bn_stats)
-        pred_shape_recon_loss = basic_loss_fn(p_recon, label_l, "cross entropy")
+        pred_shape_recon_loss = basic_loss_fn(p_recon, label_l, self.seg_loss_type, self.class_weights)
         self._join_side()
         return standard_supervised_loss, image_recon_loss, gt_shape_recon_loss, pred_shape_recon_loss
 
@@ -447,13 +465,13 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
             z_i, z_s = self._enc(perturbed_image.detach(), True)
             recon_loss = self._image_recon_loss(z_i, clean_image_l)              # (side stream when two_streams)
             y_0 = self._call(self.model["segmentation_decoder"], z_s, True)
-            seg_loss = basic_loss_fn(y_0, label_l.detach(), "cross entropy")
+            seg_loss = basic_loss_fn(y_0, label_l.detach(), self.seg_loss_type, self.class_weights)
             if separate_training:
                 perturbed_seg = perturbed_seg.detach()
             p_recon, perturbed_p_recon = self.recon_shape_pair(y_0.detach() if separate_training else y_0, False, perturbed_seg, False,
                                                                disable_track_bn_stats=True)
-            shape_loss = basic_loss_fn(p_recon, label_l, "cross entropy")
-            perturbed_p_recon_loss = basic_loss_fn(perturbed_p_recon, label_l, "cross entropy")
+            shape_loss = basic_loss_fn(p_recon, label_l, self.seg_loss_type, self.class_weights)
+            perturbed_p_recon_loss = basic_loss_fn(perturbed_p_recon, label_l, self.seg_loss_type, self.class_weights)
             self._join_side()
             return seg_loss, recon_loss, shape_loss, perturbed_p_recon_loss
         if perturbed_image is not None:
@@ -464,7 +482,7 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
             if separate_training:
                 perturbed_seg = perturbed_seg.detach()
             perturbed_p_recon = self.recon_shape(perturbed_seg, is_label_map=False, disable_track_bn_stats=True)
-            perturbed_p_recon_loss = basic_loss_fn(perturbed_p_recon, label_l, "cross entropy")
+            perturbed_p_recon_loss = basic_loss_fn(perturbed_p_recon, label_l, self.seg_loss_type, self.class_weights)
         return seg_loss, recon_loss, shape_loss, perturbed_p_recon_loss
 
     # ------------------------------------------------------------------ latent-space hard examples (model.py:300-350, 469-523)

@@ -287,6 +287,34 @@ int ctl_ce2d_fwd(const float* logit, const int64_t* label, int64_t pixels, int32
                  ctl_stream stream);
 int ctl_ce2d_bwd(const float* logit, const int64_t* label, const float* gout, int64_t pixels, int32_t c,
                  float* dlogit, ctl_stream stream);
+/* The other supervised losses of basic_loss_fn (medseg/models/custom_loss.py:8-40), fp32 NHWC logits [b][hw][c] against an int64 label map
+ * [b][hw] (ctl_loss.hip).  p = softmax over c, t = one-hot of the label, M = b * hw, s = 0.01:
+ *   CTL_LOSS_WCE     cross_entropy_2D with class weights (:720-740): w' = w / sum(w) * c;  loss = (1/M) sum_pix w'[y] * -log p_y (the divisor
+ *                    is M, not sum w');  dlogit_k = gout * w'[y] (p_k - t_k) / M.  class_weights = NULL: upstream's uniform 1/c, i.e. w' = 1.
+ *   CTL_LOSS_FOCAL   FocalLoss(gamma) (:222-255): loss = (1/M) sum_pix -(1 - p_y)^gamma log p_y.  Upstream detaches p_y (:243), so the gradient
+ *                    is gout * (1 - p_y)^gamma (p_k - t_k) / M -- not the derivative of the value.
+ *   CTL_LOSS_DICE    SoftDiceLoss (:356-396): per sample and class I = sum p t + s, U = sum p + sum t + s; loss = 1 - (sum 2I/U) / (b c).
+ *   CTL_LOSS_FG_DICE SelectiveSoftDiceLoss over the classes 1..c-1 (:434-471): term (2 sum p t + s) / (sum p + sum t + s), divisor b (c - 1).
+ *                    Both Dice forms: g_k = dL/dp_k = coef[b][k][0] t_k + coef[b][k][1], dlogit_j = gout p_j (g_j - sum_k p_k g_k).
+ * A label outside 0..c-1 is no class (t = 0 for every k, weight 0); labels are compared, never used as an index.
+ * class_weights: HOST array of c doubles (read during the call, CTL_LOSS_WCE only) or NULL; gamma: CTL_LOSS_FOCAL only.
+ * ws: ctl_seg_loss_ws_doubles(kind, b, hw, c) doubles, every one written by the forward.  Point-wise kinds: [CTL_RED_BLOCKS] block sums.
+ *   Dice kinds: [b][ctl_seg_loss_blocks(b, hw)][c][3] block sums (sum p, sum p t, count of y == k), then the [b][c][2] coefficient table the
+ *   backward reads -- hand the forward's ws to the backward (the point-wise kinds ignore it there, NULL allowed).  The blocks per sample are
+ *   capped at CTL_RED_BLOCKS / b (at least 1), so the block sums never exceed max(CTL_RED_BLOCKS, b) * c * 3 doubles.
+ * fwd: two launches (partial sums, one finalize block) write loss[0]; bwd: one launch reads gout[0] on the device and writes every element of
+ * dlogit.  Sums are ordered, fp64, free of atomics: the same bits on every call and in a graph replay.  Rows of c == 4 in 16-byte aligned
+ * tensors move as 16 bytes; any other case takes the runtime-count kernels, same arithmetic in the same order.
+ * Null pointers, an unknown kind, non-positive sizes, c outside 1..16 (foreground Dice: 2..16), more than 65535 samples, a tensor at or past
+ * 2 GiB, class weights whose sum is not finite and positive, and a gamma that is not finite and >= 0 are refused with CTL_EINVAL before any
+ * launch; ctl_seg_loss_ws_doubles returns 0 for them. */
+enum { CTL_LOSS_WCE = 0, CTL_LOSS_FOCAL = 1, CTL_LOSS_DICE = 2, CTL_LOSS_FG_DICE = 3 };
+int32_t ctl_seg_loss_blocks(int32_t b, int64_t hw);
+size_t ctl_seg_loss_ws_doubles(int32_t kind, int32_t b, int64_t hw, int32_t c);
+int ctl_seg_loss_fwd(int32_t kind, const float* logit, const int64_t* label, const double* class_weights, float gamma, int32_t b,
+                     int64_t hw, int32_t c, double* ws, float* loss, ctl_stream stream);
+int ctl_seg_loss_bwd(int32_t kind, const float* logit, const int64_t* label, const double* class_weights, float gamma, const float* gout,
+                     const double* ws, int32_t b, int64_t hw, int32_t c, float* dlogit, ctl_stream stream);
 /* loss = scale * mean((a-b)^2) (model.py:445-447: scale 0.5; util.py:216: scale 1); bwd: da = gout*2*scale*(a-b)/count */
 int ctl_mse_fwd(const float* a, const float* b, int64_t count, float scale, double* partial, float* loss,
                 ctl_stream stream);

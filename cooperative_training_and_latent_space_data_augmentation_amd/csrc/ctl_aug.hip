@@ -10,7 +10,7 @@
 //   ctl_aug_bias    smooth multiplicative bias field, min-max normalisation, Gaussian noise (intensity_transform.py:373-546), a pre-pass
 //   ctl_aug_coarse_field   the displacement of the 3x3 coarse grid (elastic_transform.py:105-172); both at the end of this file
 // The contract of all of them is written out in include/ctl_hip.h.
-#include "ctl_common.h"
+#include "ctl_device.h"
 
 #define AUG_B 256
 #define AUG_MAX_SIDE 512          // LDS staging of one row / one column tile is sized for this
@@ -18,14 +18,12 @@
 #define AUG_COLS 16               // columns of one column-pass tile: 512 x 16 floats = 32 KiB of LDS
 #define AUG_BPP 64                // min / max partial blocks per plane (the scheme of ctl_rescale_intensity)
 #define AUG_TW 64                 // warp tile: 64 pixels along x (one wave per row: coalesced stores) x 4 rows
-#define S_ (hipStream_t) stream
 
-static inline size_t aug_align(size_t b) { return (b + 255) & ~(size_t)255; }
 static inline bool aug_shape_ok(int n, int hp, int wp, int hc, int wc) {
     return n > 0 && n <= 65535 && hp > 0 && wp > 0 && hp <= AUG_MAX_SIDE && wp <= AUG_MAX_SIDE && hc > 0 && wc > 0 && hc <= hp && wc <= wp;
 }
-static inline size_t aug_tmp_bytes(int n, int hp, int wp) { return aug_align((size_t)n * 2 * hp * wp * sizeof(float)); }
-static inline size_t aug_partial_bytes(int n) { return aug_align((size_t)n * AUG_BPP * 2 * sizeof(float)); }
+static inline size_t aug_tmp_bytes(int n, int hp, int wp) { return ctl_align256((size_t)n * 2 * hp * wp * sizeof(float)); }
+static inline size_t aug_partial_bytes(int n) { return ctl_align256((size_t)n * AUG_BPP * 2 * sizeof(float)); }
 
 extern "C" size_t ctl_aug_ws_bytes(int32_t n, int32_t hp, int32_t wp) { return aug_shape_ok(n, hp, wp, 1, 1) ? aug_tmp_bytes(n, hp, wp) : 0; }
 extern "C" size_t ctl_aug_warp_ws_bytes(int32_t n, int32_t hp, int32_t wp, int32_t hc, int32_t wc) {
@@ -37,23 +35,16 @@ struct aug_range { const void* p; size_t bytes; };
 static bool aug_any_overlap(const aug_range* r, int count, int nw) {
     for (int i = 0; i < nw; ++i)
         for (int j = 0; j < count; ++j) {
-            if (j == i || (j < nw && j < i) || !r[i].p || !r[j].p) continue;
-            const uintptr_t a = (uintptr_t)r[i].p, b = (uintptr_t)r[j].p;
-            if (a < b + r[j].bytes && b < a + r[i].bytes) return true;
+            if (j == i || (j < nw && j < i)) continue;
+            if (ctl_overlap(r[i].p, r[i].bytes, r[j].p, r[j].bytes)) return true;
         }
     return false;
 }
 
 // ------------------------------------------------------------------------------------------------ elastic displacement
-__device__ __forceinline__ uint64_t aug_mix(uint64_t z) {      // splitmix64 finaliser, the generator of ctl_io.hip / ctl_mask.hip
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 // uniform in [-1, 1) on a 2^-23 grid from (seed, sample * 2 + axis, pixel): stateless, the same value whatever the launch geometry
 __device__ __forceinline__ float aug_uniform(uint64_t seed, int plane, int pixel) {
-    const uint64_t h = aug_mix(seed ^ aug_mix(((uint64_t)(uint32_t)plane << 32) | (uint32_t)pixel));
+    const uint64_t h = ctl_mix64(seed ^ ctl_mix64(((uint64_t)(uint32_t)plane << 32) | (uint32_t)pixel));
     return (float)(h >> 40) * (1.0f / 8388608.0f) - 1.0f;
 }
 
@@ -157,15 +148,6 @@ extern "C" int ctl_aug_field(const float* noise, const uint64_t* seeds, const fl
 }
 
 // ------------------------------------------------------------------------------------------------ warp
-__device__ __forceinline__ void aug_block_minmax(float& mn, float& mx, float* sm) {
-    for (int o = 32; o > 0; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o)); mx = fmaxf(mx, __shfl_xor(mx, o)); }
-    const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { sm[wv * 2] = mn; sm[wv * 2 + 1] = mx; }
-    __syncthreads();
-    mn = sm[0]; mx = sm[1];
-    for (int i = 1; i < AUG_B / 64; ++i) { mn = fminf(mn, sm[i * 2]); mx = fmaxf(mx, sm[i * 2 + 1]); }
-    __syncthreads();
-}
 __global__ __launch_bounds__(AUG_B) void aug_minmax_partial_kernel(const float* __restrict__ x, int plane_elems, float* __restrict__ partial) {
     __shared__ float sm[2 * AUG_B / 64];
     const float* xp = x + (int64_t)blockIdx.y * plane_elems;
@@ -174,7 +156,7 @@ __global__ __launch_bounds__(AUG_B) void aug_minmax_partial_kernel(const float* 
         const float v = xp[i];
         mn = fminf(mn, v); mx = fmaxf(mx, v);
     }
-    aug_block_minmax(mn, mx, sm);
+    ctl_block_minmax<AUG_B>(mn, mx, sm);
     if (threadIdx.x == 0) { partial[((int64_t)blockIdx.y * AUG_BPP + blockIdx.x) * 2] = mn; partial[((int64_t)blockIdx.y * AUG_BPP + blockIdx.x) * 2 + 1] = mx; }
 }
 
@@ -209,7 +191,7 @@ __global__ __launch_bounds__(AUG_B) void aug_warp_kernel(const float* __restrict
     if (threadIdx.x < AUG_BPP) { mn = partial[((int64_t)b * AUG_BPP + threadIdx.x) * 2]; mx = partial[((int64_t)b * AUG_BPP + threadIdx.x) * 2 + 1]; }
     if (threadIdx.x < 6) prm[threadIdx.x] = matrix[b * 6 + threadIdx.x];
     else if (threadIdx.x < 8) prm[threadIdx.x] = intensity[b * 2 + threadIdx.x - 6];
-    aug_block_minmax(mn, mx, sm);                              // its barriers also publish prm[]
+    ctl_block_minmax<AUG_B>(mn, mx, sm);                       // its barriers also publish prm[]
     const int x = (int)blockIdx.x * AUG_TW + (threadIdx.x & 63), y = (int)blockIdx.y * (AUG_B / AUG_TW) + (threadIdx.x >> 6);
     if (x >= wc || y >= hc) return;
     const int64_t plane = (int64_t)hp * wp;
@@ -282,7 +264,7 @@ extern "C" int ctl_aug_warp(const float* image, const int64_t* label, const floa
 static inline bool aug_spline_ok(int n, int hp, int wp, int n_class, int min_class) {
     return aug_shape_ok(n, hp, wp, 1, 1) && n_class >= min_class && n_class <= AUG_MAX_CLASS;
 }
-static inline size_t aug_planes_bytes(int n, int hp, int wp, int n_class) { return aug_align((size_t)n * (1 + n_class) * hp * wp * sizeof(float)); }
+static inline size_t aug_planes_bytes(int n, int hp, int wp, int n_class) { return ctl_align256((size_t)n * (1 + n_class) * hp * wp * sizeof(float)); }
 static inline size_t aug_spline_bytes(int n, int hp, int wp, int n_class) { return aug_partial_bytes(n) + aug_planes_bytes(n, hp, wp, n_class); }
 static inline size_t aug_cubic_bytes(int n, int hp, int wp, int n_class) { return aug_partial_bytes(n) + 2 * aug_planes_bytes(n, hp, wp, n_class); }
 
@@ -345,7 +327,7 @@ __global__ __launch_bounds__(AUG_B) void aug_spline_row_kernel(const float* __re
     if (pl == 0) {                                             // block-uniform
         float mn = INFINITY, mx = -INFINITY;
         if (threadIdx.x < AUG_BPP) { mn = partial[((int64_t)b * AUG_BPP + threadIdx.x) * 2]; mx = partial[((int64_t)b * AUG_BPP + threadIdx.x) * 2 + 1]; }
-        aug_block_minmax(mn, mx, sm);
+        ctl_block_minmax<AUG_B>(mn, mx, sm);
         const double scale = (double)intensity[b * 2], bright = (double)intensity[b * 2 + 1];
         for (int j = threadIdx.x; j < wp + 2 * AUG_SP_R; j += AUG_B)
             ext[j] = fmin(fmax(fma((double)image[in_row + aug_reflect(j - AUG_SP_R, wp)], scale, bright), (double)mn), (double)mx);
@@ -520,8 +502,8 @@ extern "C" int ctl_aug_warp_cubic(const float* image, const int64_t* label, cons
 static inline bool aug_bias_ok(int n, int hp, int wp) {
     return n > 0 && n <= 65535 && hp == wp && (hp & 1) == 0 && hp >= AUG_BIAS_MIN_SIDE && hp <= AUG_MAX_SIDE;
 }
-static inline size_t aug_bias_plane_bytes(int n, int hp, int wp) { return aug_align((size_t)n * hp * wp * sizeof(float)); }
-static inline size_t aug_bias_partial_bytes(int n) { return aug_align((size_t)n * AUG_BPP * 3 * sizeof(double)); }
+static inline size_t aug_bias_plane_bytes(int n, int hp, int wp) { return ctl_align256((size_t)n * hp * wp * sizeof(float)); }
+static inline size_t aug_bias_partial_bytes(int n) { return ctl_align256((size_t)n * AUG_BPP * 3 * sizeof(double)); }
 static inline size_t aug_bias_bytes(int n, int hp, int wp) { return aug_bias_plane_bytes(n, hp, wp) + aug_bias_partial_bytes(n); }
 
 extern "C" size_t ctl_aug_bias_ws_bytes(int32_t n, int32_t hp, int32_t wp) { return aug_bias_ok(n, hp, wp) ? aug_bias_bytes(n, hp, wp) : 0; }
@@ -613,7 +595,7 @@ __global__ __launch_bounds__(AUG_B) void aug_bias_field_kernel(const float* __re
 
 // standard normal from (seed, sample, pixel): the counter hash and the two uniforms of ctl_noise_clamp, Box-Muller in fp64
 __device__ __forceinline__ double aug_normal(uint64_t seed, int sample, int pixel) {
-    const uint64_t h = aug_mix(seed ^ aug_mix(((uint64_t)(uint32_t)sample << 32) | (uint32_t)pixel));
+    const uint64_t h = ctl_mix64(seed ^ ctl_mix64(((uint64_t)(uint32_t)sample << 32) | (uint32_t)pixel));
     const double u1 = (double)((h >> 40) + 1) * (1.0 / 16777216.0);          // (0, 1]
     const double u2 = (double)((h >> 8) & 0xFFFFFFu) * (1.0 / 16777216.0);   // [0, 1)
     return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);

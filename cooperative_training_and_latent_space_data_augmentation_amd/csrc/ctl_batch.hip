@@ -5,10 +5,9 @@
 // Copies and byte look-ups only: bandwidth-bound, no floating-point arithmetic, no atomics, no readback.  The slice geometry is a
 // function of blockIdx alone (index[b], then one table row), so it is fetched once per block through the scalar cache; source rows are
 // read at whatever element offset the slice has, output rows are stored as 16-byte vectors wherever the address allows.
-#include "ctl_common.h"
+#include "ctl_device.h"
 
 #define BB 256
-#define S_ (hipStream_t) stream
 #define BATCH_MAX_SIDE 32768
 #define BATCH_MAX_BLOCKS_X 64         // blocks that share one output plane (each strides over the plane's groups of four elements)
 

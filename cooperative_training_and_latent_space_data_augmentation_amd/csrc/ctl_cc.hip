@@ -15,9 +15,8 @@
 //   5. cc_output_kernel   out = class where P == the selected label, else 0; the table
 // i.e. 3 launches for ctl_cc_label (1-3, P = the caller's label array) and 5 for ctl_cc_keep_largest.  Integer atomics only (min, max,
 // add): every result is independent of arrival order, the same bits on every call.
-#include "ctl_common.h"
+#include "ctl_device.h"
 
-#define S_ (hipStream_t) stream
 #define CC_THREADS 256
 #define CC_TW 64                       // tile width: the lanes of a wave
 #define CC_TH 16                       // tile height: 4 rows per wave
@@ -249,8 +248,6 @@ struct cc_plan {
     size_t off_parent, off_size, off_best, off_ncomp, bytes;
 };
 
-static inline size_t cc_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 static int cc_make_plan(const char* who, int32_t d, int32_t h, int32_t w, int32_t n_class, int32_t mode, cc_plan* p) {
     CTL_REQUIRE(d >= 1 && h >= 1 && w >= 1, "%s: D, H, W must be positive (got %d, %d, %d)", who, d, h, w);
     CTL_REQUIRE(n_class >= 2 && n_class <= 255, "%s: n_class %d outside 2..255", who, n_class);
@@ -267,10 +264,10 @@ static int cc_make_plan(const char* who, int32_t d, int32_t h, int32_t w, int32_
     CTL_REQUIRE(p->groups * p->bpg < (1ll << 31) && (int64_t)d * p->tiles_x * p->tiles_y < (1ll << 31) && p->nsel < (1ll << 31),
                 "%s: the problem is too large for one launch (%lld voxels)", who, (long long)p->vox);
     size_t off = 0;
-    p->off_parent = off; off += cc_align((size_t)p->vox * sizeof(int32_t));
-    p->off_size = off; off += cc_align((size_t)p->vox * sizeof(int32_t));
-    p->off_best = off; off += cc_align((size_t)p->nsel * sizeof(unsigned long long));
-    p->off_ncomp = off; off += cc_align((size_t)p->nsel * sizeof(int32_t));
+    p->off_parent = off; off += ctl_align256((size_t)p->vox * sizeof(int32_t));
+    p->off_size = off; off += ctl_align256((size_t)p->vox * sizeof(int32_t));
+    p->off_best = off; off += ctl_align256((size_t)p->nsel * sizeof(unsigned long long));
+    p->off_ncomp = off; off += ctl_align256((size_t)p->nsel * sizeof(int32_t));
     p->bytes = off;
     return CTL_OK;
 }

@@ -8,11 +8,10 @@
 //                         over up to 1 + CTL_CORRUPT_MAX_COPIES stacked volumes, fp32 FMA tiles through LDS, strided for the outer axes
 // No floating-point atomics, every sum in a fixed order: identical bits on every call.  No readback, a launch sequence that depends on
 // the shapes only.
-#include "ctl_common.h"
+#include "ctl_device.h"
 #include <math.h>
 
 #define CB 256
-#define S_ (hipStream_t) stream
 #define COR_TENSOR_BYTES (1ll << 31)
 #define COR_EPB 2048                 // elements per block the spike reduction aims at
 #define COR_NCOEF 20                 // monomials u^i v^j w^k with i + j + k <= 3
@@ -20,11 +19,6 @@
 
 static inline bool cor_shape_ok(int32_t d, int32_t h, int32_t w) {
     return d >= 1 && h >= 1 && w >= 1 && (int64_t)d * h * w * 4 < COR_TENSOR_BYTES;
-}
-static inline bool cor_overlap(const float* a, int64_t na, const float* b, int64_t nb) { return a && b && a < b + nb && b < a + na; }
-static inline int cor_grid(int64_t total) {
-    const int64_t b = ctl_cdiv64(total, CB);
-    return (int)(b > 4096 ? 4096 : b);
 }
 
 // ------------------------------------------------------------------------------------------------ bias field
@@ -59,13 +53,13 @@ extern "C" int ctl_corrupt_bias(const float* x, const float* coefficients, int32
     CTL_REQUIRE(d >= 1 && h >= 1 && w >= 1, "corrupt_bias: sizes must be positive (%d x %d x %d)", d, h, w);
     CTL_REQUIRE(cor_shape_ok(d, h, w), "corrupt_bias: %d x %d x %d floats reach the 2 GiB tensor limit (32-bit byte offsets)", d, h, w);
     const int64_t n = (int64_t)d * h * w;
-    CTL_REQUIRE(!cor_overlap(x, n, out, n), "corrupt_bias: out aliases x (a separate output array is required)");
+    CTL_REQUIRE(!ctl_overlap(x, n * 4, out, n * 4), "corrupt_bias: out aliases x (a separate output array is required)");
     cor_coef cf;
     for (int i = 0; i < COR_NCOEF; ++i) {
         CTL_REQUIRE(isfinite(coefficients[i]), "corrupt_bias: coefficient %d is not finite", i);
         cf.c[i] = coefficients[i];
     }
-    cor_bias_kernel<<<dim3((unsigned)cor_grid(n)), dim3(CB), 0, S_>>>(x, out, d, h, w, cf);
+    cor_bias_kernel<<<dim3(ctl_blocks(n, CB, 4096)), dim3(CB), 0, S_>>>(x, out, d, h, w, cf);
     CTL_LAUNCH_CHECK("corrupt_bias");
     return CTL_OK;
 }
@@ -76,10 +70,7 @@ extern "C" int ctl_corrupt_bias(const float* x, const float* coefficients, int32
 struct cor_spikes { int32_t n; int32_t k[CTL_CORRUPT_MAX_SPIKES][3]; int32_t mult[CTL_CORRUPT_MAX_SPIKES]; };
 #define COR_NVAL (1 + 2 * CTL_CORRUPT_MAX_SPIKES)
 
-static inline int cor_red_blocks(int64_t n) {
-    const int64_t b = ctl_cdiv64(n, COR_EPB);
-    return (int)(b < 1 ? 1 : (b > CTL_CORRUPT_RED_BLOCKS ? CTL_CORRUPT_RED_BLOCKS : b));
-}
+static inline int cor_red_blocks(int64_t n) { return (int)ctl_blocks(n, COR_EPB, CTL_CORRUPT_RED_BLOCKS); }
 
 // th / (2 pi) for voxel (td, th, tw): every (k_a t_a) mod n_a is exact in integers, the three fractions are added in fp64
 __device__ __forceinline__ double cor_turns(const int32_t* k, int td, int th, int tw, int d, int h, int w) {
@@ -164,7 +155,7 @@ extern "C" int ctl_corrupt_spike(const float* x, int32_t d, int32_t h, int32_t w
                 CTL_CORRUPT_MAX_SPIKES);
     CTL_REQUIRE(isfinite(intensity), "corrupt_spike: intensity %g is not finite", intensity);
     const int64_t n = (int64_t)d * h * w;
-    CTL_REQUIRE(!cor_overlap(x, n, out, n), "corrupt_spike: out aliases x (a separate output array is required)");
+    CTL_REQUIRE(!ctl_overlap(x, n * 4, out, n * 4), "corrupt_spike: out aliases x (a separate output array is required)");
     const int32_t size[3] = {d, h, w};
     cor_spikes sp = {};
     sp.n = n_spikes;
@@ -185,7 +176,7 @@ extern "C" int ctl_corrupt_spike(const float* x, int32_t d, int32_t h, int32_t w
     CTL_REQUIRE(((uintptr_t)workspace & 7) == 0, "corrupt_spike: the workspace must be 8-byte aligned");
     const int nblk = cor_red_blocks(n);
     cor_spike_reduce_kernel<<<dim3((unsigned)nblk), dim3(CB), 0, S_>>>(x, d, h, w, sp, (double*)workspace);
-    cor_spike_apply_kernel<<<dim3((unsigned)cor_grid(n)), dim3(CB), 0, S_>>>(x, out, d, h, w, sp, intensity, (const double*)workspace, nblk);
+    cor_spike_apply_kernel<<<dim3(ctl_blocks(n, CB, 4096)), dim3(CB), 0, S_>>>(x, out, d, h, w, sp, intensity, (const double*)workspace, nblk);
     ctl_count_launches(1);                                     // two kernels, CTL_LAUNCH_CHECK counts one
     CTL_LAUNCH_CHECK("corrupt_spike");
     return CTL_OK;
@@ -239,13 +230,13 @@ extern "C" int ctl_corrupt_rigid3d(const float* x, int32_t d, int32_t h, int32_t
     CTL_REQUIRE(cor_shape_ok(d, h, w) && (int64_t)d * h * w * copies * 4 < COR_TENSOR_BYTES,
                 "corrupt_rigid3d: %d copies of %d x %d x %d floats reach the 2 GiB tensor limit (32-bit byte offsets)", copies, d, h, w);
     const int64_t n = (int64_t)d * h * w;
-    CTL_REQUIRE(!cor_overlap(x, n, out, n * copies), "corrupt_rigid3d: out aliases x (a separate output array is required)");
+    CTL_REQUIRE(!ctl_overlap(x, n * 4, out, n * copies * 4), "corrupt_rigid3d: out aliases x (a separate output array is required)");
     cor_rigid rg = {};
     for (int i = 0; i < copies * 12; ++i) {
         CTL_REQUIRE(isfinite(matrices[i]), "corrupt_rigid3d: matrix entry %d of copy %d is not finite", i % 12, i / 12);
         rg.m[i / 12][i % 12] = matrices[i];
     }
-    cor_rigid_kernel<<<dim3((unsigned)cor_grid(n * copies)), dim3(CB), 0, S_>>>(x, out, d, h, w, copies, rg);
+    cor_rigid_kernel<<<dim3(ctl_blocks(n * copies, CB, 4096)), dim3(CB), 0, S_>>>(x, out, d, h, w, copies, rg);
     CTL_LAUNCH_CHECK("corrupt_rigid3d");
     return CTL_OK;
 }
@@ -319,7 +310,7 @@ extern "C" int ctl_axis_operator(const float* x0, const float* xs, int32_t n_vol
     CTL_REQUIRE(cor_shape_ok(d, h, w) && n * (n_volumes - 1) * 4 < COR_TENSOR_BYTES && len * len * n_volumes * 4 < COR_TENSOR_BYTES,
                 "axis_operator: %d volumes of %d x %d x %d floats, or the %lld x %lld matrix, reach the 2 GiB tensor limit (32-bit byte offsets)",
                 n_volumes, d, h, w, (long long)len, (long long)(len * n_volumes));
-    CTL_REQUIRE(!cor_overlap(x0, n, out, n) && !cor_overlap(n_volumes > 1 ? xs : nullptr, n * (n_volumes - 1), out, n),
+    CTL_REQUIRE(!ctl_overlap(x0, n * 4, out, n * 4) && !ctl_overlap(n_volumes > 1 ? xs : nullptr, n * (n_volumes - 1) * 4, out, n * 4),
                 "axis_operator: out aliases an input volume (a separate output array is required)");
     const int inner = axis == 0 ? h * w : (axis == 1 ? w : 1);
     const int rows = (int)(n / len);

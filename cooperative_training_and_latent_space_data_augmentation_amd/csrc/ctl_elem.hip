@@ -2,7 +2,7 @@
 // backward, STN input builders, fused losses, argmax and the flat multi-tensor Adam.  All fp32 NHWC; 16 bytes per lane
 // wherever the channel count allows, wavefront(64)-shuffle + LDS block reductions, two-stage deterministic sums
 // (per-block partials in fp32, finalisation in fp64) instead of float atomics.
-#include "ctl_common.h"
+#include "ctl_device.h"
 
 #define EB 256               // threads per block for the streaming kernels
 #ifndef CTL_FIN_THREADS
@@ -10,16 +10,9 @@
 #endif
 #define MAX_STREAM_BLOCKS 2048
 
-static inline unsigned stream_blocks(int64_t work_items) {
-    int64_t b = ctl_cdiv64(work_items, EB);
-    if (b > MAX_STREAM_BLOCKS) b = MAX_STREAM_BLOCKS;
-    if (b < 1) b = 1;
-    return (unsigned)b;
-}
-
 // sums two values over the block at once: thread 0 gets both (one LDS round instead of two)
 __device__ __forceinline__ void block_sum_double2(double& a, double& b, double* sm) {
-    for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o); b += __shfl_xor(b, o); }
+    a = wave_sum_double(a); b = wave_sum_double(b);
     const int w = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) { sm[w] = a; sm[8 + w] = b; }
     __syncthreads();
@@ -46,8 +39,9 @@ __device__ __forceinline__ void sum_rows2(const float* __restrict__ partial, int
         for (int u = 0; u < 4; ++u) { s1 += (double)v1[u]; s2 += (double)v2[u]; }
     }
 }
+// (ctl_block_sum_double of ctl_device.h with the block width read from blockDim, see CTL_FIN_THREADS; kept apart because the shared form,
+// built on wave_sum_double, schedules one instruction of these kernels differently)
 __device__ __forceinline__ double block_sum_double(double v, double* sm) {
-    // 256 threads: wave shuffle then LDS
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     const int w = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) sm[w] = v;
@@ -482,9 +476,6 @@ template <int CT> __device__ __forceinline__ void row_store(float* __restrict__ 
         if (vec4) kernel<4><<<grid, dim3(EB), 0, S_>>>(__VA_ARGS__);             \
         else kernel<0><<<grid, dim3(EB), 0, S_>>>(__VA_ARGS__);                  \
     } while (0)
-static inline bool rows_vec4(int c, const void* a, const void* b = nullptr, const void* d = nullptr) {
-    return c == 4 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)d) & 15) == 0;      // 16-byte rows need 16-byte aligned tensors
-}
 template <int CT>
 __global__ __launch_bounds__(EB) void softmax_t_fwd_kernel(const float* __restrict__ x, float inv_t, float* __restrict__ p,
                                                             int64_t pixels, int c_rt) {
@@ -663,14 +654,13 @@ __global__ __launch_bounds__(EB) void accumulate_kernel(float* __restrict__ dst,
 }
 
 // ------------------------------------------------------------------------------------------------ launchers
-#define S_ (hipStream_t) stream
 
 extern "C" int ctl_accumulate(float* dst, const float* const* srcs, int32_t k, int64_t count, ctl_stream stream) {
     CTL_REQUIRE(dst && srcs && k >= 1 && k <= 8 && count > 0, "accumulate: bad arguments (1 <= k <= 8)");
     ctl_ptr8 a;
     for (int j = 0; j < 8; ++j) a.p[j] = j < k ? srcs[j] : nullptr;
     for (int j = 0; j < k; ++j) CTL_REQUIRE(a.p[j], "accumulate: null source %d", j);
-    accumulate_kernel<<<dim3(stream_blocks(count)), dim3(EB), 0, S_>>>(dst, a, k, count);
+    accumulate_kernel<<<dim3(ctl_blocks(count, EB, MAX_STREAM_BLOCKS)), dim3(EB), 0, S_>>>(dst, a, k, count);
     CTL_LAUNCH_CHECK("accumulate");
     return CTL_OK;
 }
@@ -744,8 +734,8 @@ extern "C" int ctl_bn_act_dt(const float* x, const float* scale, const float* sh
     CTL_REQUIRE(x && y && scale && shift && c % 4 == 0 && pixels > 0 && groups >= 1 && pixels % groups == 0,
                 "bn_act: bad arguments (c must be a multiple of 4, pixels of groups)");
     const int64_t quads = pixels * (c / 4);
-    bn_act_kernel<<<dim3(stream_blocks(quads)), dim3(EB), 0, S_>>>(x, (const f32x4*)scale, (const f32x4*)shift, slope, y, quads, c / 4,
-                                                                   quads / groups, bf16_mask);
+    bn_act_kernel<<<dim3(ctl_blocks(quads, EB, MAX_STREAM_BLOCKS)), dim3(EB), 0, S_>>>(x, (const f32x4*)scale, (const f32x4*)shift, slope, y, quads,
+                                                                                       c / 4, quads / groups, bf16_mask);
     CTL_LAUNCH_CHECK("bn_act");
     return CTL_OK;
 }
@@ -819,11 +809,11 @@ extern "C" int ctl_bwd_apply_dt(int32_t mode, const float* dy, const float* act_
                                 int32_t c, float* ds, float* dx, int32_t groups, uint32_t bf16_mask, ctl_stream stream) {
     CTL_REQUIRE(dy && bn_src && coef && dx && pixels > 0 && c % 4 == 0 && groups >= 1 && pixels % groups == 0, "bwd_apply: bad arguments");
     const int64_t quads = pixels * (c / 4);
-    const dim3 grid(stream_blocks(quads)), blk(EB);
+    const dim3 grid(ctl_blocks(quads, EB, MAX_STREAM_BLOCKS)), blk(EB);
     // every tensor stored as bf16 and whole channel octets: 16 bytes per lane (mask bits: 0 dy, 1 act_src, 2 bn_src, 3 ds, 4 dx)
     const unsigned need = mode == 0 ? (1u | 2u | 4u | 16u | (ds ? 8u : 0u)) : (1u | 4u | 16u);
     const bool oct = c % 8 == 0 && (bf16_mask & need) == need;
-    const dim3 grid8(stream_blocks(quads / 4));      // two octets per thread and trip
+    const dim3 grid8(ctl_blocks(quads / 4, EB, MAX_STREAM_BLOCKS));      // two octets per thread and trip
     if (mode == 0) {
         CTL_REQUIRE(act_src, "bwd_apply mode 0 needs act_src");
         if (oct)
@@ -868,7 +858,7 @@ extern "C" int ctl_sumpool2_dt(const float* dup, float* dx, int32_t n, int32_t h
                                uint32_t bf16_mask, ctl_stream stream) {
     CTL_REQUIRE(dup && dx && n > 0 && h > 0 && w > 0 && c % 4 == 0, "sumpool2: bad arguments");
     const int64_t quads = (int64_t)n * h * w * (c / 4);
-    sumpool2_kernel<<<dim3(stream_blocks(quads)), dim3(EB), 0, S_>>>(dup, dx, n, h, w, c / 4, accumulate, bf16_mask);
+    sumpool2_kernel<<<dim3(ctl_blocks(quads, EB, MAX_STREAM_BLOCKS)), dim3(EB), 0, S_>>>(dup, dx, n, h, w, c / 4, accumulate, bf16_mask);
     CTL_LAUNCH_CHECK("sumpool2");
     return CTL_OK;
 }
@@ -878,33 +868,33 @@ extern "C" int ctl_sumpool2(const float* dup, float* dx, int32_t n, int32_t h, i
 }
 extern "C" int ctl_sigmoid_bwd(const float* dy, const float* y, float* dx, int64_t count, ctl_stream stream) {
     CTL_REQUIRE(dy && y && dx && count > 0, "sigmoid_bwd: bad arguments");
-    sigmoid_bwd_kernel<<<dim3(stream_blocks(count)), dim3(EB), 0, S_>>>(dy, y, dx, count);
+    sigmoid_bwd_kernel<<<dim3(ctl_blocks(count, EB, MAX_STREAM_BLOCKS)), dim3(EB), 0, S_>>>(dy, y, dx, count);
     CTL_LAUNCH_CHECK("sigmoid_bwd");
     return CTL_OK;
 }
 extern "C" int ctl_softmax_t_fwd(const float* x, float inv_t, float* p, int64_t pixels, int32_t c, ctl_stream stream) {
     CTL_REQUIRE(x && p && pixels > 0 && c > 0 && c <= MAXC, "softmax_t_fwd: bad arguments");
-    CTL_ROW_DISPATCH(softmax_t_fwd_kernel, rows_vec4(c, x, p), dim3(stream_blocks(pixels)), x, inv_t, p, pixels, c);
+    CTL_ROW_DISPATCH(softmax_t_fwd_kernel, ctl_vec4(c, x, p), dim3(ctl_blocks(pixels, EB, MAX_STREAM_BLOCKS)), x, inv_t, p, pixels, c);
     CTL_LAUNCH_CHECK("softmax_t_fwd");
     return CTL_OK;
 }
 extern "C" int ctl_softmax_t_bwd(const float* p, const float* dp, float inv_t, float* dx, int64_t pixels, int32_t c,
                                  ctl_stream stream) {
     CTL_REQUIRE(p && dp && dx && pixels > 0 && c > 0 && c <= MAXC, "softmax_t_bwd: bad arguments");
-    CTL_ROW_DISPATCH(softmax_t_bwd_kernel, rows_vec4(c, p, dp, dx), dim3(stream_blocks(pixels)), p, dp, inv_t, dx, pixels, c);
+    CTL_ROW_DISPATCH(softmax_t_bwd_kernel, ctl_vec4(c, p, dp, dx), dim3(ctl_blocks(pixels, EB, MAX_STREAM_BLOCKS)), p, dp, inv_t, dx, pixels, c);
     CTL_LAUNCH_CHECK("softmax_t_bwd");
     return CTL_OK;
 }
 extern "C" int ctl_onehot(const int64_t* label, float* y, int64_t pixels, int32_t c, ctl_stream stream) {
     CTL_REQUIRE(label && y && pixels > 0 && c > 0, "onehot: bad arguments");
-    onehot_kernel<<<dim3(stream_blocks(pixels)), dim3(EB), 0, S_>>>(label, y, pixels, c);
+    onehot_kernel<<<dim3(ctl_blocks(pixels, EB, MAX_STREAM_BLOCKS)), dim3(EB), 0, S_>>>(label, y, pixels, c);
     CTL_LAUNCH_CHECK("onehot");
     return CTL_OK;
 }
 extern "C" int ctl_ce2d_fwd(const float* logit, const int64_t* label, int64_t pixels, int32_t c, double* partial,
                             float* loss, ctl_stream stream) {
     CTL_REQUIRE(logit && label && partial && loss && pixels > 0 && c > 0 && c <= MAXC, "ce2d_fwd: bad arguments");
-    CTL_ROW_DISPATCH(ce2d_partial_kernel, rows_vec4(c, logit), dim3(CTL_RED_BLOCKS), logit, label, pixels, c, partial);
+    CTL_ROW_DISPATCH(ce2d_partial_kernel, ctl_vec4(c, logit), dim3(CTL_RED_BLOCKS), logit, label, pixels, c, partial);
     scalar_finalize_kernel<<<dim3(1), dim3(EB), 0, S_>>>(partial, CTL_RED_BLOCKS, 1.0 / (double)pixels, loss);
     ctl_count_launches(1);      // partial + finalize
     CTL_LAUNCH_CHECK("ce2d_fwd");
@@ -913,7 +903,7 @@ extern "C" int ctl_ce2d_fwd(const float* logit, const int64_t* label, int64_t pi
 extern "C" int ctl_ce2d_bwd(const float* logit, const int64_t* label, const float* gout, int64_t pixels, int32_t c,
                             float* dlogit, ctl_stream stream) {
     CTL_REQUIRE(logit && label && gout && dlogit && pixels > 0 && c > 0 && c <= MAXC, "ce2d_bwd: bad arguments");
-    CTL_ROW_DISPATCH(ce2d_bwd_kernel, rows_vec4(c, logit, dlogit), dim3(stream_blocks(pixels)), logit, label, gout, pixels, c, dlogit);
+    CTL_ROW_DISPATCH(ce2d_bwd_kernel, ctl_vec4(c, logit, dlogit), dim3(ctl_blocks(pixels, EB, MAX_STREAM_BLOCKS)), logit, label, gout, pixels, c, dlogit);
     CTL_LAUNCH_CHECK("ce2d_bwd");
     return CTL_OK;
 }
@@ -929,13 +919,13 @@ extern "C" int ctl_mse_fwd(const float* a, const float* b, int64_t count, float 
 extern "C" int ctl_mse_bwd(const float* a, const float* b, const float* gout, int64_t count, float scale, float* da,
                            ctl_stream stream) {
     CTL_REQUIRE(a && b && gout && da && count > 0, "mse_bwd: bad arguments");
-    mse_bwd_kernel<<<dim3(stream_blocks(count)), dim3(EB), 0, S_>>>(a, b, gout, count, scale, da);
+    mse_bwd_kernel<<<dim3(ctl_blocks(count, EB, MAX_STREAM_BLOCKS)), dim3(EB), 0, S_>>>(a, b, gout, count, scale, da);
     CTL_LAUNCH_CHECK("mse_bwd");
     return CTL_OK;
 }
 extern "C" int ctl_argmax_c(const float* logit, uint8_t* out, int64_t pixels, int32_t c, ctl_stream stream) {
     CTL_REQUIRE(logit && out && pixels > 0 && c > 0 && c < 256, "argmax_c: bad arguments");
-    argmax_kernel<<<dim3(stream_blocks(pixels)), dim3(EB), 0, S_>>>(logit, out, pixels, c);
+    argmax_kernel<<<dim3(ctl_blocks(pixels, EB, MAX_STREAM_BLOCKS)), dim3(EB), 0, S_>>>(logit, out, pixels, c);
     CTL_LAUNCH_CHECK("argmax_c");
     return CTL_OK;
 }
@@ -944,7 +934,7 @@ extern "C" int ctl_adam(float* p, const float* g, float* m, float* v, int64_t co
     CTL_REQUIRE(p && g && m && v && count > 0 && step >= 1, "adam: bad arguments");
     const double bc1 = 1.0 - pow((double)beta1, (double)step);
     const double bc2 = 1.0 - pow((double)beta2, (double)step);
-    adam_kernel<<<dim3(stream_blocks(count)), dim3(EB), 0, S_>>>(p, g, m, v, count, lr, beta1, beta2, eps, (float)bc1,
+    adam_kernel<<<dim3(ctl_blocks(count, EB, MAX_STREAM_BLOCKS)), dim3(EB), 0, S_>>>(p, g, m, v, count, lr, beta1, beta2, eps, (float)bc1,
                                                                  (float)sqrt(bc2), grad_scale, nullptr);
     CTL_LAUNCH_CHECK("adam");
     return CTL_OK;
@@ -952,7 +942,7 @@ extern "C" int ctl_adam(float* p, const float* g, float* m, float* v, int64_t co
 extern "C" int ctl_adam_dev(float* p, const float* g, float* m, float* v, int64_t count, float lr, float beta1, float beta2,
                             float eps, const int64_t* state, float grad_scale, ctl_stream stream) {
     CTL_REQUIRE(p && g && m && v && count > 0 && state, "adam_dev: bad arguments");
-    adam_kernel<<<dim3(stream_blocks(count)), dim3(EB), 0, S_>>>(p, g, m, v, count, lr, beta1, beta2, eps, 1.f, 1.f, grad_scale, state);
+    adam_kernel<<<dim3(ctl_blocks(count, EB, MAX_STREAM_BLOCKS)), dim3(EB), 0, S_>>>(p, g, m, v, count, lr, beta1, beta2, eps, 1.f, 1.f, grad_scale, state);
     CTL_LAUNCH_CHECK("adam_dev");
     return CTL_OK;
 }

@@ -6,12 +6,11 @@
 //
 // A label outside 0..c-1 is no class: one-hot 0 for every k, weight 0.  Labels are only ever compared with a class index.
 #include <cmath>
-#include "ctl_common.h"
+#include "ctl_device.h"
 
 #define EB 256               // threads per block
 #define MAXC 16
 #define LOSS_MAX_STREAM_BLOCKS 2048
-#define S_ (hipStream_t) stream
 
 struct ctl_w16 { float v[MAXC]; };      // normalised class weights, a launch argument (constant from step to step)
 
@@ -46,14 +45,6 @@ template <int CT> __device__ __forceinline__ float lrow_exp(float* v, int c, flo
 #pragma unroll
     for (int k = 0; k < NC; ++k) if (k < c) { v[k] = expf(v[k] - m); s += v[k]; }
     return m;
-}
-__device__ __forceinline__ double loss_block_sum(double v, double* sm) {      // valid on thread 0; fixed order
-    v = wave_sum_double(v);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double r = 0.0;
-    if (threadIdx.x == 0) for (int i = 0; i < EB / 64; ++i) r += sm[i];
-    return r;
 }
 
 // ------------------------------------------------------------------------------------------------ point-wise kinds
@@ -101,7 +92,7 @@ __global__ __launch_bounds__(EB) void seg_pw_partial_kernel(const float* __restr
         const float f = pw_factor<CT>(kind, v, s, c, l, w, gamma);
         acc += (double)(-(f * (xl - m - logf(s))));
     }
-    acc = loss_block_sum(acc, sm);
+    acc = ctl_block_sum_double<EB / 64>(acc, sm);
     if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 __global__ __launch_bounds__(EB) void seg_pw_finalize_kernel(const double* __restrict__ partial, int blocks, double mul,
@@ -109,7 +100,7 @@ __global__ __launch_bounds__(EB) void seg_pw_finalize_kernel(const double* __res
     __shared__ double sm[EB / 64];
     double s = 0.0;
     for (int b = threadIdx.x; b < blocks; b += EB) s += partial[b];
-    s = loss_block_sum(s, sm);
+    s = ctl_block_sum_double<EB / 64>(s, sm);
     if (threadIdx.x == 0) out[0] = (float)(s * mul);
 }
 
@@ -192,7 +183,7 @@ __global__ __launch_bounds__(EB) void dice_finalize_kernel(const double* __restr
             acc += sel ? num / U : 0.0;
         }
     }
-    acc = loss_block_sum(acc, sm);
+    acc = ctl_block_sum_double<EB / 64>(acc, sm);
     if (threadIdx.x == 0) loss[0] = (float)(1.0 - acc / div);
 }
 
@@ -255,9 +246,6 @@ __global__ __launch_bounds__(EB) void seg_loss_bwd_kernel(const float* __restric
 }
 
 // ------------------------------------------------------------------------------------------------ launchers
-static inline bool loss_vec4(int c, const void* a, const void* b = nullptr) {
-    return c == 4 && (((uintptr_t)a | (uintptr_t)b) & 15) == 0;      // 16-byte rows need 16-byte aligned tensors
-}
 static inline bool kind_is_dice(int kind) { return kind == CTL_LOSS_DICE || kind == CTL_LOSS_FG_DICE; }
 // blocks per sample of the two-dimensional grids: at most `cap` blocks over all samples (one per sample where b exceeds the cap)
 static inline int sample_blocks(int64_t b, int64_t hw, int cap) {
@@ -304,7 +292,7 @@ extern "C" int ctl_seg_loss_fwd(int32_t kind, const float* logit, const int64_t*
     if (int rc = seg_loss_check("seg_loss_fwd", kind, b, hw, c)) return rc;
     ctl_w16 w;
     if (int rc = seg_loss_weights("seg_loss_fwd", kind, c, class_weights, gamma, &w)) return rc;
-    const bool v4 = loss_vec4(c, logit);
+    const bool v4 = ctl_vec4(c, logit);
     if (kind_is_dice(kind)) {
         const int nb = sample_blocks(b, hw, CTL_RED_BLOCKS);
         double* coef = ws + (size_t)b * nb * c * 3;
@@ -332,7 +320,7 @@ extern "C" int ctl_seg_loss_bwd(int32_t kind, const float* logit, const int64_t*
     const double* coef = kind_is_dice(kind) ? ws + (size_t)b * sample_blocks(b, hw, CTL_RED_BLOCKS) * c * 3 : nullptr;
     const dim3 grid(sample_blocks(b, hw, LOSS_MAX_STREAM_BLOCKS), b);
     const float pixels_f = (float)((int64_t)b * hw);
-    if (loss_vec4(c, logit, dlogit)) seg_loss_bwd_kernel<4><<<grid, dim3(EB), 0, S_>>>(logit, label, gout, coef, hw, c, kind, w, gamma, pixels_f, dlogit);
+    if (ctl_vec4(c, logit, dlogit)) seg_loss_bwd_kernel<4><<<grid, dim3(EB), 0, S_>>>(logit, label, gout, coef, hw, c, kind, w, gamma, pixels_f, dlogit);
     else seg_loss_bwd_kernel<0><<<grid, dim3(EB), 0, S_>>>(logit, label, gout, coef, hw, c, kind, w, gamma, pixels_f, dlogit);
     CTL_LAUNCH_CHECK("seg_loss_bwd");
     return CTL_OK;

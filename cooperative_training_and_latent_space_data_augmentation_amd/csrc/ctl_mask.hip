@@ -11,7 +11,7 @@
 // sits in L2/Infinity Cache and the pair is launch-latency bound; bench.py sweeps sizes to show the HBM-bound regime.
 #include <stdlib.h>
 
-#include "ctl_common.h"
+#include "ctl_device.h"
 
 #define MB 256
 // once-written / once-read streams of the HBM-sized problems: non-temporal policy (tuning: -DCTL_MASK_NT=0 none, 1 stores, 2 + loads)
@@ -417,17 +417,14 @@ __global__ __launch_bounds__(IB) void latent_mask_image_kernel(const f32x4* __re
 
 // ---- dropout2d and uniform noise from a counter hash (splitmix64): stateless, graph-replay safe given a seed buffer
 __device__ __forceinline__ float hash_uniform(uint64_t seed, uint64_t idx) {
-    uint64_t z = seed + (idx + 1) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z = z ^ (z >> 31);
+    const uint64_t z = ctl_mix64(seed + idx * CTL_MIX_GAMMA);
     return (float)(z >> 40) * (1.0f / 16777216.0f);   // 24 random bits -> [0,1)
 }
 // Device-resident RNG state (HIP-graph replays: nothing may be baked into the launch): state[0] = seed, state[1] = step counter
 // advanced once per training step by ctl_step_tick; `salt` separates the call sites of one step.
 __device__ __forceinline__ uint64_t state_seed(const int64_t* __restrict__ state, uint64_t salt) {
-    uint64_t z = (uint64_t)state[0] + ((uint64_t)state[1] + 1) * 0xD1B54A32D192ED03ull + salt * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 32)) * 0xBF58476D1CE4E5B9ull;
+    uint64_t z = (uint64_t)state[0] + ((uint64_t)state[1] + 1) * 0xD1B54A32D192ED03ull + salt * CTL_MIX_GAMMA;
+    z = (z ^ (z >> 32)) * CTL_MIX_M1;
     return z ^ (z >> 29);
 }
 // `m`: storage of z (bit 0) / out (bit 1): set = bf16 (network-internal tensors of BASELINE config 3); the product is formed in fp32 and

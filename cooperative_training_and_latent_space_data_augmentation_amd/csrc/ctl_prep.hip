@@ -7,24 +7,18 @@
 //   ctl_resample_inplane   resample_by_spacing (dataset_utils.py:39-63) with keep_z_spacing: linear for the image, nearest for the label
 // All of it is HBM-bound integer / element-wise work: no MFMA, no floating-point atomics, no readback, a launch sequence that depends
 // on the shapes only.
-#include "ctl_common.h"
+#include "ctl_device.h"
 #include <math.h>
 
 #pragma clang fp contract(off)      // every multiply and add below rounds on its own (numpy / torch order), as in ctl_io.hip
 
 #define PB 256
-#define S_ (hipStream_t) stream
 #define PREP_MAX_RANK 8
 #define PREP_BPS 128                 // most blocks that share one segment (the pass-0 block histograms are sized for it)
 #define PREP_EPB 4096                // elements per block aimed at
 #define PREP_TENSOR_BYTES (1ll << 31)
 
 struct prep_ranks { uint32_t k[PREP_MAX_RANK]; };
-
-static inline int prep_bps(int64_t seg_elems) {
-    int64_t b = ctl_cdiv64(seg_elems, PREP_EPB);
-    return (int)(b < 1 ? 1 : (b > PREP_BPS ? PREP_BPS : b));
-}
 
 // ------------------------------------------------------------------------------------------------ radix select
 // key order == float order (-0.0 before +0.0, negatives reversed); a NaN is just another key, which element it displaces is unspecified
@@ -188,7 +182,7 @@ extern "C" int ctl_order_stats(const float* x, int32_t segments, int64_t seg_ele
     CTL_REQUIRE(((uintptr_t)workspace & 3) == 0, "order_stats: the workspace must be 4-byte aligned");
     uint32_t* bh = (uint32_t*)workspace;
     uint32_t* hist = bh + (size_t)segments * PREP_BPS * 256;
-    const int bps = prep_bps(seg_elems);
+    const int bps = (int)ctl_blocks(seg_elems, PREP_EPB, PREP_BPS);
     const dim3 grid((unsigned)bps, (unsigned)segments), blk(PB);
     for (int p = 0; p < 4; ++p) prep_select_pass_kernel<<<grid, blk, 0, S_>>>(x, seg_elems, n_rank, rk, p, bps, bh, hist);
     prep_select_finish_kernel<<<dim3((unsigned)segments), blk, 0, S_>>>(n_rank, rk, bps, bh, hist, out);
@@ -249,11 +243,10 @@ extern "C" int ctl_percentile_apply(const float* x, const float* table, int32_t 
     CTL_REQUIRE(form == 0 || form == 1, "percentile_apply: form %d (0 = minmax, 1 = medic)", form);
     CTL_REQUIRE(g_lo >= 0.0 && g_lo < 1.0 && g_hi >= 0.0 && g_hi < 1.0, "percentile_apply: weights %g, %g outside [0, 1)", g_lo, g_hi);
     const int64_t total = (int64_t)segments * seg_elems;
-    CTL_REQUIRE(!out || out + total <= x || x + total <= out, "percentile_apply: out aliases x (a separate output array is required)");
-    int64_t b = out ? ctl_cdiv64(seg_elems, PB * 4) : 1;
-    b = b < 1 ? 1 : (b > 256 ? 256 : b);
-    prep_percentile_apply_kernel<<<dim3((unsigned)b, (unsigned)segments), dim3(PB), 0, S_>>>(x, table, seg_elems, g_lo, g_hi, form, new_min,
-                                                                                              new_max, out, bounds);
+    CTL_REQUIRE(!ctl_overlap(x, (size_t)total * 4, out, (size_t)total * 4), "percentile_apply: out aliases x (a separate output array is required)");
+    const unsigned b = out ? ctl_blocks(seg_elems, PB * 4, 256) : 1;
+    prep_percentile_apply_kernel<<<dim3(b, (unsigned)segments), dim3(PB), 0, S_>>>(x, table, seg_elems, g_lo, g_hi, form, new_min,
+                                                                                    new_max, out, bounds);
     CTL_LAUNCH_CHECK("percentile_apply");
     return CTL_OK;
 }

@@ -5,13 +5,12 @@
 //   ctl_restore_labels   window-grid uint8 labels -> native-grid uint8 labels, nearest neighbour, one launch
 // One thread per native voxel, lanes along x: neighbouring lanes read the same or neighbouring window pixels (L2 / L1 hits) and every
 // store of a wave is contiguous.  No workspace, no atomics, no readback: the launches depend on the shapes only.
-#include "ctl_common.h"
+#include "ctl_device.h"
 #include <math.h>
 
 #pragma clang fp contract(off)      // every multiply and add rounds on its own (the numpy statement's order), as in ctl_prep.hip
 
 #define RB 256
-#define S_ (hipStream_t) stream
 #define RESTORE_MAX_C 16
 #define RESTORE_TENSOR_BYTES (1ll << 31)
 
@@ -144,11 +143,6 @@ __global__ __launch_bounds__(RB) void restore_labels_kernel(const uint8_t* __res
     }
 }
 
-static inline unsigned restore_blocks(int64_t items) {
-    int64_t b = ctl_cdiv64(items, RB);
-    return (unsigned)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
-}
-
 // the checks both entries share: sizes, ratios, the 2 GiB limit of the label volumes
 #define RESTORE_REQUIRE_GEOMETRY(who)                                                                                                      \
     CTL_REQUIRE(n > 0 && win_h > 0 && win_w > 0 && h > 0 && w > 0 && res_h > 0 && res_w > 0,                                               \
@@ -167,8 +161,8 @@ extern "C" int ctl_restore_scores(const float* scores, int32_t n, int32_t c, int
     CTL_REQUIRE((int64_t)n * c * win_h * win_w * 4 < RESTORE_TENSOR_BYTES && (int64_t)n * h * w < RESTORE_TENSOR_BYTES &&
                     (!soft || (int64_t)n * c * h * w * 4 < RESTORE_TENSOR_BYTES),
                 "restore_scores: %d x %d x %d x %d -> %d x %d reaches the 2 GiB tensor limit (32-bit byte offsets)", n, c, win_h, win_w, h, w);
-    const dim3 grid(restore_blocks((int64_t)n * h * w)), blk(RB);
-    if (c == 4 && ((uintptr_t)scores & 15) == 0)
+    const dim3 grid(ctl_blocks((int64_t)n * h * w, RB, 2048)), blk(RB);
+    if (ctl_vec4(c, scores))
         restore_scores_kernel<4><<<grid, blk, 0, S_>>>(scores, label, soft, n, c, win_h, win_w, h, w, res_h, res_w, off_y, off_x, q_h, q_w, mode);
     else
         restore_scores_kernel<0><<<grid, blk, 0, S_>>>(scores, label, soft, n, c, win_h, win_w, h, w, res_h, res_w, off_y, off_x, q_h, q_w, mode);
@@ -182,8 +176,8 @@ extern "C" int ctl_restore_labels(const uint8_t* labels, int32_t n, int32_t win_
     RESTORE_REQUIRE_GEOMETRY("restore_labels");
     CTL_REQUIRE((int64_t)n * win_h * win_w < RESTORE_TENSOR_BYTES && (int64_t)n * h * w < RESTORE_TENSOR_BYTES,
                 "restore_labels: %d x %d x %d -> %d x %d reaches the 2 GiB tensor limit (32-bit byte offsets)", n, win_h, win_w, h, w);
-    restore_labels_kernel<<<dim3(restore_blocks((int64_t)n * h * w)), dim3(RB), 0, S_>>>(labels, out, n, win_h, win_w, h, w, res_h, res_w, off_y,
-                                                                                        off_x, q_h, q_w);
+    restore_labels_kernel<<<dim3(ctl_blocks((int64_t)n * h * w, RB, 2048)), dim3(RB), 0, S_>>>(labels, out, n, win_h, win_w, h, w, res_h, res_w,
+                                                                                              off_y, off_x, q_h, q_w);
     CTL_LAUNCH_CHECK("restore_labels");
     return CTL_OK;
 }

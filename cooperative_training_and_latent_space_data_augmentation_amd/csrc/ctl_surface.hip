@@ -33,9 +33,8 @@
 // No readback, no synchronisation, no data-dependent launch; the max / sum / count partials are those of ctl_surface_stats, bit for bit.
 #include <math.h>
 
-#include "ctl_common.h"
+#include "ctl_device.h"
 
-#define S_ (hipStream_t) stream
 #define SF_THREADS 256
 #define SF_COLS 64                     // lanes of a wave: 64 consecutive elements of the contiguous axis
 #define SF_R 8                         // output rows per thread of a column pass
@@ -44,8 +43,6 @@
 #define SF_NONE 65535u
 #define SF_MAXDIM 65534                // offsets along a row are stored as uint16
 #define SF_OUTSIDE 255                 // canonical label of a voxel that belongs to no class
-
-static inline size_t sf_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
 __device__ __forceinline__ int sf_canon_pred(uint8_t p, int n, int fg) { return fg ? (p > 0) : (p < n ? (int)p : SF_OUTSIDE); }
 __device__ __forceinline__ int sf_canon_gt(int64_t t, int n, int fg) { return fg ? (t > 0) : ((t >= 0 && t < n) ? (int)t : SF_OUTSIDE); }
@@ -460,10 +457,10 @@ static int sf_make_plan(const char* who, int32_t d, int32_t h, int32_t w, int64_
     CTL_REQUIRE(plane_blocks < (1ll << 31) && p->groups * p->bpo < (1ll << 31) && p->masks * p->vox < (1ll << 40),
                 "%s: the problem is too large for one launch (%lld masks of %lld voxels)", who, (long long)p->masks, (long long)p->vox);
     size_t off = 0;
-    p->off_code = off; off += sf_align((size_t)sides * p->vox);
-    p->off_g = off; off += sf_align((size_t)p->masks * p->vox * sizeof(uint16_t));
-    p->off_f = off; off += mode == 3 ? sf_align((size_t)p->masks * p->vox * sizeof(double)) : 0;
-    p->off_partial = off; off += reduce ? sf_align((size_t)p->groups * p->bpo * 3 * sizeof(double)) : 0;
+    p->off_code = off; off += ctl_align256((size_t)sides * p->vox);
+    p->off_g = off; off += ctl_align256((size_t)p->masks * p->vox * sizeof(uint16_t));
+    p->off_f = off; off += mode == 3 ? ctl_align256((size_t)p->masks * p->vox * sizeof(double)) : 0;
+    p->off_partial = off; off += reduce ? ctl_align256((size_t)p->groups * p->bpo * 3 * sizeof(double)) : 0;
     p->bytes = off;
     return CTL_OK;
 }
@@ -474,11 +471,6 @@ static int sf_sampling(const char* who, const double* sampling, int32_t mode, do
         CTL_REQUIRE(isfinite(s[a]) && s[a] > 0.0, "%s: sampling[%d] = %g must be finite and positive", who, a, s[a]);
     }
     return CTL_OK;
-}
-
-static inline unsigned sf_blocks(int64_t items, int per_block) {
-    int64_t b = ctl_cdiv64(items, per_block);
-    return (unsigned)(b > 8192 ? 8192 : b);
 }
 
 static int sf_stats_args(int32_t d, int32_t h, int32_t w, int32_t n_class, int32_t mode, int32_t connectivity) {
@@ -529,7 +521,7 @@ static int sf_run(const uint8_t* pred, const int64_t* gt, int32_t d, int32_t h, 
     unsigned long long* keys = nullptr;
     const int gpm = mode == 2 ? d : 1;
 
-    sf_code_kernel<<<dim3(sf_blocks(2 * p.vox, SF_THREADS)), dim3(SF_THREADS), 0, S_>>>(pred, gt, d, h, w, n_class, fg, mode, connectivity, 2, code);
+    sf_code_kernel<<<dim3(ctl_blocks(2 * p.vox, SF_THREADS, 8192)), dim3(SF_THREADS), 0, S_>>>(pred, gt, d, h, w, n_class, fg, mode, connectivity, 2, code);
     CTL_LAUNCH_CHECK("surface_code");
     if (qp) {
         unsigned* cnt = (unsigned*)(ws + qp->off_cnt);
@@ -611,11 +603,11 @@ static int sf_make_qplan(int32_t d, int32_t h, int32_t w, int64_t classes, int32
     qp->groups = classes * qp->gpm;
     qp->n_q = n_q;
     size_t off = p->bytes;
-    qp->off_cnt = off; off += sf_align((size_t)2 * d * classes * sizeof(unsigned));
-    qp->off_gn = off; off += sf_align((size_t)qp->groups * 2 * sizeof(unsigned));
-    qp->off_first = off; off += sf_align((size_t)qp->groups * sizeof(int64_t));
-    qp->off_cursor = off; off += sf_align((size_t)qp->groups * sizeof(unsigned));
-    qp->off_keys = off; off += sf_align((size_t)2 * p->vox * sizeof(unsigned long long));      // surfaces of one side are disjoint
+    qp->off_cnt = off; off += ctl_align256((size_t)2 * d * classes * sizeof(unsigned));
+    qp->off_gn = off; off += ctl_align256((size_t)qp->groups * 2 * sizeof(unsigned));
+    qp->off_first = off; off += ctl_align256((size_t)qp->groups * sizeof(int64_t));
+    qp->off_cursor = off; off += ctl_align256((size_t)qp->groups * sizeof(unsigned));
+    qp->off_keys = off; off += ctl_align256((size_t)2 * p->vox * sizeof(unsigned long long));      // surfaces of one side are disjoint
     qp->bytes = off;
     return CTL_OK;
 }
@@ -671,7 +663,7 @@ extern "C" int ctl_surface_map(const uint8_t* mask, int32_t d, int32_t h, int32_
     CTL_REQUIRE(!d2_out || workspace_bytes >= p.bytes, "surface_map: workspace of %zu bytes, %zu needed", workspace_bytes, p.bytes);
     char* ws = (char*)workspace;
     uint8_t* code = surface_out ? surface_out : (uint8_t*)(ws + p.off_code);
-    sf_code_kernel<<<dim3(sf_blocks(p.vox, SF_THREADS)), dim3(SF_THREADS), 0, S_>>>(mask, nullptr, d, h, w, 2, 1, mode, connectivity, 1, code);
+    sf_code_kernel<<<dim3(ctl_blocks(p.vox, SF_THREADS, 8192)), dim3(SF_THREADS), 0, S_>>>(mask, nullptr, d, h, w, 2, 1, mode, connectivity, 1, code);
     CTL_LAUNCH_CHECK("surface_code");
     if (!d2_out) return CTL_OK;
     uint16_t* g = (uint16_t*)(ws + p.off_g);

@@ -38,6 +38,134 @@ class CtlError(RuntimeError):
     pass
 
 
+def _signatures() -> dict:
+    """Every entry of include/ctl_hip.h, in the header's order: name -> (return type, argument types).  The one place a ctl_* name is
+    spelled as a definition: load() applies it, EXPORTED is its keys, tests/test_cabi.py compares it with the header's prototypes."""
+    p, cstr, int_, i32, i64, u32, u64, f32, f64, sz = (C.c_void_p, C.c_char_p, C.c_int, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64,
+                                                       C.c_float, C.c_double, C.c_size_t)
+    return {
+        "ctl_version": (int_, []),
+        "ctl_last_error": (cstr, []),
+        "ctl_conv_wpack_floats": (sz, [i32, i32, i32]),
+        "ctl_conv_stats_floats": (sz, [p]),
+        "ctl_conv_stats_blocks": (int_, [p]),
+        "ctl_pack_weights": (int_, [p, p, i32, i32, i32] + [i64] * 4 + [i32, p]),
+        "ctl_conv_forward": (int_, [p] * 12),
+        "ctl_conv_forward_ex": (int_, [p] * 16),
+        "ctl_conv_pool_ok": (int_, [p]),
+        "ctl_wgrad_splits": (int_, [p]),
+        "ctl_wgrad_partial_floats": (sz, [p]),
+        "ctl_wgrad_bias_partial_floats": (sz, [p]),
+        "ctl_conv_wgrad": (int_, [p] * 8),
+        "ctl_conv_wgrad_ex": (int_, [p] * 10),
+        "ctl_wgrad_group_class": (int_, [p, i32]),
+        "ctl_wgrad_group_plan": (int_, [p, i32, p]),
+        "ctl_conv_wgrad_group": (int_, [i32] + [p] * 11),
+        "ctl_wgrad_reduce": (int_, [p] * 4 + [i64] * 4 + [p, i32, p]),
+        "ctl_pack_weights_batched": (int_, [p, p, p, i32, i64, p]),
+        "ctl_wgrad_reduce_batched": (int_, [p, p, p, i32, i64, p]),
+        "ctl_pack_weights_bf16_batched": (int_, [p, p, p, i32, i64, p]),
+        "ctl_conv_wpack_floats_x3": (sz, [i32, i32, i32]),
+        "ctl_pack_weights_x3_batched": (int_, [p, p, p, i32, i64, p]),
+        "ctl_bn_finalize": (int_, [p, i32, i32, i64, p, p, f32, f32, i32] + [p] * 7 + [i32, p]),
+        "ctl_bn_finalize_ex": (int_, [p, i32, i32, i64, p, p, f32, f32, i32] + [p] * 8 + [i32, p]),
+        "ctl_bn_replay_running": (int_, [p] * 4 + [i32, f32, p]),
+        "ctl_bn_eval_coeffs": (int_, [i32] + [p] * 4 + [f32, p, p, i32, p]),
+        "ctl_bn_act": (int_, [p, p, p, f32, p, i64, i32, i32, p]),
+        "ctl_bwd_reduce": (int_, [i32] + [p] * 5 + [f32, i64, i32, p, i32, p]),
+        "ctl_bwd_reduce_rows": (int_, [i32, i64, i32]),
+        "ctl_red_blocks": (int_, []),
+        "ctl_bn_bwd_finalize": (int_, [p, i32, i64] + [p] * 6 + [i32, i32, i32, p]),
+        "ctl_bn_bwd_finalize_ex": (int_, [p, i32, i64] + [p] * 6 + [i32, i32, i32, u32, p]),
+        "ctl_bwd_apply": (int_, [i32] + [p] * 5 + [f32, p, i64, i32, p, p, i32, p]),
+        "ctl_chan_sum_finalize": (int_, [p, i32, p, i32, p]),
+        "ctl_sumpool2": (int_, [p, p] + [i32] * 5 + [p]),
+        "ctl_sigmoid_bwd": (int_, [p, p, p, i64, p]),
+        "ctl_softmax_t_fwd": (int_, [p, f32, p, i64, i32, p]),
+        "ctl_softmax_t_bwd": (int_, [p, p, f32, p, i64, i32, p]),
+        "ctl_onehot": (int_, [p, p, i64, i32, p]),
+        "ctl_ce2d_fwd": (int_, [p, p, i64, i32, p, p, p]),
+        "ctl_ce2d_bwd": (int_, [p, p, p, i64, i32, p, p]),
+        "ctl_seg_loss_blocks": (int_, [i32, i64]),
+        "ctl_seg_loss_ws_doubles": (sz, [i32, i32, i64, i32]),
+        "ctl_seg_loss_fwd": (int_, [i32, p, p, p, f32, i32, i64, i32, p, p, p]),
+        "ctl_seg_loss_bwd": (int_, [i32, p, p, p, f32, p, p, i32, i64, i32, p, p]),
+        "ctl_mse_fwd": (int_, [p, p, i64, f32, p, p, p]),
+        "ctl_mse_bwd": (int_, [p, p, p, i64, f32, p, p]),
+        "ctl_argmax_c": (int_, [p, p, i64, i32, p]),
+        "ctl_bn_act_dt": (int_, [p, p, p, f32, p, i64, i32, i32, u32, p]),
+        "ctl_bwd_reduce_dt": (int_, [i32] + [p] * 5 + [f32, i64, i32, p, i32, u32, p, p]),
+        "ctl_bwd_apply_dt": (int_, [i32] + [p] * 5 + [f32, p, i64, i32, p, p, i32, u32, p]),
+        "ctl_sumpool2_dt": (int_, [p, p] + [i32] * 5 + [u32, p]),
+        "ctl_latent_score_ws_floats": (sz, [i32] * 4),
+        "ctl_latent_score": (int_, [i32, p, p, p, i32, i32, i32, p]),
+        "ctl_latent_mask_apply_ws_floats": (sz, [i32] * 4),
+        "ctl_latent_mask_apply": (int_, [i32, p, p, p, i32] + [p] * 4 + [i32, i32, i32, p]),
+        "ctl_latent_mask_fused_ws_floats": (sz, [i32] * 4),
+        "ctl_latent_mask_fused": (int_, [i32, p, p, p, i32] + [p] * 5 + [i32, i32, i32, p]),
+        "ctl_dropout2d": (int_, [p, p, u64, f32, p, p, i32, i32, i32, p]),
+        "ctl_uniform": (int_, [p, i64, u64, p]),
+        "ctl_step_tick": (int_, [p, p]),
+        "ctl_spin": (int_, [i32, p]),
+        "ctl_dropout2d_ex": (int_, [p, p, u64, p, f32, p, p, p, i32, i32, i32, p]),
+        "ctl_uniform_dev": (int_, [p, i64, u64, p, p]),
+        "ctl_dropout2d_dt": (int_, [p, p, u64, p, f32, p, p, i32, i32, i32, u32, p]),
+        "ctl_confusion_hist": (int_, [p, p, i64, i32, p, p]),
+        "ctl_rescale_intensity_ws_floats": (sz, [i32]),
+        "ctl_rescale_intensity": (int_, [p, p, p, i32, i64, f32, f32, f32, p]),
+        "ctl_noise_clamp": (int_, [p, p, u64, f32, f32, f32, p, i64, p]),
+        "ctl_crop_or_pad": (int_, [p, p] + [i32] * 6 + [p]),
+        "ctl_surface_stats_rows": (int_, [i32] * 4),
+        "ctl_surface_stats_ws_bytes": (sz, [i32] * 6),
+        "ctl_surface_stats": (int_, [p, p] + [i32] * 7 + [p, p, p, sz, p]),
+        "ctl_surface_quantiles_ws_bytes": (sz, [i32] * 7),
+        "ctl_surface_quantiles": (int_, [p, p] + [i32] * 7 + [p, p, i32, p, p, p, sz, p]),
+        "ctl_surface_map_ws_bytes": (sz, [i32] * 4),
+        "ctl_surface_map": (int_, [p] + [i32] * 5 + [p] * 4 + [sz, p]),
+        "ctl_cc_ws_bytes": (sz, [i32] * 5),
+        "ctl_cc_label": (int_, [p] + [i32] * 6 + [p, p]),
+        "ctl_cc_keep_largest": (int_, [p] + [i32] * 6 + [p, p, p, sz, p]),
+        "ctl_aug_ws_bytes": (sz, [i32, i32, i32]),
+        "ctl_aug_warp_ws_bytes": (sz, [i32] * 5),
+        "ctl_aug_field": (int_, [p] * 4 + [i32, i32, i32, p, p, sz, p]),
+        "ctl_aug_warp": (int_, [p] * 5 + [i32] * 5 + [p, p, p, sz, p]),
+        "ctl_aug_spline_ws_bytes": (sz, [i32] * 4),
+        "ctl_aug_warp_cubic_ws_bytes": (sz, [i32] * 6),
+        "ctl_aug_spline_coeffs": (int_, [p, p, p] + [i32] * 4 + [p, p, sz, p]),
+        "ctl_aug_warp_cubic": (int_, [p] * 5 + [i32] * 6 + [p, p, p, sz, p]),
+        "ctl_aug_bias_ws_bytes": (sz, [i32, i32, i32]),
+        "ctl_aug_bias": (int_, [p] * 4 + [i32, i32, i32, p, p, sz, p]),
+        "ctl_aug_coarse_field": (int_, [p, i32, i32, i32, p, p]),
+        "ctl_order_stats_ws_bytes": (sz, [i32, i32]),
+        "ctl_order_stats": (int_, [p, i32, i64, p, i32, p, p, sz, p]),
+        "ctl_percentile_apply": (int_, [p, p, i32, i64, f64, f64, i32, f32, f32, p, p, p]),
+        "ctl_resample_inplane": (int_, [p, p] + [i32] * 6 + [f64, f64, p, p, p]),
+        "ctl_restore_scores": (int_, [p] + [i32] * 10 + [f64, f64, i32, p, p, p]),
+        "ctl_restore_labels": (int_, [p] + [i32] * 9 + [f64, f64, p, p]),
+        "ctl_corrupt_bias": (int_, [p, p, i32, i32, i32, p, p]),
+        "ctl_corrupt_spike_ws_bytes": (sz, [i32] * 4),
+        "ctl_corrupt_spike": (int_, [p, i32, i32, i32, p, p, i32, f64, p, p, sz, p]),
+        "ctl_corrupt_rigid3d": (int_, [p, i32, i32, i32, p, i32, p, p]),
+        "ctl_axis_operator": (int_, [p, p] + [i32] * 5 + [p, p, p]),
+        "ctl_slice_foreground": (int_, [p, p, i32, i64, p, p]),
+        "ctl_batch_gather": (int_, [p, p, p, i32, i64, p, i32, p, i32, i32, p, p, i32, i32, p, p, p]),
+        "ctl_adam": (int_, [p] * 4 + [i64] + [f32] * 4 + [i32, f32, p]),
+        "ctl_accumulate": (int_, [p, p, i32, i64, p]),
+        "ctl_adam_dev": (int_, [p] * 4 + [i64] + [f32] * 4 + [p, f32, p]),
+        "ctl_plan_run": (int_, [p, i32, p, i32, p]),
+        "ctl_prof_start": (int_, [cstr]),
+        "ctl_prof_start_sampled": (int_, [cstr, i32]),
+        "ctl_prof_stop": (int_, [p, sz]),
+        "ctl_launch_count": (C.c_ulonglong, []),
+        "ctl_sizeof_op": (sz, []),
+        "ctl_sizeof_conv": (sz, []),
+    }
+
+
+SIGNATURES = _signatures()
+EXPORTED = list(SIGNATURES)
+
+
 class _Lib:
     def __init__(self):
         self._lib = None
@@ -53,109 +181,9 @@ class _Lib:
         # failed with "no ROCm-capable device is detected" (build() followed by smoke() in one process).
         import torch  # noqa: F401
         lib = C.CDLL(LIB_PATH)
-        lib.ctl_last_error.restype = C.c_char_p
-        lib.ctl_version.restype = C.c_int
-        lib.ctl_launch_count.restype = C.c_ulonglong
-        for name in ("ctl_conv_wpack_floats", "ctl_conv_stats_floats", "ctl_wgrad_partial_floats",
-                     "ctl_wgrad_bias_partial_floats", "ctl_latent_score_ws_floats", "ctl_latent_mask_apply_ws_floats",
-                     "ctl_rescale_intensity_ws_floats", "ctl_sizeof_op", "ctl_sizeof_conv", "ctl_latent_mask_fused_ws_floats", "ctl_conv_wpack_floats_x3",
-                     "ctl_surface_stats_ws_bytes", "ctl_surface_map_ws_bytes", "ctl_cc_ws_bytes", "ctl_aug_ws_bytes", "ctl_aug_warp_ws_bytes",
-                     "ctl_surface_quantiles_ws_bytes",
-                     "ctl_aug_spline_ws_bytes", "ctl_aug_warp_cubic_ws_bytes", "ctl_aug_bias_ws_bytes", "ctl_order_stats_ws_bytes", "ctl_corrupt_spike_ws_bytes",
-                     "ctl_seg_loss_ws_doubles"):
-            getattr(lib, name).restype = C.c_size_t
-        p, i32, i64, f32, u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64
-        sig = {
-            "ctl_conv_wpack_floats": [i32, i32, i32],
-            "ctl_conv_stats_floats": [p], "ctl_conv_stats_blocks": [p],
-            "ctl_wgrad_splits": [p], "ctl_wgrad_partial_floats": [p], "ctl_wgrad_bias_partial_floats": [p],
-            "ctl_pack_weights": [p, p, i32, i32, i32, i64, i64, i64, i64, i32, p],
-            "ctl_conv_forward": [p] * 12, "ctl_conv_forward_ex": [p] * 16, "ctl_conv_pool_ok": [p],
-            "ctl_conv_wgrad": [p] * 8, "ctl_conv_wgrad_ex": [p] * 10,
-            "ctl_wgrad_group_class": [p, i32], "ctl_wgrad_group_plan": [p, i32, p], "ctl_conv_wgrad_group": [i32] + [p] * 11,
-            "ctl_wgrad_reduce": [p, p, p, p, i64, i64, i64, i64, p, i32, p],
-            "ctl_confusion_hist": [p, p, i64, i32, p, p],
-            "ctl_rescale_intensity": [p, p, p, i32, i64, f32, f32, f32, p],
-            "ctl_noise_clamp": [p, p, u64, f32, f32, f32, p, i64, p],
-            "ctl_rescale_intensity_ws_floats": [i32],
-            "ctl_crop_or_pad": [p, p, i32, i32, i32, i32, i32, i32, p],
-            "ctl_bn_finalize": [p, i32, i32, i64, p, p, f32, f32, i32, p, p, p, p, p, p, p, i32, p],
-            "ctl_bn_finalize_ex": [p, i32, i32, i64, p, p, f32, f32, i32, p, p, p, p, p, p, p, p, i32, p],
-            "ctl_bn_replay_running": [p, p, p, p, i32, f32, p],
-            "ctl_bn_eval_coeffs": [i32, p, p, p, p, f32, p, p, i32, p],
-            "ctl_bn_act": [p, p, p, f32, p, i64, i32, i32, p],
-            "ctl_bwd_reduce": [i32, p, p, p, p, p, f32, i64, i32, p, i32, p], "ctl_red_blocks": [],
-            "ctl_bn_bwd_finalize": [p, i32, i64, p, p, p, p, p, p, i32, i32, i32, p],
-            "ctl_bn_bwd_finalize_ex": [p, i32, i64, p, p, p, p, p, p, i32, i32, i32, C.c_uint32, p],
-            "ctl_bwd_apply": [i32, p, p, p, p, p, f32, p, i64, i32, p, p, i32, p],
-            "ctl_chan_sum_finalize": [p, i32, p, i32, p],
-            "ctl_sumpool2": [p, p, i32, i32, i32, i32, i32, p],
-            "ctl_sigmoid_bwd": [p, p, p, i64, p],
-            "ctl_softmax_t_fwd": [p, f32, p, i64, i32, p],
-            "ctl_softmax_t_bwd": [p, p, f32, p, i64, i32, p],
-            "ctl_onehot": [p, p, i64, i32, p],
-            "ctl_ce2d_fwd": [p, p, i64, i32, p, p, p],
-            "ctl_ce2d_bwd": [p, p, p, i64, i32, p, p],
-            "ctl_mse_fwd": [p, p, i64, f32, p, p, p],
-            "ctl_mse_bwd": [p, p, p, i64, f32, p, p],
-            "ctl_argmax_c": [p, p, i64, i32, p],
-            "ctl_latent_score_ws_floats": [i32, i32, i32, i32],
-            "ctl_latent_score": [i32, p, p, p, i32, i32, i32, p],
-            "ctl_latent_mask_apply": [i32, p, p, p, i32, p, p, p, p, i32, i32, i32, p],
-            "ctl_latent_mask_apply_ws_floats": [i32, i32, i32, i32],
-            "ctl_latent_mask_fused_ws_floats": [i32, i32, i32, i32],
-            "ctl_latent_mask_fused": [i32, p, p, p, i32, p, p, p, p, p, i32, i32, i32, p],
-            "ctl_dropout2d": [p, p, u64, f32, p, p, i32, i32, i32, p],
-            "ctl_uniform": [p, i64, u64, p],
-            "ctl_step_tick": [p, p],
-            "ctl_spin": [i32, p],
-            "ctl_dropout2d_ex": [p, p, u64, p, f32, p, p, p, i32, i32, i32, p],
-            "ctl_dropout2d_dt": [p, p, u64, p, f32, p, p, i32, i32, i32, C.c_uint32, p],
-            "ctl_uniform_dev": [p, i64, u64, p, p],
-            "ctl_adam_dev": [p, p, p, p, i64, f32, f32, f32, f32, p, f32, p],
-            "ctl_adam": [p, p, p, p, i64, f32, f32, f32, f32, i32, f32, p],
-            "ctl_accumulate": [p, p, i32, i64, p],
-            "ctl_plan_run": [p, i32, p, i32, p],
-            "ctl_prof_start": [C.c_char_p], "ctl_prof_start_sampled": [C.c_char_p, i32], "ctl_prof_stop": [p, C.c_size_t],
-            "ctl_pack_weights_batched": [p, p, p, i32, i64, p], "ctl_wgrad_reduce_batched": [p, p, p, i32, i64, p],
-            "ctl_pack_weights_bf16_batched": [p, p, p, i32, i64, p],
-            "ctl_pack_weights_x3_batched": [p, p, p, i32, i64, p], "ctl_conv_wpack_floats_x3": [i32, i32, i32],
-            "ctl_bwd_reduce_rows": [i32, i64, i32],
-            "ctl_bn_act_dt": [p, p, p, f32, p, i64, i32, i32, C.c_uint32, p],
-            "ctl_bwd_reduce_dt": [i32, p, p, p, p, p, f32, i64, i32, p, i32, C.c_uint32, p, p],
-            "ctl_bwd_apply_dt": [i32, p, p, p, p, p, f32, p, i64, i32, p, p, i32, C.c_uint32, p],
-            "ctl_sumpool2_dt": [p, p, i32, i32, i32, i32, i32, C.c_uint32, p],
-            "ctl_surface_stats_rows": [i32, i32, i32, i32], "ctl_surface_stats_ws_bytes": [i32] * 6,
-            "ctl_surface_stats": [p, p, i32, i32, i32, i32, i32, i32, i32, p, p, p, C.c_size_t, p],
-            "ctl_surface_map_ws_bytes": [i32] * 4,
-            "ctl_surface_quantiles_ws_bytes": [i32] * 7,
-            "ctl_surface_quantiles": [p, p, i32, i32, i32, i32, i32, i32, i32, p, p, i32, p, p, p, C.c_size_t, p],
-            "ctl_surface_map": [p, i32, i32, i32, i32, i32, p, p, p, p, C.c_size_t, p],
-            "ctl_cc_ws_bytes": [i32] * 5, "ctl_cc_label": [p, i32, i32, i32, i32, i32, i32, p, p],
-            "ctl_cc_keep_largest": [p, i32, i32, i32, i32, i32, i32, p, p, p, C.c_size_t, p],
-            "ctl_aug_ws_bytes": [i32] * 3, "ctl_aug_warp_ws_bytes": [i32] * 5, "ctl_aug_field": [p, p, p, p, i32, i32, i32, p, p, C.c_size_t, p],
-            "ctl_aug_warp": [p, p, p, p, p, i32, i32, i32, i32, i32, p, p, p, C.c_size_t, p],
-            "ctl_aug_spline_ws_bytes": [i32] * 4, "ctl_aug_warp_cubic_ws_bytes": [i32] * 6,
-            "ctl_aug_spline_coeffs": [p, p, p, i32, i32, i32, i32, p, p, C.c_size_t, p],
-            "ctl_aug_warp_cubic": [p, p, p, p, p, i32, i32, i32, i32, i32, i32, p, p, p, C.c_size_t, p],
-            "ctl_aug_bias_ws_bytes": [i32] * 3, "ctl_aug_bias": [p, p, p, p, i32, i32, i32, p, p, C.c_size_t, p],
-            "ctl_aug_coarse_field": [p, i32, i32, i32, p, p],
-            "ctl_order_stats_ws_bytes": [i32, i32], "ctl_order_stats": [p, i32, i64, p, i32, p, p, C.c_size_t, p],
-            "ctl_percentile_apply": [p, p, i32, i64, C.c_double, C.c_double, i32, f32, f32, p, p, p],
-            "ctl_resample_inplane": [p, p, i32, i32, i32, i32, i32, i32, C.c_double, C.c_double, p, p, p],
-            "ctl_restore_scores": [p, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.c_double, C.c_double, i32, p, p, p],
-            "ctl_restore_labels": [p, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.c_double, C.c_double, p, p],
-            "ctl_corrupt_bias": [p, p, i32, i32, i32, p, p], "ctl_corrupt_spike_ws_bytes": [i32] * 4,
-            "ctl_corrupt_spike": [p, i32, i32, i32, p, p, i32, C.c_double, p, p, C.c_size_t, p],
-            "ctl_corrupt_rigid3d": [p, i32, i32, i32, p, i32, p, p], "ctl_axis_operator": [p, p, i32, i32, i32, i32, i32, p, p, p],
-            "ctl_slice_foreground": [p, p, i32, i64, p, p],
-            "ctl_batch_gather": [p, p, p, i32, i64, p, i32, p, i32, i32, p, p, i32, i32, p, p, p],
-            "ctl_seg_loss_blocks": [i32, i64], "ctl_seg_loss_ws_doubles": [i32, i32, i64, i32],
-            "ctl_seg_loss_fwd": [i32, p, p, p, f32, i32, i64, i32, p, p, p],
-            "ctl_seg_loss_bwd": [i32, p, p, p, f32, p, p, i32, i64, i32, p, p],
-        }
-        for name, args in sig.items():
-            getattr(lib, name).argtypes = args
+        for name, (restype, argtypes) in SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
         if lib.ctl_version() != ABI_VERSION or lib.ctl_sizeof_op() != OP_DTYPE.itemsize or lib.ctl_sizeof_conv() != CONV_DTYPE.itemsize:
             raise CtlError(f"ABI mismatch: library version {lib.ctl_version()} vs binding {ABI_VERSION}, sizeof(ctl_op)={lib.ctl_sizeof_op()} "
                            f"vs {OP_DTYPE.itemsize}, sizeof(ctl_conv)={lib.ctl_sizeof_conv()} vs {CONV_DTYPE.itemsize}")
@@ -170,39 +198,16 @@ class _Lib:
 
 lib = _Lib()
 
-# every symbol include/ctl_hip.h declares (checked by tests/test_cabi.py without a GPU)
-EXPORTED = ["ctl_version", "ctl_last_error", "ctl_conv_wpack_floats", "ctl_conv_stats_floats", "ctl_conv_stats_blocks",
-            "ctl_pack_weights", "ctl_conv_forward", "ctl_conv_forward_ex", "ctl_conv_pool_ok", "ctl_wgrad_splits", "ctl_wgrad_partial_floats",
-            "ctl_wgrad_bias_partial_floats", "ctl_conv_wgrad", "ctl_conv_wgrad_ex", "ctl_wgrad_reduce", "ctl_bn_finalize", "ctl_bn_finalize_ex", "ctl_bn_replay_running", "ctl_bn_eval_coeffs",
-            "ctl_bn_act", "ctl_bwd_reduce", "ctl_bn_bwd_finalize", "ctl_bn_bwd_finalize_ex", "ctl_bwd_apply", "ctl_chan_sum_finalize", "ctl_sumpool2",
-            "ctl_sigmoid_bwd", "ctl_softmax_t_fwd", "ctl_softmax_t_bwd", "ctl_onehot", "ctl_ce2d_fwd", "ctl_ce2d_bwd",
-            "ctl_mse_fwd", "ctl_mse_bwd", "ctl_argmax_c", "ctl_latent_score_ws_floats", "ctl_latent_score",
-            "ctl_latent_mask_apply", "ctl_latent_mask_apply_ws_floats", "ctl_dropout2d", "ctl_uniform", "ctl_adam", "ctl_plan_run", "ctl_sizeof_op",
-            "ctl_sizeof_conv", "ctl_prof_start", "ctl_prof_start_sampled", "ctl_prof_stop", "ctl_pack_weights_batched",
-            "ctl_wgrad_reduce_batched", "ctl_confusion_hist", "ctl_rescale_intensity_ws_floats", "ctl_rescale_intensity",
-            "ctl_noise_clamp", "ctl_crop_or_pad", "ctl_step_tick", "ctl_spin", "ctl_dropout2d_ex", "ctl_dropout2d_dt", "ctl_uniform_dev", "ctl_adam_dev",
-            "ctl_latent_mask_fused_ws_floats", "ctl_latent_mask_fused", "ctl_accumulate", "ctl_pack_weights_bf16_batched",
-            "ctl_bn_act_dt", "ctl_bwd_reduce_dt", "ctl_bwd_apply_dt", "ctl_sumpool2_dt", "ctl_bwd_reduce_rows", "ctl_red_blocks",
-            "ctl_launch_count", "ctl_conv_wpack_floats_x3", "ctl_pack_weights_x3_batched", "ctl_wgrad_group_class", "ctl_wgrad_group_plan",
-            "ctl_conv_wgrad_group", "ctl_surface_stats_rows", "ctl_surface_stats_ws_bytes", "ctl_surface_stats", "ctl_surface_map_ws_bytes",
-            "ctl_surface_map", "ctl_cc_ws_bytes", "ctl_cc_label", "ctl_cc_keep_largest", "ctl_aug_ws_bytes", "ctl_aug_warp_ws_bytes", "ctl_aug_field",
-            "ctl_aug_warp", "ctl_aug_spline_ws_bytes", "ctl_aug_warp_cubic_ws_bytes", "ctl_aug_spline_coeffs", "ctl_aug_warp_cubic",
-            "ctl_aug_bias_ws_bytes", "ctl_aug_bias", "ctl_aug_coarse_field", "ctl_order_stats_ws_bytes", "ctl_order_stats",
-            "ctl_percentile_apply", "ctl_resample_inplane", "ctl_corrupt_bias", "ctl_corrupt_spike_ws_bytes", "ctl_corrupt_spike",
-            "ctl_corrupt_rigid3d", "ctl_axis_operator", "ctl_slice_foreground", "ctl_batch_gather", "ctl_surface_quantiles_ws_bytes",
-            "ctl_surface_quantiles", "ctl_restore_scores", "ctl_restore_labels", "ctl_seg_loss_blocks", "ctl_seg_loss_ws_doubles",
-            "ctl_seg_loss_fwd", "ctl_seg_loss_bwd"]
-
 
 def prof_start(kernel_filter: str = "", every: int = 1) -> None:
     """Bracket the launches whose id contains `kernel_filter` with HIP events on their own stream (every `every`-th one)."""
-    check(lib.ctl_prof_start_sampled(kernel_filter.encode(), int(every)), "ctl_prof_start_sampled")
+    call("ctl_prof_start_sampled", kernel_filter.encode(), int(every))
 
 
 def prof_stop() -> dict:
     """{kernel id: dict(launches, ms, flops, bytes)} for the launches bracketed since prof_start."""
     buf = C.create_string_buffer(1 << 18)
-    check(lib.ctl_prof_stop(buf, len(buf)), "ctl_prof_stop")
+    call("ctl_prof_stop", buf, len(buf))
     out = {}
     for line in buf.value.decode().splitlines():
         parts = line.split()
@@ -214,6 +219,11 @@ def check(rc: int, what: str = "") -> None:
     if rc != 0:
         msg = lib.ctl_last_error()
         raise CtlError(f"{what} failed (rc={rc}): {msg.decode() if msg else ''}")
+
+
+def call(name: str, *args) -> None:
+    """Call the status-returning entry `name`; a non-zero status raises CtlError naming that entry."""
+    check(getattr(lib, name)(*args), name)
 
 
 def conv_desc(**kw) -> np.ndarray:

@@ -206,7 +206,7 @@ def compose_matrix(flip, theta, translate, zoom, choice, hp: int, wp: int, shear
 
 # ---------------------------------------------------------------------------------------------- host statement of the semantics
 def _mix(z: np.ndarray) -> np.ndarray:
-    """splitmix64 finaliser on uint64 arrays (aug_mix of csrc/ctl_aug.hip)."""
+    """splitmix64 finaliser on uint64 arrays (ctl_mix64 of csrc/ctl_device.h)."""
     with np.errstate(over="ignore"):
         z = z + np.uint64(0x9E3779B97F4A7C15)
         z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)

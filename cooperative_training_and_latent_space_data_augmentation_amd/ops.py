@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _ffi
-from ._ffi import lib, check
+from ._ffi import lib, call
 
 
 def stream_ptr() -> int:
@@ -47,13 +47,41 @@ def as_nhwc_any(x: torch.Tensor) -> torch.Tensor:
     return x.contiguous(memory_format=torch.channels_last)
 
 
+def _arg(t: torch.Tensor, dtype, shape, who: str, name: str, dense: bool = False, on_device: bool = False) -> None:
+    """ValueError unless the tensor argument `name` of `who` has `dtype` (one, or a tuple to choose from) and `shape` (None: any size on
+    that axis), is contiguous (dense) and sits on the device (on_device)."""
+    dtypes = dtype if isinstance(dtype, tuple) else (dtype,)
+    fits = t.dim() == len(shape) and all(want is None or want == got for want, got in zip(shape, t.shape))
+    if t.dtype not in dtypes or not fits or (dense and not t.is_contiguous()) or (on_device and not t.is_cuda):
+        kind = ("a contiguous " if dense else "a ") + " or ".join(str(v).replace("torch.", "") for v in dtypes) + (" device" if on_device else "")
+        dims = ",".join("*" if v is None else str(int(v)) for v in shape)
+        raise ValueError(f"{who}: {name} must be {kind} tensor [{dims}], got {t.dtype} {tuple(t.shape)}"
+                         f"{'' if t.is_contiguous() else ' (strided)'}{'' if t.is_cuda else ' on the host'}")
+
+
+def _out(out: Optional[torch.Tensor], dtype, shape, device, who: str, name: str = "out", on_device: bool = True, not_input=None) -> torch.Tensor:
+    """A caller-supplied output: a new tensor when None, else it must be a contiguous `dtype` tensor of `shape` (ValueError), on the device
+    unless the wrapper leaves that to require_gpu (on_device=False), and not the tensor `not_input`."""
+    if out is None:
+        return torch.empty(tuple(shape), dtype=dtype, device=device)
+    _arg(out, dtype, tuple(shape), who, f"`{name}`", dense=True, on_device=on_device)
+    if not_input is not None and out.data_ptr() == not_input.data_ptr():
+        raise ValueError(f"{who}: `{name}` must not be the input")
+    return out
+
+
+def _workspace(query: str, *dims, device, dtype=torch.uint8, floor: int = 1):
+    """(tensor, size) for the library's size query `query(*dims)`: a `dtype` device tensor of max(size, floor) elements."""
+    size = getattr(lib, query)(*dims)
+    return torch.empty(max(size, floor), dtype=dtype, device=device), size
+
+
 # ---------------------------------------------------------------------------------------------- conv (unit-level API)
 def pack_weights(src: torch.Tensor, cout: int, cin: int, ks: int, strides, flip: bool, src_offset: int = 0) -> torch.Tensor:
     require_gpu(src)
     n = lib.ctl_conv_wpack_floats(cin, cout, ks)
     dst = torch.empty(n, dtype=torch.float32, device=src.device)
-    check(lib.ctl_pack_weights(src.data_ptr() + 4 * src_offset, dst.data_ptr(), cout, cin, ks, *[int(s) for s in strides],
-                               int(flip), stream_ptr()), "ctl_pack_weights")
+    call("ctl_pack_weights", src.data_ptr() + 4 * src_offset, dst.data_ptr(), cout, cin, ks, *[int(s) for s in strides], int(flip), stream_ptr())
     return dst
 
 
@@ -75,7 +103,7 @@ def pack_weights_bf16(w: torch.Tensor, cout: int, cin: int, ks: int, strides, fl
     table = torch.tensor([[0, 0, cout, cin, ks, int(flip), *[int(v) for v in strides], total, mode]], dtype=torch.int64, device=w.device)
     dst = torch.zeros(total, dtype=torch.float32, device=w.device)
     src = w.contiguous().float()
-    check(lib.ctl_pack_weights_bf16_batched(src.data_ptr(), dst.data_ptr(), table.data_ptr(), 1, total, stream_ptr()), "ctl_pack_weights_bf16_batched")
+    call("ctl_pack_weights_bf16_batched", src.data_ptr(), dst.data_ptr(), table.data_ptr(), 1, total, stream_ptr())
     return dst
 
 
@@ -87,7 +115,7 @@ def pack_weights_x3(w: torch.Tensor, cout: int, cin: int, ks: int, strides, flip
     table = torch.tensor([[0, 0, cout, cin, ks, int(flip), *[int(v) for v in strides], total, mode | _ffi.PACK_X3]], dtype=torch.int64, device=w.device)
     dst = torch.zeros(total, dtype=torch.float32, device=w.device)
     src = w.contiguous().float()
-    check(lib.ctl_pack_weights_x3_batched(src.data_ptr(), dst.data_ptr(), table.data_ptr(), 1, total, stream_ptr()), "ctl_pack_weights_x3_batched")
+    call("ctl_pack_weights_x3_batched", src.data_ptr(), dst.data_ptr(), table.data_ptr(), 1, total, stream_ptr())
     return dst
 
 
@@ -132,8 +160,8 @@ def conv_forward(d: np.ndarray, x, wpack, bias=None, pro_scale=None, pro_shift=N
     stats = None
     if want_stats:
         stats = torch.empty(lib.ctl_conv_stats_floats(_ffi.desc_ptr(d)), dtype=torch.float32, device=x.device)
-    check(lib.ctl_conv_forward_ex(_ffi.desc_ptr(d), ptr(x), ptr(wpack), ptr(bias), ptr(pro_scale), ptr(pro_shift), ptr(res),
-                                  ptr(res_scale), ptr(res_shift), ptr(res2), ptr(x2), ptr(y), ptr(stats), ptr(pool), ptr(xout), stream_ptr()), "ctl_conv_forward")
+    call("ctl_conv_forward_ex", _ffi.desc_ptr(d), ptr(x), ptr(wpack), ptr(bias), ptr(pro_scale), ptr(pro_shift), ptr(res),
+         ptr(res_scale), ptr(res_shift), ptr(res2), ptr(x2), ptr(y), ptr(stats), ptr(pool), ptr(xout), stream_ptr())
     return y, stats
 
 
@@ -149,10 +177,8 @@ def conv_wgrad(d: np.ndarray, x, dy, dw: torch.Tensor, strides, dbias: Optional[
     dp = _ffi.desc_ptr(d)
     wpart = torch.empty(lib.ctl_wgrad_partial_floats(dp), dtype=torch.float32, device=x.device)
     bpart = torch.empty(lib.ctl_wgrad_bias_partial_floats(dp), dtype=torch.float32, device=x.device) if dbias is not None else None
-    check(lib.ctl_conv_wgrad_ex(dp, ptr(x), ptr(pro_scale), ptr(pro_shift), ptr(dy), ptr(dy2), ptr(dy_coef), ptr(wpart), ptr(bpart),
-                                stream_ptr()), "ctl_conv_wgrad")
-    check(lib.ctl_wgrad_reduce(dp, ptr(wpart), ptr(bpart), ptr(dw), *[int(s) for s in strides], ptr(dbias), int(accumulate),
-                               stream_ptr()), "ctl_wgrad_reduce")
+    call("ctl_conv_wgrad_ex", dp, ptr(x), ptr(pro_scale), ptr(pro_shift), ptr(dy), ptr(dy2), ptr(dy_coef), ptr(wpart), ptr(bpart), stream_ptr())
+    call("ctl_wgrad_reduce", dp, ptr(wpart), ptr(bpart), ptr(dw), *[int(s) for s in strides], ptr(dbias), int(accumulate), stream_ptr())
     return dw, dbias
 
 
@@ -162,16 +188,16 @@ def bn_finalize(partial, c, count, gamma, beta, eps=1e-5, momentum=0.1, running_
     dev = partial.device
     scale, shift, mean, invstd = (torch.empty(groups * c, dtype=torch.float32, device=dev) for _ in range(4))
     blocks = partial.numel() // (2 * c * groups)
-    check(lib.ctl_bn_finalize(ptr(partial), blocks, c, count, ptr(gamma), ptr(beta), eps, momentum,
-                              int(running_mean is not None), ptr(running_mean), ptr(running_var), ptr(nbt), ptr(scale),
-                              ptr(shift), ptr(mean), ptr(invstd), groups, stream_ptr()), "ctl_bn_finalize")
+    call("ctl_bn_finalize", ptr(partial), blocks, c, count, ptr(gamma), ptr(beta), eps, momentum,
+         int(running_mean is not None), ptr(running_mean), ptr(running_var), ptr(nbt), ptr(scale),
+         ptr(shift), ptr(mean), ptr(invstd), groups, stream_ptr())
     return scale, shift, mean, invstd
 
 
 def bn_act(x, scale, shift, slope, groups=1):
     y = torch.empty_like(x)
     n, c, h, w = x.shape
-    check(lib.ctl_bn_act(ptr(x), ptr(scale), ptr(shift), slope, ptr(y), n * h * w, c, groups, stream_ptr()), "ctl_bn_act")
+    call("ctl_bn_act", ptr(x), ptr(scale), ptr(shift), slope, ptr(y), n * h * w, c, groups, stream_ptr())
     return y
 
 
@@ -180,14 +206,14 @@ def softmax_t_fwd(x: torch.Tensor, temperature: float = 2.0) -> torch.Tensor:
     require_gpu(x)
     n, c, h, w = x.shape
     p = torch.empty_like(x)
-    check(lib.ctl_softmax_t_fwd(ptr(x), 1.0 / temperature, ptr(p), n * h * w, c, stream_ptr()), "ctl_softmax_t_fwd")
+    call("ctl_softmax_t_fwd", ptr(x), 1.0 / temperature, ptr(p), n * h * w, c, stream_ptr())
     return p
 
 
 def softmax_t_bwd(p, dp, temperature: float = 2.0):
     n, c, h, w = p.shape
     dx = torch.empty_like(p)
-    check(lib.ctl_softmax_t_bwd(ptr(p), ptr(dp), 1.0 / temperature, ptr(dx), n * h * w, c, stream_ptr()), "ctl_softmax_t_bwd")
+    call("ctl_softmax_t_bwd", ptr(p), ptr(dp), 1.0 / temperature, ptr(dx), n * h * w, c, stream_ptr())
     return dx
 
 
@@ -196,7 +222,7 @@ def onehot(label: torch.Tensor, c: int) -> torch.Tensor:
     label = label.long().contiguous()
     n, h, w = label.shape
     y = empty_nhwc(n, c, h, w, label.device)
-    check(lib.ctl_onehot(ptr(label), ptr(y), n * h * w, c, stream_ptr()), "ctl_onehot")
+    call("ctl_onehot", ptr(label), ptr(y), n * h * w, c, stream_ptr())
     return y
 
 
@@ -204,14 +230,14 @@ def ce2d_fwd(logit, label):
     n, c, h, w = logit.shape
     partial = torch.empty(_ffi.RED_BLOCKS, dtype=torch.float64, device=logit.device)
     loss = torch.empty((), dtype=torch.float32, device=logit.device)
-    check(lib.ctl_ce2d_fwd(ptr(logit), ptr(label), n * h * w, c, ptr(partial), ptr(loss), stream_ptr()), "ctl_ce2d_fwd")
+    call("ctl_ce2d_fwd", ptr(logit), ptr(label), n * h * w, c, ptr(partial), ptr(loss), stream_ptr())
     return loss
 
 
 def ce2d_bwd(logit, label, gout):
     n, c, h, w = logit.shape
     d = torch.empty_like(logit)
-    check(lib.ctl_ce2d_bwd(ptr(logit), ptr(label), ptr(gout), n * h * w, c, ptr(d), stream_ptr()), "ctl_ce2d_bwd")
+    call("ctl_ce2d_bwd", ptr(logit), ptr(label), ptr(gout), n * h * w, c, ptr(d), stream_ptr())
     return d
 
 
@@ -244,7 +270,7 @@ def seg_loss_fwd(logit, label, kind, class_weights=None, gamma=2.0):
     k, n, hw, c, wts = _loss_args(logit, label, kind, class_weights)
     ws = torch.empty(max(1, lib.ctl_seg_loss_ws_doubles(k, n, hw, c)), dtype=torch.float64, device=logit.device)
     loss = torch.empty((), dtype=torch.float32, device=logit.device)
-    check(lib.ctl_seg_loss_fwd(k, ptr(logit), ptr(label), wts, gamma, n, hw, c, ptr(ws), ptr(loss), stream_ptr()), "ctl_seg_loss_fwd")
+    call("ctl_seg_loss_fwd", k, ptr(logit), ptr(label), wts, gamma, n, hw, c, ptr(ws), ptr(loss), stream_ptr())
     return loss, ws
 
 
@@ -253,20 +279,20 @@ def seg_loss_bwd(logit, label, kind, gout, ws=None, class_weights=None, gamma=2.
     k, n, hw, c, wts = _loss_args(logit, label, kind, class_weights)
     require_gpu(gout, ws)
     d = torch.empty_like(logit)
-    check(lib.ctl_seg_loss_bwd(k, ptr(logit), ptr(label), wts, gamma, ptr(gout), ptr(ws), n, hw, c, ptr(d), stream_ptr()), "ctl_seg_loss_bwd")
+    call("ctl_seg_loss_bwd", k, ptr(logit), ptr(label), wts, gamma, ptr(gout), ptr(ws), n, hw, c, ptr(d), stream_ptr())
     return d
 
 
 def mse_fwd(a, b, scale):
     partial = torch.empty(_ffi.RED_BLOCKS, dtype=torch.float64, device=a.device)
     loss = torch.empty((), dtype=torch.float32, device=a.device)
-    check(lib.ctl_mse_fwd(ptr(a), ptr(b), a.numel(), scale, ptr(partial), ptr(loss), stream_ptr()), "ctl_mse_fwd")
+    call("ctl_mse_fwd", ptr(a), ptr(b), a.numel(), scale, ptr(partial), ptr(loss), stream_ptr())
     return loss
 
 
 def mse_bwd(a, b, gout, scale):
     d = torch.empty_like(a)
-    check(lib.ctl_mse_bwd(ptr(a), ptr(b), ptr(gout), a.numel(), scale, ptr(d), stream_ptr()), "ctl_mse_bwd")
+    call("ctl_mse_bwd", ptr(a), ptr(b), ptr(gout), a.numel(), scale, ptr(d), stream_ptr())
     return d
 
 
@@ -275,7 +301,7 @@ def argmax_c(logit: torch.Tensor) -> torch.Tensor:
     logit = as_nhwc(logit)
     n, c, h, w = logit.shape
     out = torch.empty((n, h, w), dtype=torch.uint8, device=logit.device)
-    check(lib.ctl_argmax_c(ptr(logit), ptr(out), n * h * w, c, stream_ptr()), "ctl_argmax_c")
+    call("ctl_argmax_c", ptr(logit), ptr(out), n * h * w, c, stream_ptr())
     return out
 
 
@@ -287,9 +313,8 @@ def latent_score(grad: torch.Tensor, mode: int) -> torch.Tensor:
     n, c, h, w = grad.shape
     L = c if mode == 0 else h * w
     score = torch.empty((n, L), dtype=torch.float32, device=grad.device)
-    ws = lib.ctl_latent_score_ws_floats(mode, n, h * w, c)
-    scratch = torch.empty(max(ws, 1), dtype=torch.float32, device=grad.device)
-    check(lib.ctl_latent_score(mode, ptr(grad), ptr(score), ptr(scratch), n, h * w, c, stream_ptr()), "ctl_latent_score")
+    scratch, _ = _workspace("ctl_latent_score_ws_floats", mode, n, h * w, c, device=grad.device, dtype=torch.float32)
+    call("ctl_latent_score", mode, ptr(grad), ptr(score), ptr(scratch), n, h * w, c, stream_ptr())
     return score
 
 
@@ -307,8 +332,8 @@ def latent_mask_apply(code: torch.Tensor, score: torch.Tensor, mode: int, k, sof
         soft_noise = soft_noise.reshape(n, L).float().contiguous()
     ws = lib.ctl_latent_mask_apply_ws_floats(mode, n, h * w, c)
     scratch = torch.empty(ws, dtype=torch.float32, device=code.device) if ws else None
-    check(lib.ctl_latent_mask_apply(mode, ptr(code), ptr(score), ptr(soft_noise), k_host, ptr(k_dev), ptr(masked), ptr(mask),
-                                    ptr(scratch), n, h * w, c, stream_ptr()), "ctl_latent_mask_apply")
+    call("ctl_latent_mask_apply", mode, ptr(code), ptr(score), ptr(soft_noise), k_host, ptr(k_dev), ptr(masked), ptr(mask),
+         ptr(scratch), n, h * w, c, stream_ptr())
     return masked, (mask.view(n, c, 1, 1) if mode == 0 else mask.view(n, 1, h, w))
 
 
@@ -331,8 +356,8 @@ def latent_mask(grad: torch.Tensor, code: torch.Tensor, mode: int, k, soft_noise
         soft_noise = soft_noise.reshape(n, L).float().contiguous()
     need = lib.ctl_latent_mask_fused_ws_floats(mode, n, h * w, c)
     ws = torch.empty(need, dtype=torch.float32, device=code.device) if need else None
-    check(lib.ctl_latent_mask_fused(mode, ptr(grad), ptr(code), ptr(soft_noise), k_host, ptr(k_dev), ptr(masked), ptr(mask), ptr(score),
-                                    ptr(ws), n, h * w, c, stream_ptr()), "ctl_latent_mask_fused")
+    call("ctl_latent_mask_fused", mode, ptr(grad), ptr(code), ptr(soft_noise), k_host, ptr(k_dev), ptr(masked), ptr(mask), ptr(score),
+         ptr(ws), n, h * w, c, stream_ptr())
     mask = mask.view(n, c, 1, 1) if mode == 0 else mask.view(n, 1, h, w)
     return (masked, mask, score) if want_score else (masked, mask)
 
@@ -350,17 +375,16 @@ def dropout2d(z: torch.Tensor, p: float, keep: Optional[torch.Tensor] = None, se
     mask = torch.empty_like(z) if want_mask else None
     if keep is not None:
         keep = keep.reshape(n, c).float().contiguous()
-    check(lib.ctl_dropout2d_ex(ptr(z), ptr(keep), seed & (2 ** 64 - 1), ptr(state), p, ptr(out), ptr(keep_out), ptr(mask), n, h * w, c,
-                               stream_ptr()), "ctl_dropout2d_ex")
+    call("ctl_dropout2d_ex", ptr(z), ptr(keep), seed & (2 ** 64 - 1), ptr(state), p, ptr(out), ptr(keep_out), ptr(mask), n, h * w, c, stream_ptr())
     return (out, keep_out, mask) if want_mask else (out, keep_out)
 
 
 def uniform(shape, device, seed: int, state: Optional[torch.Tensor] = None) -> torch.Tensor:
     out = torch.empty(shape, dtype=torch.float32, device=device)
     if state is not None:
-        check(lib.ctl_uniform_dev(ptr(out), out.numel(), seed & (2 ** 64 - 1), ptr(state), stream_ptr()), "ctl_uniform_dev")
+        call("ctl_uniform_dev", ptr(out), out.numel(), seed & (2 ** 64 - 1), ptr(state), stream_ptr())
     else:
-        check(lib.ctl_uniform(ptr(out), out.numel(), seed & (2 ** 64 - 1), stream_ptr()), "ctl_uniform")
+        call("ctl_uniform", ptr(out), out.numel(), seed & (2 ** 64 - 1), stream_ptr())
     return out
 
 
@@ -368,17 +392,15 @@ def step_tick(state: torch.Tensor) -> None:
     """Advance the device-resident step state (RNG counter, Adam step): one launch at the head of a graph-replayed step."""
     require_gpu(state)
     assert state.dtype == torch.int64 and state.numel() >= 3
-    check(lib.ctl_step_tick(ptr(state), stream_ptr()), "ctl_step_tick")
+    call("ctl_step_tick", ptr(state), stream_ptr())
 
 
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0, state: Optional[torch.Tensor] = None):
     require_gpu(p, g, m, v)
     if state is not None:       # step count read from state[2] on the device
-        check(lib.ctl_adam_dev(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, beta1, beta2, eps, ptr(state), grad_scale, stream_ptr()),
-              "ctl_adam_dev")
+        call("ctl_adam_dev", ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, beta1, beta2, eps, ptr(state), grad_scale, stream_ptr())
     else:
-        check(lib.ctl_adam(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, beta1, beta2, eps, step, grad_scale, stream_ptr()),
-              "ctl_adam")
+        call("ctl_adam", ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, beta1, beta2, eps, step, grad_scale, stream_ptr())
 
 
 # ---------------------------------------------------------------------------------------------- SURVEY 8(f): metrics + input pipeline
@@ -391,7 +413,7 @@ def confusion_hist(label_true: torch.Tensor, label_pred: torch.Tensor, n_class: 
         raise ValueError("confusion_hist: label_true and label_pred differ in size")
     if hist is None:
         hist = torch.zeros((n_class, n_class), dtype=torch.int64, device=lt.device)
-    check(lib.ctl_confusion_hist(ptr(lt), ptr(lp), lt.numel(), n_class, ptr(hist), stream_ptr()), "ctl_confusion_hist")
+    call("ctl_confusion_hist", ptr(lt), ptr(lp), lt.numel(), n_class, ptr(hist), stream_ptr())
     return hist
 
 
@@ -425,12 +447,11 @@ def surface_stats(pred: torch.Tensor, gt: torch.Tensor, n_class: int, sampling=N
     samp = _surface_sampling(sampling, mode)
     rows = lib.ctl_surface_stats_rows(d, n_class, int(foreground_only), mode)
     if rows < 0:
-        check(rows, "ctl_surface_stats_rows")
+        _ffi.check(rows, "ctl_surface_stats_rows")
     table = torch.empty((rows, 4), dtype=torch.float64, device=p.device)
-    nbytes = lib.ctl_surface_stats_ws_bytes(d, h, w, n_class, int(foreground_only), mode)
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=p.device)
-    check(lib.ctl_surface_stats(ptr(p), ptr(g), d, h, w, n_class, int(foreground_only), mode, int(connectivity), samp, ptr(table), ptr(ws),
-                                nbytes, stream_ptr()), "ctl_surface_stats")
+    ws, nbytes = _workspace("ctl_surface_stats_ws_bytes", d, h, w, n_class, int(foreground_only), mode, device=p.device)
+    call("ctl_surface_stats", ptr(p), ptr(g), d, h, w, n_class, int(foreground_only), mode, int(connectivity), samp, ptr(table), ptr(ws),
+         nbytes, stream_ptr())
     return table.view(-1, 2, d if mode == 2 else 1, 4)
 
 
@@ -450,15 +471,14 @@ def surface_quantiles(pred: torch.Tensor, gt: torch.Tensor, n_class: int, q=(95.
     p, g = pred.to(torch.uint8).contiguous(), gt.long().contiguous()
     d, h, w = (int(v) for v in p.shape)
     samp = _surface_sampling(sampling, mode)
-    nbytes = lib.ctl_surface_quantiles_ws_bytes(d, h, w, n_class, int(foreground_only), mode, len(qs))
+    ws, nbytes = _workspace("ctl_surface_quantiles_ws_bytes", d, h, w, n_class, int(foreground_only), mode, len(qs), device=p.device)
     rows = lib.ctl_surface_stats_rows(d, n_class, int(foreground_only), mode) if nbytes else 0
     groups = max(rows, 0) // 2
     q_table = torch.empty((groups, max(len(qs), 1), 4), dtype=torch.float64, device=p.device)
     stats = torch.empty((max(rows, 0), 4), dtype=torch.float64, device=p.device) if want_stats else None
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=p.device)
-    check(lib.ctl_surface_quantiles(ptr(p), ptr(g), d, h, w, n_class, int(foreground_only), mode, int(connectivity), samp,
-                                    (C.c_double * max(len(qs), 1))(*qs), len(qs), ptr(stats) if want_stats else None, ptr(q_table), ptr(ws),
-                                    nbytes, stream_ptr()), "ctl_surface_quantiles")
+    call("ctl_surface_quantiles", ptr(p), ptr(g), d, h, w, n_class, int(foreground_only), mode, int(connectivity), samp,
+         (C.c_double * max(len(qs), 1))(*qs), len(qs), ptr(stats) if want_stats else None, ptr(q_table), ptr(ws),
+         nbytes, stream_ptr())
     gpm = d if mode == 2 else 1
     q_table = q_table.view(-1, gpm, len(qs), 4)
     return (q_table, stats.view(-1, 2, gpm, 4)) if want_stats else q_table
@@ -474,12 +494,11 @@ def _surface_map(mask: torch.Tensor, sampling, connectivity: int, per_slice: boo
     samp = _surface_sampling(sampling, mode)
     if want_d2:
         out = torch.empty((d, h, w), dtype=torch.float64, device=m.device)
-        nbytes = lib.ctl_surface_map_ws_bytes(d, h, w, mode)
-        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=m.device)
-        check(lib.ctl_surface_map(ptr(m), d, h, w, mode, int(connectivity), samp, ptr(out), None, ptr(ws), nbytes, stream_ptr()), "ctl_surface_map")
+        ws, nbytes = _workspace("ctl_surface_map_ws_bytes", d, h, w, mode, device=m.device)
+        call("ctl_surface_map", ptr(m), d, h, w, mode, int(connectivity), samp, ptr(out), None, ptr(ws), nbytes, stream_ptr())
     else:
         out = torch.empty((d, h, w), dtype=torch.uint8, device=m.device)
-        check(lib.ctl_surface_map(ptr(m), d, h, w, mode, int(connectivity), samp, None, ptr(out), None, 0, stream_ptr()), "ctl_surface_map")
+        call("ctl_surface_map", ptr(m), d, h, w, mode, int(connectivity), samp, None, ptr(out), None, 0, stream_ptr())
         out = out.bool()
     return out.reshape(mask.shape)
 
@@ -516,7 +535,7 @@ def connected_components(labelmap: torch.Tensor, n_class: int, connectivity: int
     scipy.ndimage.generate_binary_structure(ndim, connectivity).  3 launches, no readback."""
     m, d, h, w, mode = _cc_volume(labelmap, per_slice, "connected_components")
     labels = torch.empty((d, h, w), dtype=torch.int32, device=m.device)
-    check(lib.ctl_cc_label(ptr(m), d, h, w, int(n_class), mode, int(connectivity), ptr(labels), stream_ptr()), "ctl_cc_label")
+    call("ctl_cc_label", ptr(m), d, h, w, int(n_class), mode, int(connectivity), ptr(labels), stream_ptr())
     return labels.reshape(labelmap.shape)
 
 
@@ -528,15 +547,10 @@ def keep_largest_components(labelmap: torch.Tensor, n_class: int, connectivity: 
     [groups, n_class - 1, 3] = (components, voxels of the kept one, its label or -1), groups = slices with per_slice else 1.
     5 launches, no readback."""
     m, d, h, w, mode = _cc_volume(labelmap, per_slice, "keep_largest_components")
-    if out is None:
-        out = torch.empty(labelmap.shape, dtype=torch.uint8, device=m.device)
-    elif not (out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == tuple(labelmap.shape) and out.is_contiguous()):
-        raise ValueError("keep_largest_components: `out` must be a contiguous uint8 device tensor of labelmap's shape")
+    out = _out(out, torch.uint8, labelmap.shape, m.device, "keep_largest_components")
     table = torch.empty((d if mode == 2 else 1, int(n_class) - 1, 3), dtype=torch.int64, device=m.device) if want_table else None
-    nbytes = lib.ctl_cc_ws_bytes(d, h, w, int(n_class), mode)
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=m.device)
-    check(lib.ctl_cc_keep_largest(ptr(m), d, h, w, int(n_class), mode, int(connectivity), ptr(out), ptr(table), ptr(ws), nbytes, stream_ptr()),
-          "ctl_cc_keep_largest")
+    ws, nbytes = _workspace("ctl_cc_ws_bytes", d, h, w, int(n_class), mode, device=m.device)
+    call("ctl_cc_keep_largest", ptr(m), d, h, w, int(n_class), mode, int(connectivity), ptr(out), ptr(table), ptr(ws), nbytes, stream_ptr())
     return (out, table) if want_table else out
 
 
@@ -568,8 +582,7 @@ def aug_elastic_field(n: int, hp: int, wp: int, alpha, sigma, seed, noise: Optio
     n, hp, wp = int(n), int(hp), int(wp)
     if noise is not None:
         require_gpu(noise)
-        if tuple(noise.shape) != (n, 2, hp, wp) or noise.dtype != torch.float32:
-            raise ValueError(f"aug_elastic_field: noise must be float32 [n,2,hp,wp] = {(n, 2, hp, wp)}, got {noise.dtype} {tuple(noise.shape)}")
+        _arg(noise, torch.float32, (n, 2, hp, wp), "aug_elastic_field", "noise")
         noise = noise.contiguous()
         device = noise.device
     elif device is None:
@@ -578,11 +591,8 @@ def aug_elastic_field(n: int, hp: int, wp: int, alpha, sigma, seed, noise: Optio
     a = _aug_vec(alpha, n, torch.float32, device, "aug_elastic_field", "alpha")
     s = _aug_vec(sigma, n, torch.float32, device, "aug_elastic_field", "sigma")
     sd = _aug_vec(seed, n, torch.int64, device, "aug_elastic_field", "seed")
-    if out is None:
-        out = torch.empty((n, 2, hp, wp), dtype=torch.float32, device=device)
-    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (n, 2, hp, wp) and out.is_contiguous()):
-        raise ValueError("aug_elastic_field: `out` must be a contiguous float32 device tensor [n,2,hp,wp]")
-    check(lib.ctl_aug_field(ptr(noise), ptr(sd), ptr(a), ptr(s), n, hp, wp, ptr(out), ptr(ws), nbytes, stream_ptr()), "ctl_aug_field")
+    out = _out(out, torch.float32, (n, 2, hp, wp), device, "aug_elastic_field")
+    call("ctl_aug_field", ptr(noise), ptr(sd), ptr(a), ptr(s), n, hp, wp, ptr(out), ptr(ws), nbytes, stream_ptr())
     return out
 
 
@@ -599,25 +609,18 @@ def aug_bias_field(image: torch.Tensor, bias: torch.Tensor, seed=None, noise: Op
     pixel), seed a scalar or one int64 per sample (None = 0).  A sample whose record is off and a black plane are copied bit for bit.
     hp == wp, even, 128..512.  2 launches, no readback."""
     require_gpu(image, bias, noise)
-    if image.dim() != 4 or image.shape[1] != 1 or image.dtype != torch.float32:
-        raise ValueError(f"aug_bias_field: image must be float32 [n,1,hp,wp], got {image.dtype} {tuple(image.shape)}")
+    _arg(image, torch.float32, (None, 1, None, None), "aug_bias_field", "image")
     n, _, hp, wp = (int(v) for v in image.shape)
     if hp != wp or hp % 2 or not 128 <= hp <= 512:
         raise ValueError(f"aug_bias_field: the plane must be square with an even side of 128..512, got {hp}x{wp}")
-    if bias.dtype != torch.float32 or tuple(bias.shape) != (n, BIAS_FLOATS):
-        raise ValueError(f"aug_bias_field: bias must be float32 [n,{BIAS_FLOATS}] = {(n, BIAS_FLOATS)}, got {bias.dtype} {tuple(bias.shape)}")
+    _arg(bias, torch.float32, (n, BIAS_FLOATS), "aug_bias_field", "bias")
     if noise is not None:
-        if tuple(noise.shape) != (n, 1, hp, wp) or noise.dtype != torch.float32:
-            raise ValueError(f"aug_bias_field: noise must be float32 [n,1,hp,wp] = {(n, 1, hp, wp)}, got {noise.dtype} {tuple(noise.shape)}")
+        _arg(noise, torch.float32, (n, 1, hp, wp), "aug_bias_field", "noise")
         noise = noise.contiguous()
     sd = _aug_vec(0 if seed is None else seed, n, torch.int64, image.device, "aug_bias_field", "seed")
     ws, nbytes = _aug_ws(lib.ctl_aug_bias_ws_bytes(n, hp, wp), n, hp, wp, hp, wp, image.device, "aug_bias_field")
-    if out is None:
-        out = torch.empty((n, 1, hp, wp), dtype=torch.float32, device=image.device)
-    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (n, 1, hp, wp) and out.is_contiguous()):
-        raise ValueError("aug_bias_field: `out` must be a contiguous float32 device tensor [n,1,hp,wp]")
-    check(lib.ctl_aug_bias(ptr(image.contiguous()), ptr(bias.contiguous()), ptr(noise), ptr(sd), n, hp, wp, ptr(out), ptr(ws), nbytes,
-                           stream_ptr()), "ctl_aug_bias")
+    out = _out(out, torch.float32, (n, 1, hp, wp), image.device, "aug_bias_field")
+    call("ctl_aug_bias", ptr(image.contiguous()), ptr(bias.contiguous()), ptr(noise), ptr(sd), n, hp, wp, ptr(out), ptr(ws), nbytes, stream_ptr())
     return out
 
 
@@ -628,19 +631,16 @@ def aug_coarse_field(n: int, hp: int, wp: int, coarse: torch.Tensor, device=None
     coefficients, clip bounds, on); a host tensor is uploaded, a device tensor is read by the kernel.  A sample that is off gets zeros.
     hp, wp <= 512.  1 launch."""
     n, hp, wp = int(n), int(hp), int(wp)
-    if not isinstance(coarse, torch.Tensor) or coarse.dtype != torch.float32 or tuple(coarse.shape) != (n, COARSE_FLOATS):
-        raise ValueError(f"aug_coarse_field: coarse must be a float32 tensor [n,{COARSE_FLOATS}] = {(n, COARSE_FLOATS)}, got "
-                         f"{getattr(coarse, 'dtype', type(coarse))} {tuple(getattr(coarse, 'shape', ()))}")
+    if not isinstance(coarse, torch.Tensor):
+        raise ValueError(f"aug_coarse_field: coarse must be a float32 tensor [n,{COARSE_FLOATS}], got {type(coarse)}")
+    _arg(coarse, torch.float32, (n, COARSE_FLOATS), "aug_coarse_field", "coarse")
     if n < 1 or n > 65535 or hp < 1 or wp < 1 or hp > 512 or wp > 512:
         raise ValueError(f"aug_coarse_field: n={n}, {hp}x{wp} is refused: sizes must be positive and planes at most 512x512")
     if device is None:
         device = coarse.device if coarse.is_cuda else torch.device("cuda")
     coarse = coarse.to(device).contiguous()
-    if out is None:
-        out = torch.empty((n, 2, hp, wp), dtype=torch.float32, device=device)
-    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (n, 2, hp, wp) and out.is_contiguous()):
-        raise ValueError("aug_coarse_field: `out` must be a contiguous float32 device tensor [n,2,hp,wp]")
-    check(lib.ctl_aug_coarse_field(ptr(coarse), n, hp, wp, ptr(out), stream_ptr()), "ctl_aug_coarse_field")
+    out = _out(out, torch.float32, (n, 2, hp, wp), device, "aug_coarse_field")
+    call("ctl_aug_coarse_field", ptr(coarse), n, hp, wp, ptr(out), stream_ptr())
     return out
 
 
@@ -657,8 +657,7 @@ def aug_spline_coeffs(image: torch.Tensor, label: Optional[torch.Tensor] = None,
     None = (1, 0)), plane 1 + k of the indicator label == k for k < n_class (label int64 [n,hp,wp]; not read when n_class is 0).  What
     aug_warp(interp="cubic") gathers from.  3 launches, no readback."""
     require_gpu(image, label, intensity)
-    if image.dim() != 4 or image.shape[1] != 1 or image.dtype != torch.float32:
-        raise ValueError(f"aug_spline_coeffs: image must be float32 [n,1,hp,wp], got {image.dtype} {tuple(image.shape)}")
+    _arg(image, torch.float32, (None, 1, None, None), "aug_spline_coeffs", "image")
     n, _, hp, wp = (int(v) for v in image.shape)
     n_class = _aug_class_count(n_class, 0, "aug_spline_coeffs")
     if n_class and (label is None or label.dtype != torch.int64 or tuple(label.shape) != (n, hp, wp)):
@@ -666,15 +665,11 @@ def aug_spline_coeffs(image: torch.Tensor, label: Optional[torch.Tensor] = None,
     if intensity is None:
         intensity = torch.zeros((n, 2), dtype=torch.float32, device=image.device)
         intensity[:, 0] = 1.0
-    if intensity.dtype != torch.float32 or tuple(intensity.shape) != (n, 2):
-        raise ValueError(f"aug_spline_coeffs: intensity must be float32 [n,2], got {intensity.dtype} {tuple(intensity.shape)}")
+    _arg(intensity, torch.float32, (n, 2), "aug_spline_coeffs", "intensity")
     ws, nbytes = _aug_ws(lib.ctl_aug_spline_ws_bytes(n, hp, wp, n_class), n, hp, wp, 1, 1, image.device, "aug_spline_coeffs")
-    if out is None:
-        out = torch.empty((n, 1 + n_class, hp, wp), dtype=torch.float32, device=image.device)
-    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (n, 1 + n_class, hp, wp) and out.is_contiguous()):
-        raise ValueError("aug_spline_coeffs: `out` must be a contiguous float32 device tensor [n,1+n_class,hp,wp]")
-    check(lib.ctl_aug_spline_coeffs(ptr(image.contiguous()), ptr(label.contiguous() if n_class else None), ptr(intensity.contiguous()), n, hp, wp,
-                                    n_class, ptr(out), ptr(ws), nbytes, stream_ptr()), "ctl_aug_spline_coeffs")
+    out = _out(out, torch.float32, (n, 1 + n_class, hp, wp), image.device, "aug_spline_coeffs")
+    call("ctl_aug_spline_coeffs", ptr(image.contiguous()), ptr(label.contiguous() if n_class else None), ptr(intensity.contiguous()), n, hp, wp,
+         n_class, ptr(out), ptr(ws), nbytes, stream_ptr())
     return out
 
 
@@ -694,36 +689,27 @@ def aug_warp(image: torch.Tensor, label: torch.Tensor, matrix: torch.Tensor, int
     if interp == "cubic":
         n_class = _aug_class_count(n_class, 1, "aug_warp(interp='cubic')")
     require_gpu(image, label, matrix, intensity, field)
-    if image.dim() != 4 or image.shape[1] != 1 or image.dtype != torch.float32:
-        raise ValueError(f"aug_warp: image must be float32 [n,1,hp,wp], got {image.dtype} {tuple(image.shape)}")
+    _arg(image, torch.float32, (None, 1, None, None), "aug_warp", "image")
     n, _, hp, wp = (int(v) for v in image.shape)
-    if label.dtype != torch.int64 or tuple(label.shape) != (n, hp, wp):
-        raise ValueError(f"aug_warp: label must be int64 [n,hp,wp] = {(n, hp, wp)}, got {label.dtype} {tuple(label.shape)}")
-    if matrix.dtype != torch.float32 or tuple(matrix.shape) != (n, 2, 3):
-        raise ValueError(f"aug_warp: matrix must be float32 [n,2,3], got {matrix.dtype} {tuple(matrix.shape)}")
-    if intensity.dtype != torch.float32 or tuple(intensity.shape) != (n, 2):
-        raise ValueError(f"aug_warp: intensity must be float32 [n,2], got {intensity.dtype} {tuple(intensity.shape)}")
-    if field is not None and (field.dtype != torch.float32 or tuple(field.shape) != (n, 2, hp, wp)):
-        raise ValueError(f"aug_warp: field must be float32 [n,2,hp,wp], got {field.dtype} {tuple(field.shape)}")
+    _arg(label, torch.int64, (n, hp, wp), "aug_warp", "label")
+    _arg(matrix, torch.float32, (n, 2, 3), "aug_warp", "matrix")
+    _arg(intensity, torch.float32, (n, 2), "aug_warp", "intensity")
+    if field is not None:
+        _arg(field, torch.float32, (n, 2, hp, wp), "aug_warp", "field")
     hc, wc = int(crop[0]), int(crop[1])
     ws_bytes = lib.ctl_aug_warp_cubic_ws_bytes(n, hp, wp, hc, wc, n_class) if interp == "cubic" else lib.ctl_aug_warp_ws_bytes(n, hp, wp, hc, wc)
     ws, nbytes = _aug_ws(ws_bytes, n, hp, wp, hc, wc, image.device, "aug_warp")
-    if out is None:
-        io = torch.empty((n, 1, hc, wc), dtype=torch.float32, device=image.device)
-        lo = torch.empty((n, hc, wc), dtype=torch.int64, device=image.device)
-    else:
-        io, lo = out
-        if not (io.is_cuda and io.dtype == torch.float32 and tuple(io.shape) == (n, 1, hc, wc) and io.is_contiguous()
-                and lo.is_cuda and lo.dtype == torch.int64 and tuple(lo.shape) == (n, hc, wc) and lo.is_contiguous()):
-            raise ValueError("aug_warp: `out` must be (float32 [n,1,hc,wc], int64 [n,hc,wc]) contiguous device tensors")
+    io, lo = (None, None) if out is None else out
+    io = _out(io, torch.float32, (n, 1, hc, wc), image.device, "aug_warp", "out[0]")
+    lo = _out(lo, torch.int64, (n, hc, wc), image.device, "aug_warp", "out[1]")
     image, label, matrix, intensity = image.contiguous(), label.contiguous(), matrix.contiguous(), intensity.contiguous()
     field = None if field is None else field.contiguous()
     if interp == "cubic":
-        check(lib.ctl_aug_warp_cubic(ptr(image), ptr(label), ptr(matrix), ptr(intensity), ptr(field), n, hp, wp, hc, wc, n_class, ptr(io), ptr(lo),
-                                     ptr(ws), nbytes, stream_ptr()), "ctl_aug_warp_cubic")
+        call("ctl_aug_warp_cubic", ptr(image), ptr(label), ptr(matrix), ptr(intensity), ptr(field), n, hp, wp, hc, wc, n_class, ptr(io), ptr(lo),
+             ptr(ws), nbytes, stream_ptr())
         return io, lo
-    check(lib.ctl_aug_warp(ptr(image), ptr(label), ptr(matrix), ptr(intensity), ptr(field), n, hp, wp,
-                           hc, wc, ptr(io), ptr(lo), ptr(ws), nbytes, stream_ptr()), "ctl_aug_warp")
+    call("ctl_aug_warp", ptr(image), ptr(label), ptr(matrix), ptr(intensity), ptr(field), n, hp, wp,
+         hc, wc, ptr(io), ptr(lo), ptr(ws), nbytes, stream_ptr())
     return io, lo
 
 
@@ -734,14 +720,9 @@ def rescale_intensity(data: torch.Tensor, new_min: float = 0.0, new_max: float =
     require_gpu(data)
     x = data.float().contiguous()
     n, c, h, w = x.shape
-    if out is None:
-        out = torch.empty_like(x)
-    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == tuple(x.shape) and out.is_contiguous()):
-        raise ValueError("rescale_intensity: `out` must be a contiguous float32 device tensor of data's shape")
-    elif out.data_ptr() == x.data_ptr():
-        raise ValueError("rescale_intensity: `out` must not be the input")
-    ws = torch.empty(lib.ctl_rescale_intensity_ws_floats(n * c), dtype=torch.float32, device=x.device)
-    check(lib.ctl_rescale_intensity(ptr(x), ptr(out), ptr(ws), n * c, h * w, new_min, new_max, eps, stream_ptr()), "ctl_rescale_intensity")
+    out = _out(out, torch.float32, x.shape, x.device, "rescale_intensity", not_input=x)
+    ws, _ = _workspace("ctl_rescale_intensity_ws_floats", n * c, device=x.device, dtype=torch.float32, floor=0)
+    call("ctl_rescale_intensity", ptr(x), ptr(out), ptr(ws), n * c, h * w, new_min, new_max, eps, stream_ptr())
     return out
 
 
@@ -755,7 +736,7 @@ def noise_clamp(x: torch.Tensor, noise: Optional[torch.Tensor] = None, sigma: fl
         if noise.shape != x.shape:
             raise ValueError("noise_clamp: noise must have the shape of x")
     out = torch.empty_like(x)
-    check(lib.ctl_noise_clamp(ptr(x), ptr(noise), seed & (2 ** 64 - 1), sigma, lo, hi, ptr(out), x.numel(), stream_ptr()), "ctl_noise_clamp")
+    call("ctl_noise_clamp", ptr(x), ptr(noise), seed & (2 ** 64 - 1), sigma, lo, hi, ptr(out), x.numel(), stream_ptr())
     return out
 
 
@@ -769,8 +750,7 @@ def crop_or_pad(image: torch.Tensor, crop_size, label: Optional[torch.Tensor] = 
             raise ValueError("crop_or_pad: expected a [n,h,w] or [h,w] tensor with 1-, 4- or 8-byte elements")
         n, h, w = a3.shape
         out = torch.empty((n, int(crop_size[0]), int(crop_size[1])), dtype=a3.dtype, device=a3.device)
-        check(lib.ctl_crop_or_pad(ptr(a3), ptr(out), a3.element_size(), n, h, w, int(crop_size[0]), int(crop_size[1]), stream_ptr()),
-              "ctl_crop_or_pad")
+        call("ctl_crop_or_pad", ptr(a3), ptr(out), a3.element_size(), n, h, w, int(crop_size[0]), int(crop_size[1]), stream_ptr())
         return out[0] if squeeze else out
     return one(image), (None if label is None else one(label))
 
@@ -820,10 +800,8 @@ def _segmented(x: torch.Tensor, segments: int, who: str):
 def _order_stats(x: torch.Tensor, segments: int, seg_elems: int, ranks) -> torch.Tensor:
     ranks = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
     table = torch.empty((segments, ranks.size), dtype=torch.float32, device=x.device)
-    nbytes = lib.ctl_order_stats_ws_bytes(segments, int(ranks.size))
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
-    check(lib.ctl_order_stats(ptr(x), segments, seg_elems, ranks.ctypes.data, int(ranks.size), ptr(table), ptr(ws), nbytes, stream_ptr()),
-          "ctl_order_stats")
+    ws, nbytes = _workspace("ctl_order_stats_ws_bytes", segments, int(ranks.size), device=x.device)
+    call("ctl_order_stats", ptr(x), segments, seg_elems, ranks.ctypes.data, int(ranks.size), ptr(table), ptr(ws), nbytes, stream_ptr())
     return table
 
 
@@ -854,8 +832,7 @@ def percentile(x: torch.Tensor, q, segments: int = 1) -> torch.Tensor:
         pair = q[i:i + 2] if i + 1 < len(q) else [q[i], q[i]]
         table, g_lo, g_hi = _percentile_table(x, segments, seg_elems, pair[0], pair[1])
         bounds = torch.empty((segments, 2), dtype=torch.float32, device=x.device)
-        check(lib.ctl_percentile_apply(ptr(x), ptr(table), segments, seg_elems, g_lo, g_hi, 0, 0.0, 1.0, None, ptr(bounds), stream_ptr()),
-              "ctl_percentile_apply")
+        call("ctl_percentile_apply", ptr(x), ptr(table), segments, seg_elems, g_lo, g_hi, 0, 0.0, 1.0, None, ptr(bounds), stream_ptr())
         out[:, i:i + 2] = bounds[:, :len(q) - i]
     return out
 
@@ -877,16 +854,11 @@ def percentile_normalize(x: torch.Tensor, q=(2.0, 98.0), form: str = "minmax", s
     x, segments, seg_elems = _segmented(x, segments, "percentile_normalize")
     if len(q) != 2:
         raise ValueError("percentile_normalize: q is a (low, high) pair of percentiles")
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == tuple(shape) and out.is_contiguous()):
-        raise ValueError("percentile_normalize: `out` must be a contiguous float32 device tensor of x's shape")
-    elif out.data_ptr() == x.data_ptr():
-        raise ValueError("percentile_normalize: `out` must not be the input")
+    out = _out(out, torch.float32, shape, x.device, "percentile_normalize", not_input=x)
     table, g_lo, g_hi = _percentile_table(x, segments, seg_elems, q[0], q[1])
     bounds = torch.empty((segments, 2), dtype=torch.float32, device=x.device) if want_bounds else None
-    check(lib.ctl_percentile_apply(ptr(x), ptr(table), segments, seg_elems, g_lo, g_hi, PERCENTILE_FORMS[form], float(new_min), float(new_max),
-                                   ptr(out), ptr(bounds), stream_ptr()), "ctl_percentile_apply")
+    call("ctl_percentile_apply", ptr(x), ptr(table), segments, seg_elems, g_lo, g_hi, PERCENTILE_FORMS[form], float(new_min), float(new_max),
+         ptr(out), ptr(bounds), stream_ptr())
     return (out, bounds) if want_bounds else out
 
 
@@ -897,12 +869,10 @@ def resample_inplane(image: torch.Tensor, spacing, new_spacing, label: Optional[
     coordinate j * new_spacing / spacing; 0 where that reaches size - 0.5.  When the scalings sum to within 1e-4 of their count the inputs
     are returned unchanged, as upstream does.  One launch per array, no readback."""
     require_gpu(image)
-    if image.dim() != 3 or image.dtype != torch.float32:
-        raise ValueError(f"resample_inplane: expected a float32 [n,h,w] image, got {image.dtype} {tuple(image.shape)}")
+    _arg(image, torch.float32, (None, None, None), "resample_inplane", "image")
     if label is not None:
         require_gpu(label)
-        if label.dtype not in (torch.uint8, torch.int64) or tuple(label.shape) != tuple(image.shape):
-            raise ValueError(f"resample_inplane: expected a uint8 or int64 label of the image's shape, got {label.dtype} {tuple(label.shape)}")
+        _arg(label, (torch.uint8, torch.int64), tuple(image.shape), "resample_inplane", "label")
     n, h, w = (int(v) for v in image.shape)
     new_h, new_w, r_h, r_w, identity = resample_geometry(n, h, w, spacing, new_spacing)
     if identity:
@@ -913,8 +883,8 @@ def resample_inplane(image: torch.Tensor, spacing, new_spacing, label: Optional[
     if label is not None:
         label = label.contiguous()
         label_out = torch.empty((n, new_h, new_w), dtype=label.dtype, device=label.device)
-    check(lib.ctl_resample_inplane(ptr(image), ptr(label), 0 if label is None else label.element_size(), n, h, w, new_h, new_w, r_h, r_w,
-                                   ptr(image_out), ptr(label_out), stream_ptr()), "ctl_resample_inplane")
+    call("ctl_resample_inplane", ptr(image), ptr(label), 0 if label is None else label.element_size(), n, h, w, new_h, new_w, r_h, r_w,
+         ptr(image_out), ptr(label_out), stream_ptr())
     return image_out, label_out, (float(new_spacing[0]), float(new_spacing[1]), float(spacing[2]))
 
 
@@ -929,14 +899,6 @@ def _restore_args(geometry, n: int, window, who: str):
         raise ValueError(f"{who}: the input's window {tuple(int(v) for v in window)} is not the geometry's {(int(hc), int(wc))}")
     return (int(n), int(hc), int(wc), int(h), int(w), int(rh), int(rw), int(geometry.offset[0]), int(geometry.offset[1]),
             float(geometry.q[0]), float(geometry.q[1]))
-
-
-def _restore_out(out: Optional[torch.Tensor], shape, device, who: str) -> torch.Tensor:
-    if out is None:
-        return torch.empty(shape, dtype=torch.uint8, device=device)
-    if not (out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == tuple(shape) and out.is_contiguous()):
-        raise ValueError(f"{who}: `out` must be a contiguous uint8 device tensor of shape {tuple(shape)}")
-    return out
 
 
 def restore_scores(scores: torch.Tensor, geometry, mode: str = "logit", want_soft: bool = False, out: Optional[torch.Tensor] = None):
@@ -954,10 +916,9 @@ def restore_scores(scores: torch.Tensor, geometry, mode: str = "logit", want_sof
     require_gpu(scores, out)
     scores = as_nhwc(scores)
     h, w = args[3], args[4]
-    label = _restore_out(out, (n, h, w), scores.device, "restore_scores")
+    label = _out(out, torch.uint8, (n, h, w), scores.device, "restore_scores")
     soft = torch.empty((n, c, h, w), dtype=torch.float32, device=scores.device) if want_soft else None
-    check(lib.ctl_restore_scores(ptr(scores), args[0], c, *args[1:], RESTORE_MODES[mode], ptr(label), ptr(soft), stream_ptr()),
-          "ctl_restore_scores")
+    call("ctl_restore_scores", ptr(scores), args[0], c, *args[1:], RESTORE_MODES[mode], ptr(label), ptr(soft), stream_ptr())
     return (label, soft) if want_soft else label
 
 
@@ -970,8 +931,8 @@ def restore_labels(labels: torch.Tensor, geometry, out: Optional[torch.Tensor] =
     args = _restore_args(geometry, n, labels.shape[1:], "restore_labels")
     require_gpu(labels, out)
     labels = labels.contiguous()
-    res = _restore_out(out, (n, args[3], args[4]), labels.device, "restore_labels")
-    check(lib.ctl_restore_labels(ptr(labels), *args, ptr(res), stream_ptr()), "ctl_restore_labels")
+    res = _out(out, torch.uint8, (n, args[3], args[4]), labels.device, "restore_labels")
+    call("ctl_restore_labels", ptr(labels), *args, ptr(res), stream_ptr())
     return res
 
 
@@ -987,14 +948,6 @@ def _volume(x: torch.Tensor, who: str):
     return (x,) + tuple(int(v) for v in x.shape)
 
 
-def _volume_out(out: Optional[torch.Tensor], shape, like: torch.Tensor, who: str) -> torch.Tensor:
-    if out is None:
-        return torch.empty(shape, dtype=torch.float32, device=like.device)
-    if not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == tuple(shape) and out.is_contiguous()):
-        raise ValueError(f"{who}: `out` must be a contiguous float32 device tensor of shape {tuple(shape)}")
-    return out
-
-
 def corrupt_bias_field(x: torch.Tensor, coefficients, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x * exp(cubic polynomial of the normalised voxel coordinates) in float32 (ctl_corrupt_bias): x [D,H,W], coefficients = 20 host
     numbers in the loop order i, j, k of u^i v^j w^k (rounded to float32).  One launch."""
@@ -1002,8 +955,8 @@ def corrupt_bias_field(x: torch.Tensor, coefficients, out: Optional[torch.Tensor
     coef = np.ascontiguousarray(coefficients, dtype=np.float32).reshape(-1)
     if coef.size != 20:
         raise ValueError(f"corrupt_bias_field: {coef.size} coefficients, 20 expected (i + j + k <= 3)")
-    out = _volume_out(out, (d, h, w), x, "corrupt_bias_field")
-    check(lib.ctl_corrupt_bias(ptr(x), coef.ctypes.data, d, h, w, ptr(out), stream_ptr()), "ctl_corrupt_bias")
+    out = _out(out, torch.float32, (d, h, w), x.device, "corrupt_bias_field")
+    call("ctl_corrupt_bias", ptr(x), coef.ctypes.data, d, h, w, ptr(out), stream_ptr())
     return out
 
 
@@ -1023,10 +976,10 @@ def corrupt_spike(x: torch.Tensor, k, mult, intensity: float, out: Optional[torc
     mult = np.ascontiguousarray(mult, dtype=np.int32).reshape(-1)
     if mult.size != k.shape[0]:
         raise ValueError("corrupt_spike: one multiplicity per wave vector")
-    out = _volume_out(out, (d, h, w), x, "corrupt_spike")
+    out = _out(out, torch.float32, (d, h, w), x.device, "corrupt_spike")
     ws = corrupt_spike_workspace((d, h, w), k.shape[0], x.device) if workspace is None else workspace
-    check(lib.ctl_corrupt_spike(ptr(x), d, h, w, k.ctypes.data, mult.ctypes.data, int(k.shape[0]), float(intensity), ptr(out), ptr(ws),
-                                ws.numel() * ws.element_size(), stream_ptr()), "ctl_corrupt_spike")
+    call("ctl_corrupt_spike", ptr(x), d, h, w, k.ctypes.data, mult.ctypes.data, int(k.shape[0]), float(intensity), ptr(out), ptr(ws),
+         ws.numel() * ws.element_size(), stream_ptr())
     return out
 
 
@@ -1035,8 +988,8 @@ def corrupt_rigid3d(x: torch.Tensor, matrices, out: Optional[torch.Tensor] = Non
     the volume extended by zeros, float32 coordinates (ctl_corrupt_rigid3d).  An identity matrix returns x bit for bit.  One launch."""
     x, d, h, w = _volume(x, "corrupt_rigid3d")
     m = np.ascontiguousarray(matrices, dtype=np.float32).reshape(-1, 12)
-    out = _volume_out(out, (m.shape[0], d, h, w), x, "corrupt_rigid3d")
-    check(lib.ctl_corrupt_rigid3d(ptr(x), d, h, w, m.ctypes.data, int(m.shape[0]), ptr(out), stream_ptr()), "ctl_corrupt_rigid3d")
+    out = _out(out, torch.float32, (m.shape[0], d, h, w), x.device, "corrupt_rigid3d")
+    call("ctl_corrupt_rigid3d", ptr(x), d, h, w, m.ctypes.data, int(m.shape[0]), ptr(out), stream_ptr())
     return out
 
 
@@ -1058,10 +1011,9 @@ def axis_operator(x: torch.Tensor, matrix: torch.Tensor, axis: int, stack: Optio
         n_vol += int(stack.shape[0])
     length = (d, h, w)[axis]
     require_gpu(matrix)
-    if matrix.dtype != torch.float32 or tuple(matrix.shape) != (length, n_vol * length) or not matrix.is_contiguous():
-        raise ValueError(f"axis_operator: expected a contiguous float32 matrix [{length}, {n_vol * length}], got {matrix.dtype} {tuple(matrix.shape)}")
-    out = _volume_out(out, (d, h, w), x, "axis_operator")
-    check(lib.ctl_axis_operator(ptr(x), ptr(stack), n_vol, d, h, w, axis, ptr(matrix), ptr(out), stream_ptr()), "ctl_axis_operator")
+    _arg(matrix, torch.float32, (length, n_vol * length), "axis_operator", "matrix", dense=True)
+    out = _out(out, torch.float32, (d, h, w), x.device, "axis_operator")
+    call("ctl_axis_operator", ptr(x), ptr(stack), n_vol, d, h, w, axis, ptr(matrix), ptr(out), stream_ptr())
     return out
 
 
@@ -1079,21 +1031,13 @@ def _arenas(image_arena: torch.Tensor, label_arena: torch.Tensor, table: torch.T
     return int(table.shape[0]), int(label_arena.numel())
 
 
-def _dense_out(out: Optional[torch.Tensor], shape, dtype, device, who: str, name: str) -> torch.Tensor:
-    if out is None:
-        return torch.empty(shape, dtype=dtype, device=device)
-    if out.dtype != dtype or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
-        raise ValueError(f"{who}: `{name}` must be a contiguous {dtype} tensor of shape {tuple(shape)}, got {out.dtype} {tuple(out.shape)}")
-    return out
-
-
 def slice_foreground(label_arena: torch.Tensor, table: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """int32 device tensor [S]: the number of non-zero raw label bytes of every slice of the packed uint8 arena (ctl_slice_foreground;
     table: int64 [S,3] of element offset, h, w).  One launch, integer adds only, no readback."""
     n_slices, elems = _arenas(None, label_arena, table, "slice_foreground")
-    out = _dense_out(out, (n_slices,), torch.int32, label_arena.device, "slice_foreground", "out")
+    out = _out(out, torch.int32, (n_slices,), label_arena.device, "slice_foreground", on_device=False)        # a host `out` is require_gpu's to refuse
     require_gpu(label_arena, table, out)
-    check(lib.ctl_slice_foreground(ptr(label_arena), ptr(table), n_slices, elems, ptr(out), stream_ptr()), "ctl_slice_foreground")
+    call("ctl_slice_foreground", ptr(label_arena), ptr(table), n_slices, elems, ptr(out), stream_ptr())
     return out
 
 
@@ -1129,17 +1073,17 @@ def batch_gather(image_arena: torch.Tensor, label_arena: torch.Tensor, table: to
     if host_index and (int(index_h.min()) < 0 or int(index_h.max()) >= n_slices):
         raise IndexError(f"{who}: host index outside [0, {n_slices}): min {int(index_h.min())}, max {int(index_h.max())}")
     dev = image_arena.device
-    image = _dense_out(None if out is None else out[0], (n, 1, H, W), torch.float32, dev, who, "out[0]")
-    label = _dense_out(None if out is None else out[1], (n, H, W), torch.int64, dev, who, "out[1]")
+    image = _out(None if out is None else out[0], torch.float32, (n, 1, H, W), dev, who, "out[0]", on_device=False)      # host outputs are
+    label = _out(None if out is None else out[1], torch.int64, (n, H, W), dev, who, "out[1]", on_device=False)           # require_gpu's to refuse
     oi = ol = None
     Hc = Wc = 0
     if crop is not None:
         Hc, Wc = int(crop[0]), int(crop[1])
-        oi = _dense_out(None if orig_out is None else orig_out[0], (n, 1, Hc, Wc), torch.float32, dev, who, "orig_out[0]")
-        ol = _dense_out(None if orig_out is None else orig_out[1], (n, Hc, Wc), torch.int64, dev, who, "orig_out[1]")
+        oi = _out(None if orig_out is None else orig_out[0], torch.float32, (n, 1, Hc, Wc), dev, who, "orig_out[0]", on_device=False)
+        ol = _out(None if orig_out is None else orig_out[1], torch.int64, (n, Hc, Wc), dev, who, "orig_out[1]", on_device=False)
     require_gpu(image_arena, label_arena, table, lut, image, label, oi, ol)
     if host_index:
         index = torch.from_numpy(index_h.astype(np.int32)).pin_memory().to(dev, non_blocking=True)
-    check(lib.ctl_batch_gather(ptr(image_arena), ptr(label_arena), ptr(table), n_slices, elems, ptr(index), n, ptr(lut), H, W, ptr(image),
-                               ptr(label), Hc, Wc, ptr(oi), ptr(ol), stream_ptr()), "ctl_batch_gather")
+    call("ctl_batch_gather", ptr(image_arena), ptr(label_arena), ptr(table), n_slices, elems, ptr(index), n, ptr(lut), H, W, ptr(image),
+         ptr(label), Hc, Wc, ptr(oi), ptr(ol), stream_ptr())
     return (image, label) if crop is None else (image, label, oi, ol)

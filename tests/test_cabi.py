@@ -53,6 +53,37 @@ def test_every_declared_symbol_is_exported():
     assert declared == set(_ffi.EXPORTED), declared ^ set(_ffi.EXPORTED)
 
 
+def _c_class(ctype: str) -> type:
+    """The ctypes class a C parameter or return type of ctl_hip.h is passed as; every pointer (and ctl_stream) is one class."""
+    words = ctype.replace("*", " * ").split()
+    if "*" in words or "ctl_stream" in words:
+        return ctypes.c_void_p
+    scalar = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32, "uint64_t": ctypes.c_uint64,
+              "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t, "unsigned long long": ctypes.c_ulonglong}
+    return scalar[" ".join(w for w in words if w != "const")]
+
+
+def test_binding_signatures_match_the_header():
+    """Argument for argument and return type for return type: the ctypes signature of every entry is the header's prototype, no entry is
+    left without argtypes (ctypes would pass its pointers as C int), and the parser skips no prototype."""
+    header = open(os.path.join(ROOT, "include", "ctl_hip.h")).read()
+    header = re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", header, flags=re.S))
+    protos = re.findall(r"([A-Za-z_][\w \t\*]*?)\b(ctl_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", header)
+    assert len(protos) == len({name for _, name, _ in protos})
+    assert {name for _, name, _ in protos} == set(_ffi.EXPORTED)
+    pointer = lambda t: ctypes.c_void_p if t is ctypes.c_char_p else t
+    wrong = []
+    for ret, name, args in protos:
+        fn = getattr(_ffi.lib, name)
+        assert fn.argtypes is not None, name
+        params = [] if args.strip() in ("", "void") else [a.strip() for a in args.split(",")]
+        want = [_c_class(a if "*" in a else a.rsplit(None, 1)[0]) for a in params]     # a scalar's class comes from its type, not its name
+        want_ret = ctypes.c_char_p if ret.split() == ["const", "char*"] else _c_class(ret)
+        if [pointer(t) for t in fn.argtypes] != want or fn.restype is not want_ret:
+            wrong.append((name, fn.restype, list(fn.argtypes), want_ret, want))
+    assert not wrong, wrong
+
+
 def test_struct_layouts_match():
     assert _ffi.lib.ctl_sizeof_op() == _ffi.OP_DTYPE.itemsize == 328
     assert _ffi.lib.ctl_sizeof_conv() == _ffi.CONV_DTYPE.itemsize == 96

@@ -77,6 +77,10 @@ PRO_MAX = 256           # CTL_PRO_MAX (csrc/ctl_conv_common.h): the [groups][cin
 
 T = namedtuple("T", "ref n h w c b16", defaults=(False,))     # tensor descriptor: ref = (slot, byte offset), NHWC dims, bf16 storage?
 
+# what a conv launch with a statistics epilogue leaves behind: ref of its partial sums [groups][blocks][2][cout], their row count, and the
+# 2x2 sum-pool of g when a tail epilogue wrote one (else None).  Also the `pre` / `pre_tail` arguments of the backward emitters
+Stats = namedtuple("Stats", "ref blocks pool")
+
 
 def _rup(x: int, a: int) -> int:
     return (x + a - 1) // a * a
@@ -256,15 +260,16 @@ class PassStack:
 
 
 class PlanBuilder:
-    def __init__(self, net: "CtlNet"):
+    def __init__(self, net: "CtlNet", *, groups=1, pp=(0, 1), affine_mask=0, split_tail=False):
         self.net = net
         # BatchNorm groups: independent passes batched along n (each keeps its own statistics), see ctl_conv.groups
-        self.groups = int(getattr(net, "_cur_groups", 1))
+        self.groups = int(groups)
         self.ops: List[np.ndarray] = []
         self.b16 = bool(getattr(net, "bf16", False))
-        self.pp = tuple(getattr(net, "_cur_pp", (0, 1)))                 # forward plans: pass slot (p, P) of a stacked arena, see Arena
-        self.affine_mask = int(getattr(net, "_cur_affine_mask", 0))      # backward plans: the groups that add to gamma / beta gradients (0 = all)
-        self.split_tail = bool(getattr(net, "_cur_split", False))        # backward plans: also cut into data-gradient chain | weight-gradient tail
+        self.pp = tuple(pp)                       # forward plans: pass slot (p, P) of a stacked arena, see Arena
+        self.affine_mask = int(affine_mask)       # backward plans: the groups that add to gamma / beta gradients (0 = all)
+        self.split_tail = bool(split_tail)        # backward plans: also cut into data-gradient chain | weight-gradient tail
+        self.n_drop = self.keep_off = 0           # forward plans with Dropout2d: call sites so far (the salt), floats of injected keep patterns consumed
         self.act = Arena(S_ACT, self.b16, self.pp)
         self.bscr = Arena(S_BSCR, self.b16)
         self.scr_bytes = 0
@@ -327,7 +332,7 @@ class PlanBuilder:
         tail = (T block_out, T v, slope): this conv writes dL/dOut of a residual block; the epilogue stores g = dOut * leaky'(block_out)
         instead and takes the BatchNorm-backward sums of the tail (sum g, sum g*v) into the statistics partials (CTL_EPI_TAILBWD).
         x2 = (T u, coef_ref): the input is the virtual BatchNorm-backward result A*x + B*u + C (pro_affine 2, bf16 family).
-        Returns (T y, stats_ref or None, stats_blocks)."""
+        Returns (T y, Stats or None): where the launch leaves its statistics partials (and the pooled g of a tail), None without any."""
         res2, want_pool, pool_t = None, False, None
         if tail is not None:
             assert res is None and bnbwd is None and bias_ref is None and act == 0
@@ -366,8 +371,7 @@ class PlanBuilder:
         if want_pool and FUSE_POOL and lib.ctl_conv_pool_ok(_ffi.desc_ptr(d)):
             # the tail epilogue also writes sumpool2(g) for the consuming nearest-upsample block (its 1x1 weight / data gradients)
             pool_t = self.bscr.tensor(out.n, out.h // 2, out.w // 2, out.c)
-        self.last_pool = pool_t
-        stats_ref, blocks = None, 0
+        stats_ref = None
         if stats:
             blocks = lib.ctl_conv_stats_blocks(_ffi.desc_ptr(d))
             if blocks <= 0:
@@ -382,7 +386,7 @@ class PlanBuilder:
                                    pool_t.ref if pool_t is not None else None, xout.ref if xout is not None else None]):
             self.set_t(op, idx, ref)
         assert xout is None or (x2 is not None and (xout.n, xout.h, xout.w, xout.c, xout.b16) == (x.n, x.h, x.w, x.c, x.b16))
-        return out, stats_ref, blocks
+        return out, (Stats(stats_ref, blocks, pool_t) if stats else None)
 
     def wgrad(self, x: T, dy: T, ks, *, stride=1, in_mode=0, pro=None, dw_ref, strides, dbias_ref=None, accumulate=False, dy2=None):
         """CTL_OP_WGRAD + CTL_OP_WGRAD_REDUCE for the conv x -> dy.  dy2 = (T u, coef_ref): the output gradient is the virtual
@@ -471,8 +475,8 @@ class PlanBuilder:
         self.reduce_recs = []
 
     # -- BatchNorm
-    def bn_forward(self, bn: BNInfo, stats_ref, blocks, count, mode: str):
-        """Returns dict(scale, shift, mean, invstd) of refs living in the ACT arena."""
+    def bn_forward(self, bn: BNInfo, st: Optional[Stats], count, mode: str):
+        """st: the statistics of the producing conv (unused in mode C).  Returns dict(scale, shift, mean, invstd) of refs living in the ACT arena."""
         c, G = bn.c, self.groups
         assert count % G == 0
         count //= G                                   # the statistics of one group
@@ -486,10 +490,10 @@ class PlanBuilder:
                 self.set_t(op, idx, ref)
             return co
         op = self.op(_ffi.OP_BN_FINALIZE)
-        op["i"][0], op["i"][1], op["i"][2], op["i"][3] = blocks, c, 1 if mode == "A" else 0, G
+        op["i"][0], op["i"][1], op["i"][2], op["i"][3] = st.blocks, c, 1 if mode == "A" else 0, G
         op["l"][0] = count
         op["f"][0], op["f"][1] = EPS, MOMENTUM
-        for idx, ref in enumerate([stats_ref, self.P(bn.g_off), self.P(bn.b_off), (S_B, 4 * bn.rm_off),
+        for idx, ref in enumerate([st.ref, self.P(bn.g_off), self.P(bn.b_off), (S_B, 4 * bn.rm_off),
                                    (S_B, 4 * bn.rv_off), (S_NBT, 8 * bn.nbt_idx), co["scale"], co["shift"], co["mean"],
                                    co["invstd"], co["uvar"]]):
             self.set_t(op, idx, ref)
@@ -556,15 +560,15 @@ class PlanBuilder:
             self.set_t(op, idx, ref)
         return coef
 
-    def bn_backward_from_stats(self, g: T, bn_src: T, bn: BNInfo, co, stats_ref, blocks, *, dx: T, affine_grad: bool):
+    def bn_backward_from_stats(self, g: T, bn_src: T, bn: BNInfo, co, st: Stats, *, dx: T, affine_grad: bool):
         """BatchNorm backward whose reduction already happened in the producing conv (conv(..., bnbwd=...)): finalize + apply.
         dx = None: finalize only (the consumers apply the coefficients in their staging).  Returns the coefficient ref."""
         c, pixels, G = bn_src.c, bn_src.n * bn_src.h * bn_src.w, self.groups
         coef = self.bscr.alloc(4 * 3 * c * G)
         op = self.op(_ffi.OP_BN_BWD_FINALIZE)
-        op["i"][0], op["i"][1], op["i"][2], op["i"][3], op["i"][4] = c, 0, G, blocks, self.affine_mask
+        op["i"][0], op["i"][1], op["i"][2], op["i"][3], op["i"][4] = c, 0, G, st.blocks, self.affine_mask
         op["l"][0] = pixels // G
-        for idx, ref in enumerate([stats_ref, self.P(bn.g_off), co["mean"], co["invstd"], coef,
+        for idx, ref in enumerate([st.ref, self.P(bn.g_off), co["mean"], co["invstd"], coef,
                                    self.G(bn.g_off) if affine_grad else None, self.G(bn.b_off) if affine_grad else None]):
             self.set_t(op, idx, ref)
         if dx is None:
@@ -1047,40 +1051,39 @@ class CtlNet(nn.Module):
         rec = {"prefix": prefix, "pre": pre, "xin": xin, "xin_pro": xin_pro}
         if pre == "down":
             ci = C[prefix + ".down"]
-            src, _, _ = pb.conv(xin, self._wp_ref(ci.wp_fwd), ci.cout, 3, stride=2, pro=xin_pro, bias_ref=pb.P(ci.b_off))
+            src, _ = pb.conv(xin, self._wp_ref(ci.wp_fwd), ci.cout, 3, stride=2, pro=xin_pro, bias_ref=pb.P(ci.b_off))
             src_mode = _ffi.IN_PLAIN
         elif pre == "convT":
             ci = C[prefix + ".up"]
-            src, _, _ = pb.conv(xin, self._wp_ref(ci.wp_fwd), ci.cout, 1, bias_ref=pb.P(ci.b_off), nsub=4)
+            src, _ = pb.conv(xin, self._wp_ref(ci.wp_fwd), ci.cout, 1, bias_ref=pb.P(ci.b_off), nsub=4)
             src_mode = _ffi.IN_PLAIN
         else:
             src, src_mode = xin, _ffi.IN_UP2
         c0, c3, c1 = C[prefix + ".conv.0"], C[prefix + ".conv.3"], C[prefix + ".conv_input"]
         if pre == "nn" and c0.wp_upf >= 0:
             # conv3x3(nearest_up(x)) as four 2x2 phase convs on x, outputs scattered to (2i+a, 2j+b): 16 taps per 4 outputs, not 36
-            u, st, blk = pb.conv(xin, self._wp_ref(c0.wp_upf), c0.cout, 2, nsub=4, pad=2, hout=xin.h, wout=xin.w,
-                                 bias_ref=pb.P(c0.b_off), stats=train)
+            u, st = pb.conv(xin, self._wp_ref(c0.wp_upf), c0.cout, 2, nsub=4, pad=2, hout=xin.h, wout=xin.w,
+                            bias_ref=pb.P(c0.b_off), stats=train)
         else:
-            u, st, blk = pb.conv(src, self._wp_ref(c0.wp_fwd), c0.cout, 3, in_mode=src_mode, bias_ref=pb.P(c0.b_off), stats=train)
-        co1 = pb.bn_forward(B[prefix + ".conv.1"], st, blk, u.n * u.h * u.w, mode)
-        v, st, blk = pb.conv(u, self._wp_ref(c3.wp_fwd), c3.cout, 3, pro=(co1["scale"], co1["shift"], SLOPE),
-                             bias_ref=pb.P(c3.b_off), stats=train)
-        co2 = pb.bn_forward(B[prefix + ".conv.4"], st, blk, v.n * v.h * v.w, mode)
-        out, _, _ = pb.conv(src, self._wp_ref(c1.wp_fwd), c1.cout, 1, in_mode=src_mode, bias_ref=pb.P(c1.b_off),
-                            res=(v, co2["scale"], co2["shift"]), act=_ffi.ACT_LEAKY, slope=SLOPE)
+            u, st = pb.conv(src, self._wp_ref(c0.wp_fwd), c0.cout, 3, in_mode=src_mode, bias_ref=pb.P(c0.b_off), stats=train)
+        co1 = pb.bn_forward(B[prefix + ".conv.1"], st, u.n * u.h * u.w, mode)
+        v, st = pb.conv(u, self._wp_ref(c3.wp_fwd), c3.cout, 3, pro=(co1["scale"], co1["shift"], SLOPE),
+                        bias_ref=pb.P(c3.b_off), stats=train)
+        co2 = pb.bn_forward(B[prefix + ".conv.4"], st, v.n * v.h * v.w, mode)
+        out, _ = pb.conv(src, self._wp_ref(c1.wp_fwd), c1.cout, 1, in_mode=src_mode, bias_ref=pb.P(c1.b_off),
+                         res=(v, co2["scale"], co2["shift"]), act=_ffi.ACT_LEAKY, slope=SLOPE)
         rec.update(src=src, src_mode=src_mode, u=u, v=v, out=out, co1=co1, co2=co2)
         if self.drop_p is not None and train:
             # res_x = self.drop(res_x): the block hands on the dropped tensor, keeps `out` (the LeakyReLU derivative needs its sign)
             # and the [n][c] pattern for the backward pass
             keep = pb.act.alloc(4 * out.n * out.c)
             dropped = pb.act.tensor(out.n, out.h, out.w, out.c)
-            idx = getattr(pb, "_n_drop", 0)
-            pb._n_drop = idx + 1
             keep_in = None
             if self._drop_keep is not None:
-                keep_in = (S_KEEP, 4 * getattr(pb, "_keep_off", 0))
-                pb._keep_off = getattr(pb, "_keep_off", 0) + out.n * out.c
-            pb.dropout(out, dropped, float(self.drop_p), keep_in=keep_in, keep_out=keep, salt=0x5D0 + idx)
+                keep_in = (S_KEEP, 4 * pb.keep_off)
+                pb.keep_off += out.n * out.c
+            pb.dropout(out, dropped, float(self.drop_p), keep_in=keep_in, keep_out=keep, salt=0x5D0 + pb.n_drop)
+            pb.n_drop += 1
             rec["drop"] = (keep, float(self.drop_p))
             return dropped, rec
         return out, rec
@@ -1097,13 +1100,14 @@ class CtlNet(nn.Module):
 
     def _emit_block_bwd(self, pb: PlanBuilder, rec: dict, d_out: T, d_in: Optional[T], need_w: bool, affine: bool, *, pre_tail=None,
                         tail_next=None, act_next=None):
-        """Backward of one residual block.  Returns the gradient w.r.t. the block input `xin` (post-activation tensor
-        the block consumed; if rec['xin_pro'] is set it is the gradient w.r.t. the *activated* virtual tensor).
-        pre_tail = (stats_ref, blocks): `d_out` is already g = dOut * leaky'(out) and the tail's BatchNorm-backward sums are in the
+        """Backward of one residual block.  Returns (d_in, pre): d_in = the gradient w.r.t. the block input `xin` (post-activation tensor
+        the block consumed; if rec['xin_pro'] is set it is the gradient w.r.t. the *activated* virtual tensor), pre = None unless
+        tail_next / act_next is given.
+        pre_tail = Stats of the producer: `d_out` is already g = dOut * leaky'(out) and the tail's BatchNorm-backward sums are in the
         statistics partials (the launch that wrote it carried CTL_EPI_TAILBWD).  tail_next = `_tail_of` the block that consumes THIS
-        block's input gradient: the last launch writing it carries the flag; then returns (d_in, stats_ref, blocks).
+        block's input gradient: the last launch writing it carries the flag and pre = its Stats (the consumer's `pre_tail`).
         act_next = (T u, scale_ref, shift_ref, slope): the consumer is a conv-BatchNorm-activation pair with BatchNorm input u (`down`
-        blocks): the last launch carries CTL_EPI_BNBWD, d_in is g = dAct * act'(BN(u)); same return."""
+        blocks): the last launch carries CTL_EPI_BNBWD, d_in is g = dAct * act'(BN(u)), pre = its Stats (the consumer's `pre`)."""
         assert not (tail_next is not None and act_next is not None)
         ep = dict(tail=tail_next) if act_next is None else dict(bnbwd=act_next, keep_stats=True)
         C, B = self._convs, self._bns
@@ -1132,7 +1136,7 @@ class CtlNet(nn.Module):
         if pre_tail is not None:
             assert rec.get("drop") is None
             ds, dv = d_out, (None if virt else A.tensor(out.n, out.h, out.w, out.c))
-            coef2 = pb.bn_backward_from_stats(ds, v, B[prefix + ".conv.4"], rec["co2"], pre_tail[0], pre_tail[1], dx=dv, affine_grad=need_w and affine)
+            coef2 = pb.bn_backward_from_stats(ds, v, B[prefix + ".conv.4"], rec["co2"], pre_tail, dx=dv, affine_grad=need_w and affine)
         else:
             ds, dv = A.tensor(out.n, out.h, out.w, out.c), (None if virt else A.tensor(out.n, out.h, out.w, out.c))
             coef2 = pb.bn_backward(0, d_out, out, v, B[prefix + ".conv.4"], rec["co2"], SLOPE, ds=ds, dx=dv, affine_grad=need_w and affine)
@@ -1153,14 +1157,14 @@ class CtlNet(nn.Module):
         # dgrad of conv.3; its epilogue already multiplies by leaky'(BN1(u)) and takes the BatchNorm-backward sums (no
         # separate reduction pass); the apply runs in place
         if (FUSE_BNBWD and not pb.b16) or (FUSE_BNBWD16 and pb.b16 and dv.b16 and u.b16):
-            g1, st, blk = pb.conv(dv, self._wp_ref(c3.wp_dgrad), c3.cin, 3, arena=A,
-                                  bnbwd=(u, rec["co1"]["scale"], rec["co1"]["shift"], SLOPE), x2=dv2, xout=dv_out)
-            coef1 = pb.bn_backward_from_stats(g1, u, B[prefix + ".conv.1"], rec["co1"], st, blk, dx=None if virt_u else g1, affine_grad=need_w and affine)
+            g1, st = pb.conv(dv, self._wp_ref(c3.wp_dgrad), c3.cin, 3, arena=A,
+                             bnbwd=(u, rec["co1"]["scale"], rec["co1"]["shift"], SLOPE), x2=dv2, xout=dv_out)
+            coef1 = pb.bn_backward_from_stats(g1, u, B[prefix + ".conv.1"], rec["co1"], st, dx=None if virt_u else g1, affine_grad=need_w and affine)
             du = g1
             if virt_u:
                 du2 = (u, coef1)
         else:
-            da, _, _ = pb.conv(dv, self._wp_ref(c3.wp_dgrad), c3.cin, 3, arena=A, x2=dv2, xout=dv_out)
+            da, _ = pb.conv(dv, self._wp_ref(c3.wp_dgrad), c3.cin, 3, arena=A, x2=dv2, xout=dv_out)
             # BN1 -> LeakyReLU tail (in place: dU overwrites dA)
             pb.bn_backward(1, da, None, u, B[prefix + ".conv.1"], rec["co1"], SLOPE, ds=None, dx=da, affine_grad=need_w and affine)
             du = da
@@ -1170,8 +1174,8 @@ class CtlNet(nn.Module):
         if pre == "nn":
             # nearest-upsample backward = 2x2 sum-pool; it commutes with pointwise (1x1) convs, so both the 1x1 weight gradient
             # (sum up(x)*dS == sum x*pool(dS)) and the 1x1 data gradient below run on the pooled dS at a quarter of the pixels
-            if pre_tail is not None and len(pre_tail) > 2 and pre_tail[2] is not None:
-                ds_low = pre_tail[2]            # written by the tail epilogue of the launch that produced dS (FUSE_POOL)
+            if pre_tail is not None and pre_tail.pool is not None:
+                ds_low = pre_tail.pool          # written by the tail epilogue of the launch that produced dS (FUSE_POOL)
             else:
                 ds_low = A.tensor(ds.n, ds.h // 2, ds.w // 2, ds.c)
                 pb.sumpool2(ds, ds_low)
@@ -1195,15 +1199,13 @@ class CtlNet(nn.Module):
             dsrc_shape = (src.n, 2 * src.h, 2 * src.w, src.c)
         if d_in is None:
             d_in = A.tensor(xin.n, xin.h, xin.w, xin.c)
-        fin = lambda st, blk: d_in if (tail_next is None and act_next is None) else (d_in, st, blk, pb.last_pool)
         if pre == "nn":
             # sumpool2(conv3x3^T(dU)) as one 4x4 stride-2 conv (no full-resolution gradient tensor at all), then the 1x1 part
             pb.conv(du, self._wp_ref(c0.wp_up), c0.cin, 4, stride=2, out=d_in, x2=du2, xout=du_out)
             if du_out is not None:
                 wgrads_c0_c1()
             assert act_next is None
-            _, st, blk = pb.conv(ds_low, self._wp_ref(c1.wp_dgrad), c1.cin, 1, out=d_in, accum=True, tail=tail_next)
-            return fin(st, blk)
+            return pb.conv(ds_low, self._wp_ref(c1.wp_dgrad), c1.cin, 1, out=d_in, accum=True, tail=tail_next)
         dsrc = A.tensor(*dsrc_shape)
         pb.conv(du, self._wp_ref(c0.wp_dgrad), c0.cin, 3, out=dsrc, x2=du2, xout=du_out)
         if du_out is not None:
@@ -1216,23 +1218,21 @@ class CtlNet(nn.Module):
                 # role swap: "input" = dsrc (full res), "output gradient" = xin  ->  Wt[ci][co][a][b]
                 pb.wgrad(dsrc, xin, 2, stride=2, dw_ref=pb.G(ci.w_off), strides=(ci.cout * 4, 4, 2, 1))
             assert act_next is None
-            _, st, blk = pb.conv(dsrc, self._wp_ref(ci.wp_dgrad), ci.cin, 2, stride=2, out=d_in, tail=tail_next)
-        else:  # down: stride-2 conv
-            ci = C[prefix + ".down"]
-            if need_w:
-                pb.wgrad(xin, dsrc, 3, stride=2, pro=rec["xin_pro"], dw_ref=pb.G(ci.w_off), strides=(ci.cin * k9, k9, 3, 1),
-                         dbias_ref=pb.G(ci.b_off))
-            if ci.wp_s2d >= 0 and xin.h == 2 * dsrc.h and xin.w == 2 * dsrc.w:
-                _, st, blk = pb.conv(dsrc, self._wp_ref(ci.wp_s2d), ci.cin, 2, nsub=4, pad=0, hout=dsrc.h, wout=dsrc.w, out=d_in, **ep)
-            else:       # odd sizes: 3x3 conv over the zero-inserted gradient
-                _, st, blk = pb.conv(dsrc, self._wp_ref(ci.wp_dgrad), ci.cin, 3, in_mode=_ffi.IN_ZINS2, out=d_in, hout=xin.h, wout=xin.w, **ep)
-        return fin(st, blk)
+            return pb.conv(dsrc, self._wp_ref(ci.wp_dgrad), ci.cin, 2, stride=2, out=d_in, tail=tail_next)
+        ci = C[prefix + ".down"]      # down: stride-2 conv
+        if need_w:
+            pb.wgrad(xin, dsrc, 3, stride=2, pro=rec["xin_pro"], dw_ref=pb.G(ci.w_off), strides=(ci.cin * k9, k9, 3, 1),
+                     dbias_ref=pb.G(ci.b_off))
+        if ci.wp_s2d >= 0 and xin.h == 2 * dsrc.h and xin.w == 2 * dsrc.w:
+            return pb.conv(dsrc, self._wp_ref(ci.wp_s2d), ci.cin, 2, nsub=4, pad=0, hout=dsrc.h, wout=dsrc.w, out=d_in, **ep)
+        # odd sizes: 3x3 conv over the zero-inserted gradient
+        return pb.conv(dsrc, self._wp_ref(ci.wp_dgrad), ci.cin, 3, in_mode=_ffi.IN_ZINS2, out=d_in, hout=xin.h, wout=xin.w, **ep)
 
     def _emit_conv_bn_pair_bwd(self, pb, conv_key, bn_key, x: T, x_pro, u: T, co, slope, d_act: T, d_x: Optional[T], need_w, affine,
                                need_dx=True, tail_next=None, pre=None, act_next=None):
-        """Backward of  a = act(BN(conv3x3/1x1(x)))  given d_act (gradient w.r.t. a).  Returns gradient w.r.t. x
-        (w.r.t. the activated virtual tensor if x_pro is set).
-        pre = (stats_ref, blocks): d_act is already g = dAct * act'(BN(u)) and its BatchNorm-backward sums are in the statistics partials
+        """Backward of  a = act(BN(conv3x3/1x1(x)))  given d_act (gradient w.r.t. a).  Returns (d_x, pre) like _emit_block_bwd: the gradient
+        w.r.t. x (w.r.t. the activated virtual tensor if x_pro is set; None without need_dx) and the Stats of the launch that wrote it.
+        pre = Stats of the producer: d_act is already g = dAct * act'(BN(u)) and its BatchNorm-backward sums are in the statistics partials
         (the launch that wrote it carried CTL_EPI_BNBWD: `act_next` of its producer); the apply pass then runs inside the consumers' staging
         where they can take it (3x3 weight gradient; 3x3 data gradient into a bf16 tensor).  act_next: see _emit_block_bwd."""
         ci, bn = self._convs[conv_key], self._bns[bn_key]
@@ -1248,7 +1248,7 @@ class CtlNet(nn.Module):
             # takes any output width (the shape encoder's 4-channel input gradient)
             stored = need_dx and not (d_x.b16 == pb.b16 and (x.c % 16 == 0 or not pb.b16))
             du = A.tensor(u.n, u.h, u.w, u.c) if stored else None
-            coef = pb.bn_backward_from_stats(d_act, u, bn, co, pre[0], pre[1], dx=du, affine_grad=need_w and affine)
+            coef = pb.bn_backward_from_stats(d_act, u, bn, co, pre, dx=du, affine_grad=need_w and affine)
             if not stored:
                 du, dy2 = d_act, (u, coef)
         else:
@@ -1262,14 +1262,14 @@ class CtlNet(nn.Module):
         if du_out is None:
             wgrad()
         if not need_dx:
-            return None
+            return None, None
         if d_x is None:
             d_x = A.tensor(x.n, x.h, x.w, x.c)
         ep = dict(tail=tail_next) if act_next is None else dict(bnbwd=act_next, keep_stats=True)
-        _, st, blk = pb.conv(du, self._wp_ref(ci.wp_dgrad), ci.cin, ci.ks, out=d_x, x2=dy2, xout=du_out, **ep)
+        _, st = pb.conv(du, self._wp_ref(ci.wp_dgrad), ci.cin, ci.ks, out=d_x, x2=dy2, xout=du_out, **ep)
         if du_out is not None:
             wgrad()
-        return d_x if (tail_next is None and act_next is None) else (d_x, st, blk, pb.last_pool)
+        return d_x, st
 
     # ---------------------------------------------------------------- public compute entry points
     def _alloc_out(self, shape):
@@ -1296,11 +1296,7 @@ class CtlNet(nn.Module):
         key = ("f", n, h, w, mode, groups, self.drop_p, self._drop_keep is not None) + (() if stack is None else (pp,))
         plan = self._plans.get(key)
         if plan is None:
-            self._cur_groups, self._cur_pp = groups, pp
-            try:
-                plan = self._plans[key] = self._compile_forward(n, h, w, mode)
-            finally:
-                self._cur_groups, self._cur_pp = 1, (0, 1)
+            plan = self._plans[key] = self._compile_forward(n, h, w, mode, groups=groups, pp=pp)
         self._check_prologue_tables(plan)
         self.ensure_packed()
         if stack is None:
@@ -1426,11 +1422,8 @@ class CtlNet(nn.Module):
         plan = self._plans.get(key)
         if plan is None:
             view = _StackedForward(_stack_rec(plan0.rec, P), P * G)
-            self._cur_groups, self._cur_affine_mask, self._cur_split = P * G, (0 if amask == full else amask), True
-            try:
-                plan = self._plans[key] = self._compile_backward(view, "A", mask, need_dx, need_w, amask != 0)
-            finally:
-                self._cur_groups, self._cur_affine_mask, self._cur_split = 1, 0, False
+            plan = self._plans[key] = self._compile_backward(view, "A", mask, need_dx, need_w, amask != 0,
+                                                             affine_mask=0 if amask == full else amask, split_tail=True)
         lease = self._arenas.acquire(plan.bscr_bytes, self.device)
         stack.keep.append(lease)          # (the tail may still read the arena on another stream when this call returns: held until the step ends)
         self._dbg_last = (plan, lease.t)
@@ -1468,11 +1461,7 @@ class CtlNet(nn.Module):
         key = ("b", n, h, w, mode, mask, need_dx, need_w, affine, fwd_plan.groups, id(fwd_plan))
         plan = self._plans.get(key)
         if plan is None:
-            self._cur_groups = fwd_plan.groups
-            try:
-                plan = self._plans[key] = self._compile_backward(fwd_plan, mode, mask, need_dx, need_w, affine)
-            finally:
-                self._cur_groups = 1
+            plan = self._plans[key] = self._compile_backward(fwd_plan, mode, mask, need_dx, need_w, affine)
         self._check_prologue_tables(plan)
         lease = self._arenas.acquire(plan.bscr_bytes, self.device)
         bscr = lease.t
@@ -1514,13 +1503,13 @@ class MyEncoder(CtlNet):
         train = mode != "C"
         c0, c3 = C[px + "inc.0"], C[px + "inc.3"]
         if c0.wp_c4 >= 0:
-            u0, st, blk = pb.conv(x, self._wp_ref(c0.wp_c4), c0.cout, 3, in_mode=_ffi.IN_C4, bias_ref=pb.P(c0.b_off), stats=train)
+            u0, st = pb.conv(x, self._wp_ref(c0.wp_c4), c0.cout, 3, in_mode=_ffi.IN_C4, bias_ref=pb.P(c0.b_off), stats=train)
         else:
-            u0, st, blk = pb.conv(x, self._wp_ref(c0.wp_fwd), c0.cout, 3, bias_ref=pb.P(c0.b_off), stats=train)
-        co0 = pb.bn_forward(B[px + "inc.1"], st, blk, u0.n * u0.h * u0.w, mode)
-        v0, st, blk = pb.conv(u0, self._wp_ref(c3.wp_fwd), c3.cout, 3, pro=(co0["scale"], co0["shift"], SLOPE),
-                              bias_ref=pb.P(c3.b_off), stats=train)
-        co1 = pb.bn_forward(B[px + "inc.4"], st, blk, v0.n * v0.h * v0.w, mode)
+            u0, st = pb.conv(x, self._wp_ref(c0.wp_fwd), c0.cout, 3, bias_ref=pb.P(c0.b_off), stats=train)
+        co0 = pb.bn_forward(B[px + "inc.1"], st, u0.n * u0.h * u0.w, mode)
+        v0, st = pb.conv(u0, self._wp_ref(c3.wp_fwd), c3.cout, 3, pro=(co0["scale"], co0["shift"], SLOPE),
+                         bias_ref=pb.P(c3.b_off), stats=train)
+        co1 = pb.bn_forward(B[px + "inc.4"], st, v0.n * v0.h * v0.w, mode)
         rec = {"x": x, "u0": u0, "v0": v0, "co0": co0, "co1": co1, "blocks": []}
         cur, cur_pro = v0, (co1["scale"], co1["shift"], SLOPE)      # x1 = LReLU(BN(v0)) stays virtual
         for i in range(1, 5):
@@ -1528,8 +1517,8 @@ class MyEncoder(CtlNet):
             cur_pro = None
             rec["blocks"].append(brec)
         cf = C[px + "final_conv.0"]
-        uf, st, blk = pb.conv(cur, self._wp_ref(cf.wp_fwd), cf.cout, 1, bias_ref=pb.P(cf.b_off), stats=train)
-        cof = pb.bn_forward(B[px + "final_conv.1"], st, blk, uf.n * uf.h * uf.w, mode)
+        uf, st = pb.conv(cur, self._wp_ref(cf.wp_fwd), cf.cout, 1, bias_ref=pb.P(cf.b_off), stats=train)
+        cof = pb.bn_forward(B[px + "final_conv.1"], st, uf.n * uf.h * uf.w, mode)
         pb.bn_act(uf, cof, 0.0, z_out)                               # act = ReLU
         rec.update(uf=uf, cof=cof, z=z_out, x4=cur)
         return rec
@@ -1539,11 +1528,8 @@ class MyEncoder(CtlNet):
         dbg = {"dz": dz}                 # where the intermediate gradients live (tests read them through CtlNet._dbg_last)
         blocks = rec["blocks"]
         tail = self._tail_of(pb, blocks[-1])
-        d = self._emit_conv_bn_pair_bwd(pb, px + "final_conv.0", px + "final_conv.1", rec["x4"], None, rec["uf"], rec["cof"], 0.0,
-                                        dz, None, need_w, affine, tail_next=tail)
-        pre = None
-        if tail is not None:
-            d, pre = d[0], d[1:]
+        d, pre = self._emit_conv_bn_pair_bwd(pb, px + "final_conv.0", px + "final_conv.1", rec["x4"], None, rec["uf"], rec["cof"], 0.0,
+                                             dz, None, need_w, affine, tail_next=tail)
         dbg["d_down5"] = d               # gradient w.r.t. the output of down4 (with FUSE_TAIL: already times leaky'(out), i.e. dS of down4)
         dbg["tail_down5"] = pre          # ... and where the tail's BatchNorm-backward sums of down4 are (statistics partials ref, rows)
         u0, v0 = rec["u0"], rec["v0"]
@@ -1556,19 +1542,13 @@ class MyEncoder(CtlNet):
         act0 = (u0, rec["co0"]["scale"], rec["co0"]["shift"], SLOPE) if pair16 else None
         for i, brec in reversed(list(enumerate(blocks))):
             tail = self._tail_of(pb, blocks[i - 1]) if i >= 1 else None
-            d = self._emit_block_bwd(pb, brec, d, None, need_w, affine, pre_tail=pre, tail_next=tail, act_next=act1 if i == 0 else None)
-            pre = None
-            if tail is not None or (i == 0 and act1 is not None):
-                d, pre = d[0], d[1:]
+            d, pre = self._emit_block_bwd(pb, brec, d, None, need_w, affine, pre_tail=pre, tail_next=tail, act_next=act1 if i == 0 else None)
             dbg[f"d_down{i + 1}"] = d    # gradient w.r.t. the input of block down{i+1} (down1 with FUSE_PAIR16: g of the inc.3 pair)
             dbg[f"tail_down{i + 1}"] = pre
         # d = gradient w.r.t. x1 = LReLU(BN(v0))
         pro0 = (rec["co0"]["scale"], rec["co0"]["shift"], SLOPE)
-        d = self._emit_conv_bn_pair_bwd(pb, px + "inc.3", px + "inc.4", u0, pro0, v0, rec["co1"], SLOPE, d, None,
-                                        need_w, affine, pre=pre, act_next=act0)
-        pre = None
-        if act0 is not None:
-            d, pre = d[0], d[1:]
+        d, pre = self._emit_conv_bn_pair_bwd(pb, px + "inc.3", px + "inc.4", u0, pro0, v0, rec["co1"], SLOPE, d, None,
+                                             need_w, affine, pre=pre, act_next=act0)
         dbg["d_inc3"], dbg["pre_inc3"] = d, pre
         dx = T((S_DX, 0), *rec["x"][1:]) if need_dx else None
         self._emit_conv_bn_pair_bwd(pb, px + "inc.0", px + "inc.1", rec["x"], None, u0, rec["co0"], SLOPE, d, dx,
@@ -1580,14 +1560,14 @@ class MyEncoder(CtlNet):
             h, w = (h + 1) // 2, (w + 1) // 2
         return (n, h, w, self.chan[4])
 
-    def _compile_forward(self, n, h, w, mode) -> Plan:
-        pb = PlanBuilder(self)
+    def _compile_forward(self, n, h, w, mode, *, groups=1, pp=(0, 1)) -> Plan:
+        pb = PlanBuilder(self, groups=groups, pp=pp)
         zs = self._zdims(n, h, w)
         rec = self._emit_encoder_fwd(pb, T((S_X, 0), n, h, w, self.cin), mode, T((S_OUT0, 0), *zs))
         return pb.finish(rec, [zs])
 
-    def _compile_backward(self, fwd: Plan, mode, mask, need_dx, need_w, affine) -> Plan:
-        pb = PlanBuilder(self)
+    def _compile_backward(self, fwd: Plan, mode, mask, need_dx, need_w, affine, *, affine_mask=0, split_tail=False) -> Plan:
+        pb = PlanBuilder(self, groups=fwd.groups, affine_mask=affine_mask, split_tail=split_tail)
         if need_w:
             pb.zero((S_GRAD, 0), 4 * self._pcount)
         z = fwd.rec["z"]
@@ -1609,25 +1589,29 @@ class Dual_Branch_Encoder(MyEncoder):
                          _spec=_init.dual_encoder_spec(input_channel, z_level_1_channel, feature_reduce),
                          _prefix="general_encoder.", bf16=bf16)
 
-    def _compile_forward(self, n, h, w, mode) -> Plan:
-        pb = PlanBuilder(self)
+    def _emit_decoupler_fwd(self, pb: PlanBuilder, z_i: T, z_s: T, mode: str) -> dict:
+        """z_s = code_decoupler(z_i): conv - BatchNorm - LeakyReLU - conv - BatchNorm - ReLU.  Returns its record entries."""
         C, B = self._convs, self._bns
         train = mode != "C"
+        d0, d3 = C["code_decoupler.0"], C["code_decoupler.3"]
+        ud, st = pb.conv(z_i, self._wp_ref(d0.wp_fwd), d0.cout, 3, bias_ref=pb.P(d0.b_off), stats=train)
+        cod0 = pb.bn_forward(B["code_decoupler.1"], st, ud.n * ud.h * ud.w, mode)
+        vd, st = pb.conv(ud, self._wp_ref(d3.wp_fwd), d3.cout, 3, pro=(cod0["scale"], cod0["shift"], SLOPE),
+                         bias_ref=pb.P(d3.b_off), stats=train)
+        cod1 = pb.bn_forward(B["code_decoupler.4"], st, vd.n * vd.h * vd.w, mode)
+        pb.bn_act(vd, cod1, 0.0, z_s)                                # nn.ReLU at the end of code_decoupler
+        return dict(ud=ud, vd=vd, cod0=cod0, cod1=cod1, z_s=z_s)
+
+    def _compile_forward(self, n, h, w, mode, *, groups=1, pp=(0, 1)) -> Plan:
+        pb = PlanBuilder(self, groups=groups, pp=pp)
         zs = self._zdims(n, h, w)
         z_i, z_s = T((S_OUT0, 0), *zs), T((S_OUT1, 0), *zs)
         rec = self._emit_encoder_fwd(pb, T((S_X, 0), n, h, w, self.cin), mode, z_i)
-        d0, d3 = C["code_decoupler.0"], C["code_decoupler.3"]
-        ud, st, blk = pb.conv(z_i, self._wp_ref(d0.wp_fwd), d0.cout, 3, bias_ref=pb.P(d0.b_off), stats=train)
-        cod0 = pb.bn_forward(B["code_decoupler.1"], st, blk, ud.n * ud.h * ud.w, mode)
-        vd, st, blk = pb.conv(ud, self._wp_ref(d3.wp_fwd), d3.cout, 3, pro=(cod0["scale"], cod0["shift"], SLOPE),
-                              bias_ref=pb.P(d3.b_off), stats=train)
-        cod1 = pb.bn_forward(B["code_decoupler.4"], st, blk, vd.n * vd.h * vd.w, mode)
-        pb.bn_act(vd, cod1, 0.0, z_s)                                # nn.ReLU at the end of code_decoupler
-        rec.update(ud=ud, vd=vd, cod0=cod0, cod1=cod1, z_s=z_s)
+        rec.update(self._emit_decoupler_fwd(pb, z_i, z_s, mode))
         return pb.finish(rec, [zs, zs])
 
-    def _compile_backward(self, fwd: Plan, mode, mask, need_dx, need_w, affine) -> Plan:
-        pb = PlanBuilder(self)
+    def _compile_backward(self, fwd: Plan, mode, mask, need_dx, need_w, affine, *, affine_mask=0, split_tail=False) -> Plan:
+        pb = PlanBuilder(self, groups=fwd.groups, affine_mask=affine_mask, split_tail=split_tail)
         rec = fwd.rec
         if need_w:
             pb.zero((S_GRAD, 0), 4 * self._pcount)
@@ -1637,8 +1621,8 @@ class Dual_Branch_Encoder(MyEncoder):
         if mask[1]:
             dzs = T((S_DOUT1, 0), *z_i[1:])
             pro = (rec["cod0"]["scale"], rec["cod0"]["shift"], SLOPE)
-            d = self._emit_conv_bn_pair_bwd(pb, "code_decoupler.3", "code_decoupler.4", rec["ud"], pro, rec["vd"], rec["cod1"], 0.0,
-                                            dzs, None, need_w, affine)
+            d, _ = self._emit_conv_bn_pair_bwd(pb, "code_decoupler.3", "code_decoupler.4", rec["ud"], pro, rec["vd"], rec["cod1"], 0.0,
+                                               dzs, None, need_w, affine)
             # conv d.0 consumes z_i: its dgrad is added to the gradient arriving at z_i directly
             ci, bn = self._convs["code_decoupler.0"], self._bns["code_decoupler.1"]
             du = pb.bscr.tensor(*rec["ud"][1:])
@@ -1665,16 +1649,8 @@ class Dual_Branch_Encoder(MyEncoder):
     def _compile_filter(self, n, h, w, mode) -> Plan:
         """code_decoupler alone (encoder_decoder.py:496-498): z_i [n, h, w, C] in the input slot -> z_s."""
         pb = PlanBuilder(self)
-        C, B = self._convs, self._bns
-        train = mode != "C"
-        d0, d3 = C["code_decoupler.0"], C["code_decoupler.3"]
-        z_i, z_s = T((S_X, 0), n, h, w, d0.cin), T((S_OUT0, 0), n, h, w, d3.cout)
-        ud, st, blk = pb.conv(z_i, self._wp_ref(d0.wp_fwd), d0.cout, 3, bias_ref=pb.P(d0.b_off), stats=train)
-        cod0 = pb.bn_forward(B["code_decoupler.1"], st, blk, ud.n * ud.h * ud.w, mode)
-        vd, st, blk = pb.conv(ud, self._wp_ref(d3.wp_fwd), d3.cout, 3, pro=(cod0["scale"], cod0["shift"], SLOPE),
-                              bias_ref=pb.P(d3.b_off), stats=train)
-        cod1 = pb.bn_forward(B["code_decoupler.4"], st, blk, vd.n * vd.h * vd.w, mode)
-        pb.bn_act(vd, cod1, 0.0, z_s)
+        d0, d3 = self._convs["code_decoupler.0"], self._convs["code_decoupler.3"]
+        self._emit_decoupler_fwd(pb, T((S_X, 0), n, h, w, d0.cin), T((S_OUT0, 0), n, h, w, d3.cout), mode)
         return pb.finish({}, [(n, h, w, d3.cout)])
 
     def filter_code(self, z):
@@ -1714,8 +1690,8 @@ class MyDecoder(CtlNet):
         self.sigmoid = last_act in ("sigmoid", "Sigmoid") or isinstance(last_act, nn.Sigmoid)
         super().__init__(_init.decoder_spec(input_channel, output_channel, up_type, feature_reduce), input_channel, device, bf16)
 
-    def _compile_forward(self, n, h, w, mode) -> Plan:
-        pb = PlanBuilder(self)
+    def _compile_forward(self, n, h, w, mode, *, groups=1, pp=(0, 1)) -> Plan:
+        pb = PlanBuilder(self, groups=groups, pp=pp)
         cur = T((S_X, 0), n, h, w, self.cin)
         rec = {"x": cur, "blocks": []}
         pre = "nn" if self.up_type == "NN" else "convT"
@@ -1729,8 +1705,8 @@ class MyDecoder(CtlNet):
         rec.update(x4=cur, out=out)
         return pb.finish(rec, [(out.n, out.h, out.w, out.c)])
 
-    def _compile_backward(self, fwd: Plan, mode, mask, need_dx, need_w, affine) -> Plan:
-        pb = PlanBuilder(self)
+    def _compile_backward(self, fwd: Plan, mode, mask, need_dx, need_w, affine, *, affine_mask=0, split_tail=False) -> Plan:
+        pb = PlanBuilder(self, groups=fwd.groups, affine_mask=affine_mask, split_tail=split_tail)
         rec = fwd.rec
         if need_w:
             pb.zero((S_GRAD, 0), 4 * self._pcount)
@@ -1744,16 +1720,12 @@ class MyDecoder(CtlNet):
             pb.wgrad(x4, dout, 1, dw_ref=pb.G(cf.w_off), strides=(cf.cin, 1, 1, 1), dbias_ref=pb.G(cf.b_off))
         blocks = rec["blocks"]
         tail = self._tail_of(pb, blocks[3])
-        d, st, blk = pb.conv(dout, self._wp_ref(cf.wp_dgrad), cf.cin, 1, arena=pb.bscr, tail=tail)
-        pre = (st, blk, pb.last_pool) if tail is not None else None
+        d, pre = pb.conv(dout, self._wp_ref(cf.wp_dgrad), cf.cin, 1, arena=pb.bscr, tail=tail)
         dbg = {"d_out4": d, "tail_out4": pre}
         for i in range(3, -1, -1):
             d_in = T((S_DX, 0), *rec["x"][1:]) if (i == 0 and need_dx) else None
             tail = self._tail_of(pb, blocks[i - 1]) if i >= 1 else None
-            d = self._emit_block_bwd(pb, blocks[i], d, d_in, need_w, affine, pre_tail=pre, tail_next=tail)
-            pre = None
-            if tail is not None:
-                d, pre = d[0], d[1:]
+            d, pre = self._emit_block_bwd(pb, blocks[i], d, d_in, need_w, affine, pre_tail=pre, tail_next=tail)
             dbg[f"d_out{i}"] = d
             dbg[f"tail_out{i}"] = pre
         return pb.finish(dbg)

@@ -32,19 +32,12 @@ def the_rules(image_ch, num_classes, reduce_factor, dtype):
 
 
 def compile_forward(net, n, h, w, mode, groups=1):
-    net._cur_groups, net._cur_pp = groups, (0, 1)
-    try:
-        return net._compile_forward(n, h, w, mode)
-    finally:
-        net._cur_groups, net._cur_pp = 1, (0, 1)
+    return net._compile_forward(n, h, w, mode, groups=groups)
 
 
 def compile_backward(net, fwd, groups, mask, need_dx):
-    net._cur_groups = groups
-    try:
-        return net._compile_backward(fwd, "A", mask, need_dx, True, True)
-    finally:
-        net._cur_groups = 1
+    assert fwd.groups == groups                    # a backward plan has the BatchNorm groups of its forward pass
+    return net._compile_backward(fwd, "A", mask, need_dx, True, True)
 
 
 def conv_of(op):

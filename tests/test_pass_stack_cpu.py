@@ -13,19 +13,12 @@ from cooperative_training_and_latent_space_data_augmentation_amd.nets import T, 
 
 
 def compile_forward(net, n, h, w, mode, groups=1, pp=(0, 1)):
-    net._cur_groups, net._cur_pp = groups, pp
-    try:
-        return net._compile_forward(n, h, w, mode)
-    finally:
-        net._cur_groups, net._cur_pp = 1, (0, 1)
+    return net._compile_forward(n, h, w, mode, groups=groups, pp=pp)
 
 
-def compile_backward(net, fwd, groups, mask, need_dx, amask=0):
-    net._cur_groups, net._cur_affine_mask = groups, amask
-    try:
-        return net._compile_backward(fwd, "A", mask, need_dx, True, True)
-    finally:
-        net._cur_groups, net._cur_affine_mask = 1, 0
+def compile_backward(net, fwd, groups, mask, need_dx, amask=0, split_tail=False):
+    assert fwd.groups == groups                    # a backward plan has the BatchNorm groups of its forward pass
+    return net._compile_backward(fwd, "A", mask, need_dx, True, True, affine_mask=amask, split_tail=split_tail)
 
 
 def tensors_of(obj, out):
@@ -94,6 +87,38 @@ def test_mode_b_passes_are_masked_out_of_the_affine_gradients():
     assert all(int(o["i"][4]) == 0 for o in b_all.ops if int(o["kind"]) == _ffi.OP_BN_BWD_FINALIZE)
 
 
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("name,h", [("image_encoder", 32), ("segmentation_decoder", 4)])
+def test_nothing_of_one_compile_reaches_the_next(name, h, dtype):
+    """The compile parameters are arguments: after a grouped pass-slot forward and a masked, split backward on the same network object,
+    plans compiled with the default arguments are byte for byte those of a freshly built network."""
+    mask = (True, True) if name == "image_encoder" else (True,)
+
+    def default_pair(net):
+        f = net._compile_forward(2, h, h, "A")
+        return f, net._compile_backward(f, "A", mask, True, True, True)
+
+    def same(a, b):
+        sizes = lambda p: (p.n_ops, p.act_bytes, p.scr_bytes, p.bscr_bytes, p.out_shapes, p.groups, p.pro_entries, len(p.bn_log))
+        assert a.ops.tobytes() == b.ops.tobytes() and sizes(a) == sizes(b) and a.rec == b.rec
+        assert a.main_ops is b.main_ops is None and a.tail_ops is b.tail_ops is None
+        assert (a.table_np is None) == (b.table_np is None) and (a.table_np is None or a.table_np.tobytes() == b.table_np.tobytes())
+
+    torch.manual_seed(0)
+    net = nets.build_networks(device="cpu", dtype=dtype)[name]
+    f2 = net._compile_forward(2, h, h, "A", groups=2, pp=(1, 2))
+    b2 = net._compile_backward(f2, "A", mask, True, True, True, affine_mask=1, split_tail=True)
+    assert f2.groups == b2.groups == 2 and b2.main_ops is not None
+    assert any(int(o["i"][4]) == 1 for o in b2.ops if int(o["kind"]) == _ffi.OP_BN_BWD_FINALIZE)
+    used = default_pair(net)
+    torch.manual_seed(0)
+    fresh = default_pair(nets.build_networks(device="cpu", dtype=dtype)[name])
+    for a, b in zip(used, fresh):
+        same(a, b)
+    assert used[0].groups == used[1].groups == 1 and used[0].act_bytes < f2.act_bytes       # (one slot of one group, not two stacked ones)
+    assert all(int(o["i"][4]) == 0 for o in used[1].ops if int(o["kind"]) == _ffi.OP_BN_BWD_FINALIZE)
+
+
 def test_gather_stacked_uses_views_of_one_allocation_without_a_copy():
     alloc = lambda s: torch.empty((s[0], s[3], s[1], s[2]), memory_format=torch.channels_last)
     base = torch.randn(8, 16, 4, 4).contiguous(memory_format=torch.channels_last)
@@ -120,11 +145,7 @@ def test_split_backward_plan_is_the_plan_with_the_weight_gradient_family_moved_b
     p0 = compile_forward(net, 4, h, w, "A", 1, (0, 2))
     view = _StackedForward(_stack_rec(p0.rec, 2), 2)
     mask = (True, True) if name == "image_encoder" else (True,)
-    net._cur_split = True
-    try:
-        b = compile_backward(net, view, 2, mask, name != "image_encoder")
-    finally:
-        net._cur_split = False
+    b = compile_backward(net, view, 2, mask, name != "image_encoder", split_tail=True)
     assert b.main_ops is not None and b.tail_ops is not None and len(b.main_ops) + len(b.tail_ops) == b.n_ops
     from collections import Counter
     key = lambda o: o.tobytes()

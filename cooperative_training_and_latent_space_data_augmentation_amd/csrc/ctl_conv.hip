@@ -54,6 +54,7 @@ extern "C" int ctl_debug_timing(unsigned long long* out8) {
 #define TM_FLUSH
 #endif
 #include "ctl_conv_igemm.h"
+#include "ctl_conv_host.h"
 
 
 #ifndef CTL_WGRAD_PIPE_ASM_MFMA
@@ -918,44 +919,27 @@ extern "C" int ctl_pack_weights(const float* src, float* dst, int32_t cout, int3
     return CTL_OK;
 }
 
-struct conv_call {
-    const ctl_conv* d; ctl_conv_cfg c;
-    const float *x, *wpack, *bias, *pro_scale, *pro_shift, *res, *res_scale, *res_shift, *res2, *x2;
-    float *y, *stats_partial, *pool, *xout;
-    hipStream_t stream;
-    bool query;      // only report the grid (ctl_conv_stats_blocks), launch nothing
-    int grid_x;
-};
-
 template <int KS, int S, int MODE, int MT, int TW, int NT, int EPI, bool X2 = false>
-static void conv_go(conv_call& a) {
+static void conv_go(ctl_conv_call& a) {
     if constexpr (!X2 && ((KS == 3 && S == 1 && MODE == CTL_IN_PLAIN) || (KS == 4 && S == 2)) && EPI != 2) {
         if (a.d->pro_affine == 2) { conv_go<KS, S, MODE, MT, TW, NT, EPI, true>(a); return; }      // the BatchNorm-backward prologue (checked in ctl_conv_forward_ex)
     }
-    static int occ = 0;          // resident blocks per CU of this instantiation (asked once)
-    if (!occ) {
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv_igemm_kernel<KS, S, MODE, MT, TW, NT, EPI, X2>, 256, 0) != hipSuccess || n < 1) {
-            (void)hipGetLastError();
-            n = 2;
-        }
-        occ = n;
-    }
+    static const int occ = ctl_resident_blocks(conv_igemm_kernel<KS, S, MODE, MT, TW, NT, EPI, X2>, 2);      // of this instantiation (asked once)
     const ctl_conv* d = a.d;
     const int ntiles = d->n * a.c.tiles_h * a.c.tiles_w;
     a.grid_x = ctl_conv_grid_x(ntiles, (a.c.cot / NT) * d->nsub, occ);
     if (a.query) return;
     const dim3 grid((unsigned)a.grid_x, (unsigned)(a.c.cot / NT), (unsigned)d->nsub);
     conv_igemm_kernel<KS, S, MODE, MT, TW, NT, EPI, X2><<<grid, dim3(256), 0, a.stream>>>(
-        *d, a.x, a.wpack, a.bias, a.pro_scale, a.pro_shift, a.res, a.res_scale, a.res_shift, a.y, a.stats_partial, a.c.tiles_h,
-        a.c.tiles_w, a.c.g, (int64_t)ctl_conv_wpack_floats(d->cin, d->cout, d->ks), ntiles, a.res2, a.x2, a.pool, a.xout);
+        *d, ctl_f(a.x), ctl_f(a.wpack), a.bias, a.pro_scale, a.pro_shift, ctl_f(a.res), a.res_scale, a.res_shift, ctl_f(a.y), a.stats_partial, a.c.tiles_h,
+        a.c.tiles_w, a.c.g, (int64_t)ctl_conv_wpack_floats(d->cin, d->cout, d->ks), ntiles, ctl_f(a.res2), ctl_f(a.x2), ctl_f(a.pool), ctl_f(a.xout));
 }
 // the launches that write dL/dOut of a residual block (and can carry CTL_EPI_TAILBWD): the 1x1 data gradients, the 2x2 stride-2 conv
 // behind a ConvTranspose2d, the four phase problems / the zero-insert form of a stride-2 3x3 data gradient
 template <int KS, int S, int MODE>
 constexpr bool conv_tail_ok() { return (KS == 1 && MODE == CTL_IN_PLAIN) || KS == 2 || (KS == 3 && S == 1 && MODE == CTL_IN_ZINS2); }
 template <int KS, int S, int MODE, int MT, int TW>
-static void conv_go_nt(conv_call& a) {
+static void conv_go_nt(ctl_conv_call& a) {
     const bool epi = (a.d->epi_flags & (CTL_EPI_RES | CTL_EPI_ACCUM | CTL_EPI_BNBWD)) != 0;
     if constexpr (conv_tail_ok<KS, S, MODE>()) {
         if (a.d->epi_flags & CTL_EPI_TAILBWD) {
@@ -973,36 +957,29 @@ static void conv_go_nt(conv_call& a) {
     else { if (epi) conv_go<KS, S, MODE, MT, TW, 1, 1>(a); else conv_go<KS, S, MODE, MT, TW, 1, 0>(a); }
 }
 template <int KS, int S, int MODE>
-static void conv_go_tile(conv_call& a) {
+static void conv_go_tile(ctl_conv_call& a) {
     if (S == 1 && a.c.mt == 4 && a.c.tw == 32) conv_go_nt<KS, S, MODE, (S == 1 ? 4 : 2), (S == 1 ? 32 : 16)>(a);
     else if (a.c.mt == 2) conv_go_nt<KS, S, MODE, 2, 16>(a);
     else conv_go_nt<KS, S, MODE, 1, 16>(a);
 }
-static int conv_dispatch(conv_call& a) {
-    const int k = a.d->ks, s = a.d->stride, m = a.d->in_mode;
-    if (k == 3 && s == 1 && m == CTL_IN_PLAIN) conv_go_tile<3, 1, CTL_IN_PLAIN>(a);
-    else if (k == 3 && s == 1 && m == CTL_IN_UP2) conv_go_tile<3, 1, CTL_IN_UP2>(a);
-    else if (k == 3 && s == 1 && m == CTL_IN_ZINS2) conv_go_tile<3, 1, CTL_IN_ZINS2>(a);
-    else if (k == 3 && s == 1 && m == CTL_IN_C4) conv_go_tile<3, 1, CTL_IN_C4>(a);
-    else if (k == 3 && s == 2) conv_go_tile<3, 2, CTL_IN_PLAIN>(a);
-    else if (k == 1 && m == CTL_IN_PLAIN) conv_go_tile<1, 1, CTL_IN_PLAIN>(a);
-    else if (k == 1 && m == CTL_IN_UP2) conv_go_tile<1, 1, CTL_IN_UP2>(a);
-    else if (k == 2 && s == 2) conv_go_tile<2, 2, CTL_IN_PLAIN>(a);
-    else if (k == 2 && s == 1) conv_go_tile<2, 1, CTL_IN_PLAIN>(a);
-    else if (k == 4 && s == 2) {          // only the LDS-feasible shapes are instantiated
-        const bool epi = (a.d->epi_flags & (CTL_EPI_RES | CTL_EPI_ACCUM | CTL_EPI_BNBWD)) != 0;
-        if (a.c.mt == 2 && a.c.nt == 1) { if (epi) conv_go<4, 2, CTL_IN_PLAIN, 2, 16, 1, 1>(a); else conv_go<4, 2, CTL_IN_PLAIN, 2, 16, 1, 0>(a); }
-        else if (a.c.nt == 2) { if (epi) conv_go<4, 2, CTL_IN_PLAIN, 1, 16, 2, 1>(a); else conv_go<4, 2, CTL_IN_PLAIN, 1, 16, 2, 0>(a); }
-        else { if (epi) conv_go<4, 2, CTL_IN_PLAIN, 1, 16, 1, 1>(a); else conv_go<4, 2, CTL_IN_PLAIN, 1, 16, 1, 0>(a); }
-    }
-    else CTL_FAIL(CTL_EUNSUPPORTED, "conv_forward: no kernel for this combination");
+static int conv_dispatch(ctl_conv_call& a) {
+    const bool built = ctl_visit_shape(a.d->ks, a.d->stride, a.d->in_mode, [&](auto K, auto S, auto M) {
+        if constexpr (K == 4) {          // only the LDS-feasible shapes are instantiated
+            const bool epi = (a.d->epi_flags & (CTL_EPI_RES | CTL_EPI_ACCUM | CTL_EPI_BNBWD)) != 0;
+            if (a.c.mt == 2 && a.c.nt == 1) { if (epi) conv_go<4, 2, CTL_IN_PLAIN, 2, 16, 1, 1>(a); else conv_go<4, 2, CTL_IN_PLAIN, 2, 16, 1, 0>(a); }
+            else if (a.c.nt == 2) { if (epi) conv_go<4, 2, CTL_IN_PLAIN, 1, 16, 2, 1>(a); else conv_go<4, 2, CTL_IN_PLAIN, 1, 16, 2, 0>(a); }
+            else { if (epi) conv_go<4, 2, CTL_IN_PLAIN, 1, 16, 1, 1>(a); else conv_go<4, 2, CTL_IN_PLAIN, 1, 16, 1, 0>(a); }
+        } else conv_go_tile<K, S, M>(a);
+        return true;
+    });
+    if (!built) CTL_FAIL(CTL_EUNSUPPORTED, "conv_forward: no kernel for this combination");
     return CTL_OK;
 }
 
 extern "C" int ctl_conv_stats_blocks(const ctl_conv* d) {
     if (d->dt & CTL_DT_BF16) return ctl_conv_bf16_stats_blocks(d);
     if (d->dt & CTL_DT_X3) return ctl_conv_x3_stats_blocks(d);
-    conv_call a = {};
+    ctl_conv_call a = {};
     a.d = d;
     if (ctl_conv_pick_cfg(d, &a.c, 0) != CTL_OK) return -1;
     a.query = true;
@@ -1038,7 +1015,7 @@ extern "C" int ctl_conv_forward_ex(const ctl_conv* d, const float* x, const floa
     CTL_REQUIRE(!xout || d->pro_affine == 2, "conv_forward: `xout` (the virtual input written out) goes with the BatchNorm-backward prologue (pro_affine 2)");
     CTL_REQUIRE(!pool || ctl_conv_pool_ok(d), "conv_forward: `pool` needs a CTL_EPI_TAILBWD 1x1 conv with even output sizes whose tile configuration gives every wave a row pair (ctl_conv_pool_ok)");
     CTL_REQUIRE((d->dt & CTL_DT_BF16) || !(d->dt & (CTL_DT_X16 | CTL_DT_Y16 | CTL_DT_RES16)), "conv_forward: bf16-stored tensors need CTL_DT_BF16");
-    conv_call a = {};
+    ctl_conv_call a = {};
     a.d = d;
     int rc = ctl_conv_pick_cfg(d, &a.c, 0);
     if (rc != CTL_OK) return rc;
@@ -1093,31 +1070,12 @@ extern "C" int ctl_conv_forward_ex(const ctl_conv* d, const float* x, const floa
 #ifndef CTL_WGRAD_PIPE
 #define CTL_WGRAD_PIPE 1
 #endif
-struct wgrad_cfg { ctl_conv_cfg c; int ntw, splits, ntiles, cin_p, cout_p; };
-
-struct wgrad_call {
-    const ctl_conv* d; wgrad_cfg* w;
-    const float *x, *pro_scale, *pro_shift, *dy, *dy2, *dy_coef;
-    float *w_partial, *b_partial;
-    hipStream_t stream;
-    bool query;          // only compute w->splits
-};
-
 // splits = blocks along x: the grid (splits x cin chunks x cout tile groups) is what is resident at once (256 CUs x the
 // kernel's occupancy, at most CTL_PERSIST = 4 per CU).  More blocks would run in rounds and pay the per-block setup and the
 // cross-wave reduction + partial write again (each ~1.5 tiles worth of time), and write / re-read more partials.
 template <int KS, int S, int MODE, int MT, int TW, int NTW>
-static void wgrad_go(wgrad_call& a) {
-    static int occ = 0;
-    if (!occ) {
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv_wgrad_kernel<KS, S, MODE, MT, TW, NTW>, 256, 0) != hipSuccess || n < 1) {
-            (void)hipGetLastError();
-            n = 2;
-        }
-        occ = n;
-    }
-    wgrad_cfg& w = *a.w;
+static void wgrad_go(ctl_wgrad_call& a) {
+    static const int occ = ctl_resident_blocks(conv_wgrad_kernel<KS, S, MODE, MT, TW, NTW>, 2);
     static int per_cu = -1;
     if (per_cu < 0) {
         // ONE block per CU: the weight gradients co-run with the other launch chain, and every block costs a partial tensor that the
@@ -1126,101 +1084,91 @@ static void wgrad_go(wgrad_call& a) {
         per_cu = ctl_tune_int("CTL_WGRAD_PERSIST", 1);
         if (per_cu < 1) per_cu = 1;
     }
-    const int par = w.c.g * (w.c.cot / NTW);
+    const int par = a.c.g * (a.c.cot / NTW);
     static const int slots = ctl_tune_int("CTL_WGRAD_SLOTS", 0);      // tuning hook: total blocks
     // (the HBM-side members of the family -- 1x1 convs, the <= 4-channel first layers -- run at 0.28 of 8 TB/s with one block per CU and
     // 0.37 with two or four.  While the backward still had its element-wise passes the STEP was no faster for it (17.37-17.53 vs
     // 17.43-17.59 ms); without them two blocks give 16.80 -> 16.72 ms, four 16.79: tuning hook CTL_WGRAD_NARROW_PERSIST)
     static const int narrow_cu = ctl_tune_int("CTL_WGRAD_NARROW_PERSIST", 2);
     const int cu_blocks = (KS == 1 || MODE == CTL_IN_C4) ? narrow_cu : per_cu;
-    int splits = (slots > 0 ? slots : ctl_num_cus() * (occ < cu_blocks ? occ : cu_blocks)) / par;
-    if (splits > 512) splits = 512;
-    if (splits > w.ntiles) splits = w.ntiles;
-    if (splits < 1) splits = 1;
-    w.splits = splits;
+    const int splits = a.splits = ctl_wgrad_clamp_splits(slots > 0 ? slots : ctl_num_cus() * (occ < cu_blocks ? occ : cu_blocks), par, 512, a.ntiles);
     if (a.query) return;
-    const dim3 grid((unsigned)splits, (unsigned)w.c.g, (unsigned)(w.c.cot / NTW));
+    const dim3 grid((unsigned)splits, (unsigned)a.c.g, (unsigned)(a.c.cot / NTW));
     if constexpr (KS == 3 && S == 1 && MODE != CTL_IN_C4) {
         // Two LDS images, staging inside the MFMA stream.  Measured alone (profiles/r3_wgrad_pipe.txt): with the two-tensor output
         // gradient 5-8 % faster than the single-image loop on layers with >= 16 tiles per block (its extra loads and FMAs ride behind
         // the MFMAs), equal without it, 10 % slower at 4 tiles per block (one more exposed load latency per block) -> 1 = the
         // two-tensor launches with >= 8 tiles per block, 2 = every eligible launch, 0 = off
         static const int pipe = ctl_tune_int("CTL_WGRAD_PIPE", CTL_WGRAD_PIPE);
-        const bool pipe_on = pipe >= 2 || (pipe == 1 && a.dy2 && w.ntiles >= 8 * splits);
+        const bool pipe_on = pipe >= 2 || (pipe == 1 && a.dy2 && a.ntiles >= 8 * splits);
         if (pipe_on && a.d->cin % 4 == 0 && a.d->cout % 4 == 0 && a.d->cin <= CTL_PRO_MAX) {
             if (a.dy2)
                 conv_wgrad_kernel<KS, S, MODE, MT, TW, NTW, true, true><<<grid, dim3(256), 0, a.stream>>>(
-                    *a.d, a.x, a.pro_scale, a.pro_shift, a.dy, a.w_partial, a.b_partial, w.c.tiles_h, w.c.tiles_w, w.ntiles, w.cin_p, w.cout_p, a.dy2, a.dy_coef);
+                    *a.d, ctl_f(a.x), a.pro_scale, a.pro_shift, ctl_f(a.dy), a.w_partial, a.b_partial, a.c.tiles_h, a.c.tiles_w, a.ntiles, a.cin_p, a.cout_p, ctl_f(a.dy2), a.dy_coef);
             else
                 conv_wgrad_kernel<KS, S, MODE, MT, TW, NTW, false, true><<<grid, dim3(256), 0, a.stream>>>(
-                    *a.d, a.x, a.pro_scale, a.pro_shift, a.dy, a.w_partial, a.b_partial, w.c.tiles_h, w.c.tiles_w, w.ntiles, w.cin_p, w.cout_p, nullptr, nullptr);
+                    *a.d, ctl_f(a.x), a.pro_scale, a.pro_shift, ctl_f(a.dy), a.w_partial, a.b_partial, a.c.tiles_h, a.c.tiles_w, a.ntiles, a.cin_p, a.cout_p, nullptr, nullptr);
             return;
         }
     }
     if constexpr (KS == 3 && S == 1) {      // the two-tensor output gradient: the 3x3 convs of the residual blocks and of the encoder heads
         if (a.dy2) {
             conv_wgrad_kernel<KS, S, MODE, MT, TW, NTW, true><<<grid, dim3(256), 0, a.stream>>>(
-                *a.d, a.x, a.pro_scale, a.pro_shift, a.dy, a.w_partial, a.b_partial, w.c.tiles_h, w.c.tiles_w, w.ntiles, w.cin_p, w.cout_p, a.dy2, a.dy_coef);
+                *a.d, ctl_f(a.x), a.pro_scale, a.pro_shift, ctl_f(a.dy), a.w_partial, a.b_partial, a.c.tiles_h, a.c.tiles_w, a.ntiles, a.cin_p, a.cout_p, ctl_f(a.dy2), a.dy_coef);
             return;
         }
     }
     conv_wgrad_kernel<KS, S, MODE, MT, TW, NTW><<<grid, dim3(256), 0, a.stream>>>(
-        *a.d, a.x, a.pro_scale, a.pro_shift, a.dy, a.w_partial, a.b_partial, w.c.tiles_h, w.c.tiles_w, w.ntiles, w.cin_p, w.cout_p, nullptr, nullptr);
+        *a.d, ctl_f(a.x), a.pro_scale, a.pro_shift, ctl_f(a.dy), a.w_partial, a.b_partial, a.c.tiles_h, a.c.tiles_w, a.ntiles, a.cin_p, a.cout_p, nullptr, nullptr);
 }
 template <int KS, int S, int MODE>
-static void wgrad_go_tile(wgrad_call& a) {
-    const wgrad_cfg& w = *a.w;
-    if (w.c.mt == 2) { if (w.ntw == 2) wgrad_go<KS, S, MODE, 2, 16, 2>(a); else wgrad_go<KS, S, MODE, 2, 16, 1>(a); }
-    else { if (w.ntw == 2) wgrad_go<KS, S, MODE, 1, 16, 2>(a); else wgrad_go<KS, S, MODE, 1, 16, 1>(a); }
+static void wgrad_go_tile(ctl_wgrad_call& a) {
+    if (a.c.mt == 2) { if (a.ntw == 2) wgrad_go<KS, S, MODE, 2, 16, 2>(a); else wgrad_go<KS, S, MODE, 2, 16, 1>(a); }
+    else { if (a.ntw == 2) wgrad_go<KS, S, MODE, 1, 16, 2>(a); else wgrad_go<KS, S, MODE, 1, 16, 1>(a); }
 }
-static int wgrad_dispatch(wgrad_call& a) {
-    const int k = a.d->ks, s = a.d->stride, m = a.d->in_mode;
-    if (k == 3 && s == 1 && m == CTL_IN_PLAIN) wgrad_go_tile<3, 1, CTL_IN_PLAIN>(a);
-    else if (k == 3 && s == 1 && m == CTL_IN_UP2) wgrad_go_tile<3, 1, CTL_IN_UP2>(a);
-    else if (k == 3 && s == 1 && m == CTL_IN_C4) wgrad_go_tile<3, 1, CTL_IN_C4>(a);
-    else if (k == 3 && s == 2) wgrad_go_tile<3, 2, CTL_IN_PLAIN>(a);
-    else if (k == 1 && m == CTL_IN_PLAIN) wgrad_go_tile<1, 1, CTL_IN_PLAIN>(a);
-    else if (k == 1 && m == CTL_IN_UP2) wgrad_go_tile<1, 1, CTL_IN_UP2>(a);
-    else if (k == 2 && s == 2) wgrad_go_tile<2, 2, CTL_IN_PLAIN>(a);
-    else CTL_FAIL(CTL_EUNSUPPORTED, "conv_wgrad: no kernel for this combination");
+static int wgrad_dispatch(ctl_wgrad_call& a) {
+    const bool built = ctl_visit_shape(a.d->ks, a.d->stride, a.d->in_mode, [&](auto K, auto S, auto M) {
+        if constexpr (K == 4 || (K == 2 && S == 1) || M == CTL_IN_ZINS2) return false;      // (forward-type launches only)
+        else { wgrad_go_tile<K, S, M>(a); return true; }
+    });
+    if (!built) CTL_FAIL(CTL_EUNSUPPORTED, "conv_wgrad: no kernel for this combination");
     return CTL_OK;
 }
 
-static int wgrad_pick(const ctl_conv* d, wgrad_cfg* w) {
+static int wgrad_pick(const ctl_conv* d, ctl_wgrad_call* a) {
     CTL_REQUIRE(d->nsub == 1, "wgrad: nsub must be 1");
     CTL_REQUIRE(d->in_mode != CTL_IN_ZINS2, "wgrad: zero-insert input is not a forward mode");
-    int rc = ctl_conv_pick_cfg(d, &w->c, 1);
+    a->d = d;
+    int rc = ctl_conv_pick_cfg(d, &a->c, 1);
     if (rc != CTL_OK) return rc;
-    w->ntw = (w->c.cot >= 2 && w->c.cot % 2 == 0) ? 2 : 1;
-    w->ntiles = d->n * w->c.tiles_h * w->c.tiles_w;
-    w->cin_p = w->c.g * 16;
-    w->cout_p = w->c.cot * 16;
+    ctl_wgrad_geometry(*a);
     if (d->dt & CTL_DT_BF16) {            // the bf16 kernels have their own occupancy, hence their own split count
-        w->splits = ctl_wgrad_bf16_splits(d);
-        return w->splits > 0 ? CTL_OK : CTL_EUNSUPPORTED;
+        a->splits = ctl_wgrad_bf16_splits(d);
+        return a->splits > 0 ? CTL_OK : CTL_EUNSUPPORTED;
     }
     if (d->dt & CTL_DT_X3) {              // ... and so has the X3 kernel (ctl_wgrad_x3.hip)
-        w->splits = ctl_wgrad_x3_splits(d);
-        return w->splits > 0 ? CTL_OK : CTL_EUNSUPPORTED;
+        a->splits = ctl_wgrad_x3_splits(d);
+        return a->splits > 0 ? CTL_OK : CTL_EUNSUPPORTED;
     }
-    wgrad_call a = {};
-    a.d = d; a.w = w; a.query = true;
-    return wgrad_dispatch(a);
+    a->query = true;
+    rc = wgrad_dispatch(*a);
+    a->query = false;
+    return rc;
 }
 
 extern "C" int ctl_wgrad_splits(const ctl_conv* d) {
-    wgrad_cfg w;
-    return wgrad_pick(d, &w) == CTL_OK ? w.splits : -1;
+    ctl_wgrad_call a = {};
+    return wgrad_pick(d, &a) == CTL_OK ? a.splits : -1;
 }
 extern "C" size_t ctl_wgrad_partial_floats(const ctl_conv* d) {
-    wgrad_cfg w;
-    if (wgrad_pick(d, &w) != CTL_OK) return 0;
-    return (size_t)w.splits * d->ks * d->ks * w.cin_p * w.cout_p;
+    ctl_wgrad_call a = {};
+    if (wgrad_pick(d, &a) != CTL_OK) return 0;
+    return (size_t)a.splits * d->ks * d->ks * a.cin_p * a.cout_p;
 }
 extern "C" size_t ctl_wgrad_bias_partial_floats(const ctl_conv* d) {
-    wgrad_cfg w;
-    if (wgrad_pick(d, &w) != CTL_OK) return 0;
-    return (size_t)w.splits * w.cout_p;
+    ctl_wgrad_call a = {};
+    if (wgrad_pick(d, &a) != CTL_OK) return 0;
+    return (size_t)a.splits * a.cout_p;
 }
 
 extern "C" int ctl_conv_wgrad(const ctl_conv* d, const float* x, const float* pro_scale, const float* pro_shift,
@@ -1230,31 +1178,21 @@ extern "C" int ctl_conv_wgrad(const ctl_conv* d, const float* x, const float* pr
 extern "C" int ctl_conv_wgrad_ex(const ctl_conv* d, const float* x, const float* pro_scale, const float* pro_shift,
                                  const float* dy, const float* dy2, const float* dy_coef, float* w_partial, float* b_partial,
                                  ctl_stream stream) {
-    CTL_REQUIRE(d && x && dy && w_partial, "conv_wgrad: null argument");
-    CTL_REQUIRE(d->pro_affine == 0 || d->pro_affine == 1, "conv_wgrad: pro_affine must be 0 or 1");
-    CTL_REQUIRE(!dy2 || (dy_coef && d->ks == 3 && d->stride == 1 && d->cout % 16 == 0 &&
-                         (d->groups > 1 ? d->groups : 1) * d->cout <= CTL_PRO_MAX),
-                "conv_wgrad: the two-tensor output gradient needs coefficients, a 3x3 stride-1 conv, cout %% 16 == 0 and groups * cout <= %d (got cout %d)", CTL_PRO_MAX, d->cout);
-    CTL_REQUIRE(!d->pro_affine || (pro_scale && pro_shift), "conv_wgrad: prologue without scale/shift");
-    CTL_REQUIRE(!d->pro_affine || (d->groups > 1 ? d->groups : 1) * d->cin <= CTL_PRO_MAX, "conv_wgrad: groups * cin = %d prologue coefficients exceed %d", (d->groups > 1 ? d->groups : 1) * d->cin, CTL_PRO_MAX);
-    CTL_REQUIRE(!d->pro_affine || (d->pro_slope >= 0.f && d->pro_slope <= 1.f), "conv_wgrad: prologue slope must be in [0, 1]");
-    CTL_REQUIRE((int64_t)d->n * d->hin * d->win * d->cin * 4 < (1ll << 31) &&
-                (int64_t)d->n * d->hout * d->wout * d->cout * 4 < (1ll << 31),
-                "conv_wgrad: tensors must stay below 2 GiB (32-bit buffer offsets)");
-    wgrad_cfg w;
-    int rc = wgrad_pick(d, &w);
+    int rc = ctl_wgrad_check(d, x, pro_scale, pro_shift, dy, dy2, dy_coef, w_partial, "conv_wgrad", -1);
+    if (rc != CTL_OK) return rc;
+    ctl_wgrad_call a = {};
+    rc = wgrad_pick(d, &a);
     if (rc != CTL_OK) return rc;
     if (d->dt & CTL_DT_X3) return ctl_conv_wgrad_x3(d, x, pro_scale, pro_shift, dy, dy2, dy_coef, w_partial, b_partial, stream);
     if (d->dt & CTL_DT_BF16) {
-        const int ptok16 = ctl_prof_begin("conv_wgrad_bf16", d, &w.c, w.ntw, (hipStream_t)stream, dy2 != nullptr);
+        const int ptok16 = ctl_prof_begin("conv_wgrad_bf16", d, &a.c, a.ntw, (hipStream_t)stream, dy2 != nullptr);
         rc = ctl_conv_wgrad_bf16(d, x, pro_scale, pro_shift, dy, dy2, dy_coef, w_partial, b_partial, stream);
         ctl_prof_end(ptok16, (hipStream_t)stream);
         return rc;
     }
-    wgrad_call a = {};
-    a.d = d; a.w = &w; a.x = x; a.pro_scale = pro_scale; a.pro_shift = pro_shift; a.dy = dy; a.dy2 = dy2; a.dy_coef = dy_coef; a.w_partial = w_partial;
+    a.x = x; a.pro_scale = pro_scale; a.pro_shift = pro_shift; a.dy = dy; a.dy2 = dy2; a.dy_coef = dy_coef; a.w_partial = w_partial;
     a.b_partial = b_partial; a.stream = (hipStream_t)stream;
-    const int ptok = ctl_prof_begin("conv_wgrad", d, &w.c, w.ntw, a.stream, dy2 != nullptr);
+    const int ptok = ctl_prof_begin("conv_wgrad", d, &a.c, a.ntw, a.stream, dy2 != nullptr);
     rc = wgrad_dispatch(a);
     if (rc != CTL_OK) return rc;
     ctl_prof_end(ptok, a.stream);
@@ -1267,7 +1205,7 @@ extern "C" int ctl_wgrad_reduce(const ctl_conv* d, const float* w_partial, const
                                 int32_t accumulate, ctl_stream stream) {
     CTL_REQUIRE(d && w_partial && dw, "wgrad_reduce: null argument");
     CTL_REQUIRE(!dbias || b_partial, "wgrad_reduce: dbias without b_partial");
-    wgrad_cfg w;
+    ctl_wgrad_call w = {};
     int rc = wgrad_pick(d, &w);
     if (rc != CTL_OK) return rc;
     const int taps = d->ks * d->ks;

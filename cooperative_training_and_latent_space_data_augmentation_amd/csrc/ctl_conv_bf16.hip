@@ -15,6 +15,7 @@
 // prologue, weights) and stored tensors; accumulation, bias, statistics, residual and activation arithmetic stay fp32.
 // With 14x fewer matrix cycles than fp32 these kernels are HBM-bound: what matters is bytes in flight, not VALU.
 #include "ctl_conv_bf16_common.h"
+#include "ctl_conv_host.h"
 
 #define NFRAG_OF(KS) (((KS) * (KS) + 1) / 2)
 
@@ -713,23 +714,9 @@ extern "C" int ctl_pack_weights_bf16_batched(const float* params, float* wpack, 
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-struct conv16_call {
-    const ctl_conv* d; ctl_conv_cfg c;
-    const void *x, *x2, *wpack, *res, *res2; void *y, *pool, *xout;
-    const float *bias, *pro_scale, *pro_shift, *res_scale, *res_shift; float* stats_partial;
-    hipStream_t stream; bool query; int grid_x;
-};
 template <int KS, int S, int MODE, int MT, int TW, int NT, int FAST, int XB, bool X2 = false>
-static void conv16_go_f(conv16_call& a) {
-    static int occ = 0;
-    if (!occ) {
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv_igemm_bf16_kernel<KS, S, MODE, MT, TW, NT, FAST, XB, X2>, 256, 0) != hipSuccess || n < 1) {
-            (void)hipGetLastError();
-            n = 2;
-        }
-        occ = n;
-    }
+static void conv16_go_f(ctl_conv_call& a) {
+    static const int occ = ctl_resident_blocks(conv_igemm_bf16_kernel<KS, S, MODE, MT, TW, NT, FAST, XB, X2>, 2);
     const ctl_conv* d = a.d;
     const int ntiles = d->n * a.c.tiles_h * a.c.tiles_w;
     a.grid_x = ctl_conv_grid_x(ntiles, (a.c.cot / NT) * d->nsub, occ);
@@ -740,7 +727,7 @@ static void conv16_go_f(conv16_call& a) {
         a.c.g, (int64_t)ctl_conv_wpack_floats(d->cin, d->cout, d->ks) * 4, ntiles, a.pool, a.xout);
 }
 template <int KS, int S, int MODE, int MT, int TW, int NT>
-static void conv16_go(conv16_call& a) {
+static void conv16_go(ctl_conv_call& a) {
     const ctl_conv* d = a.d;
     // the FAST instantiations (see the kernel): bf16 on both sides, whole channel tiles; 1 = bias / statistics only, 2 = bf16 residual
     // with affine (+ LeakyReLU): the tail of every residual block, 3 = accumulate into the bf16 output (the 1x1 data gradients)
@@ -789,7 +776,7 @@ static void conv16_go(conv16_call& a) {
     }
 }
 template <int KS, int S, int MODE>
-static void conv16_go_tile(conv16_call& a) {
+static void conv16_go_tile(ctl_conv_call& a) {
     const bool big = S == 1 && a.c.mt == 4 && a.c.tw == 32;
     if (a.c.nt == 2) {
         if (big) conv16_go<KS, S, MODE, (S == 1 ? 4 : 2), (S == 1 ? 32 : 16), 2>(a);
@@ -801,26 +788,25 @@ static void conv16_go_tile(conv16_call& a) {
         else conv16_go<KS, S, MODE, 1, 16, 1>(a);
     }
 }
-static int conv16_dispatch(conv16_call& a) {
-    const int k = a.d->ks, s = a.d->stride, m = a.d->in_mode == CTL_IN_C4 ? CTL_IN_PLAIN : a.d->in_mode;
-    if (k == 3 && s == 1 && m == CTL_IN_PLAIN) conv16_go_tile<3, 1, CTL_IN_PLAIN>(a);
-    else if (k == 3 && s == 1 && m == CTL_IN_UP2) conv16_go_tile<3, 1, CTL_IN_UP2>(a);
-    else if (k == 3 && s == 1 && m == CTL_IN_ZINS2) conv16_go_tile<3, 1, CTL_IN_ZINS2>(a);
-    else if (k == 3 && s == 2) conv16_go_tile<3, 2, CTL_IN_PLAIN>(a);
-    else if (k == 1 && m == CTL_IN_PLAIN) conv16_go_tile<1, 1, CTL_IN_PLAIN>(a);
-    else if (k == 1 && m == CTL_IN_UP2) conv16_go_tile<1, 1, CTL_IN_UP2>(a);
-    else if (k == 2 && s == 2) conv16_go_tile<2, 2, CTL_IN_PLAIN>(a);
-    else if (k == 2 && s == 1) conv16_go_tile<2, 1, CTL_IN_PLAIN>(a);
-    else if (k == 4 && s == 2) {
-        if (a.c.mt == 2 && a.c.nt == 1) conv16_go<4, 2, CTL_IN_PLAIN, 2, 16, 1>(a);
-        else if (a.c.nt == 2) conv16_go<4, 2, CTL_IN_PLAIN, 1, 16, 2>(a);
-        else conv16_go<4, 2, CTL_IN_PLAIN, 1, 16, 1>(a);
-    } else CTL_FAIL(CTL_EUNSUPPORTED, "conv_forward(bf16): no kernel for this combination");
+static int conv16_dispatch(ctl_conv_call& a) {
+    // (CTL_IN_C4 is a layout of the fp32 family's first layers: here those run through the plain path)
+    const bool built = ctl_visit_shape(a.d->ks, a.d->stride, a.d->in_mode == CTL_IN_C4 ? CTL_IN_PLAIN : a.d->in_mode, [&](auto K, auto S, auto M) {
+        if constexpr (M == CTL_IN_C4) return false;
+        else {
+            if constexpr (K == 4) {
+                if (a.c.mt == 2 && a.c.nt == 1) conv16_go<4, 2, CTL_IN_PLAIN, 2, 16, 1>(a);
+                else if (a.c.nt == 2) conv16_go<4, 2, CTL_IN_PLAIN, 1, 16, 2>(a);
+                else conv16_go<4, 2, CTL_IN_PLAIN, 1, 16, 1>(a);
+            } else conv16_go_tile<K, S, M>(a);
+            return true;
+        }
+    });
+    if (!built) CTL_FAIL(CTL_EUNSUPPORTED, "conv_forward(bf16): no kernel for this combination");
     return CTL_OK;
 }
 
 int ctl_conv_bf16_stats_blocks(const ctl_conv* d) {
-    conv16_call a = {};
+    ctl_conv_call a = {};
     a.d = d;
     if (ctl_conv_pick_cfg(d, &a.c, 0) != CTL_OK) return -1;
     a.query = true;
@@ -846,7 +832,7 @@ int ctl_conv_forward_bf16(const ctl_conv* d, const void* x, const void* x2, cons
                 "conv_forward(bf16): CTL_EPI_BNBWD needs bf16-stored x, y and u with whole 16-channel tiles (got cin %d, cout %d)", d->cin, d->cout);
     CTL_REQUIRE(!(d->dt & CTL_DT_X16) || d->cin % 16 == 0, "conv_forward(bf16): bf16-stored inputs need cin %% 16 == 0 (got %d)", d->cin);
     CTL_REQUIRE(!(d->dt & (CTL_DT_Y16 | CTL_DT_RES16)) || d->cout % 4 == 0, "conv_forward(bf16): bf16-stored outputs need cout %% 4 == 0");
-    conv16_call a = {};
+    ctl_conv_call a = {};
     a.d = d;
     int rc = ctl_conv_pick_cfg(d, &a.c, 0);
     if (rc != CTL_OK) return rc;

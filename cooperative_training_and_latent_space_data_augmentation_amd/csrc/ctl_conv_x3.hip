@@ -36,6 +36,7 @@ extern "C" int ctl_debug_timing_x3(unsigned long long* out12) {
 }
 #endif
 #include "ctl_conv_igemm.h"
+#include "ctl_conv_host.h"
 
 // ------------------------------------------------------------------------------------------------ weight packing
 // Same table records as pack_weights_batched_kernel (modes 0-3 | CTL_PACK_X3); records without CTL_PACK_X3 are skipped here, records
@@ -113,16 +114,6 @@ extern "C" int ctl_pack_weights_x3_batched(const float* params, float* wpack, co
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-struct conv3_call {
-    const ctl_conv* d; ctl_conv_cfg c;
-    const float *x, *wpack, *bias, *pro_scale, *pro_shift, *res, *res_scale, *res_shift, *res2, *x2;
-    float *y, *stats_partial, *pool, *xout;
-    hipStream_t stream;
-    bool query;
-    int grid_x;
-    int stat_rows_per_block;      // 4 for the producer / consumer form (one statistics row per consumer wave)
-};
-
 // The producer / consumer form (ctl_conv_igemm.h, PC): one 512-thread block per CU.  Taken when a block gets at least CTL_X3_PC_MIN_STEPS
 // (tile, chunk) steps: its pipeline costs one exposed load + staging at the head of a block.
 #ifndef CTL_X3_PC_DEFAULT
@@ -141,7 +132,7 @@ static bool conv3_pc_shape_ok(const ctl_conv* d) {
 template <int KS, int S, int MODE, int MT, int TW, int NT, int EPI, bool X2>
 constexpr bool conv3_pc_ok() { return S == 1 && KS == 3 && MODE == CTL_IN_PLAIN && (EPI == 0 || EPI == 3); }
 template <int KS, int S, int MODE, int MT, int TW, int NT, int EPI, bool X2>
-static bool conv3_go_pc(conv3_call& a) {
+static bool conv3_go_pc(ctl_conv_call& a) {
     if constexpr (conv3_pc_ok<KS, S, MODE, MT, TW, NT, EPI, X2>()) {
         if (!a.c.pc) return false;
         const ctl_conv* d = a.d;
@@ -152,41 +143,33 @@ static bool conv3_go_pc(conv3_call& a) {
         if (a.query) return true;
         const dim3 grid((unsigned)grid_x, (unsigned)(a.c.cot / NT), (unsigned)d->nsub);
         conv_igemm_kernel<KS, S, MODE, MT, TW, NT, EPI, X2, true, true><<<grid, dim3(512), 0, a.stream>>>(
-            *d, a.x, a.wpack, a.bias, a.pro_scale, a.pro_shift, a.res, a.res_scale, a.res_shift, a.y, a.stats_partial, a.c.tiles_h,
-            a.c.tiles_w, a.c.g, (int64_t)ctl_conv_wpack_floats_x3(d->cin, d->cout, d->ks), ntiles, a.res2, a.x2, a.pool, a.xout);
+            *d, ctl_f(a.x), ctl_f(a.wpack), a.bias, a.pro_scale, a.pro_shift, ctl_f(a.res), a.res_scale, a.res_shift, ctl_f(a.y), a.stats_partial, a.c.tiles_h,
+            a.c.tiles_w, a.c.g, (int64_t)ctl_conv_wpack_floats_x3(d->cin, d->cout, d->ks), ntiles, ctl_f(a.res2), ctl_f(a.x2), ctl_f(a.pool), ctl_f(a.xout));
         return true;
     }
     return false;
 }
 template <int KS, int S, int MODE, int MT, int TW, int NT, int EPI, bool X2 = false>
-static void conv3_go(conv3_call& a) {
+static void conv3_go(ctl_conv_call& a) {
     if constexpr (!X2 && ((KS == 3 && S == 1 && MODE == CTL_IN_PLAIN) || (KS == 4 && S == 2)) && EPI != 2) {
         if (a.d->pro_affine == 2) { conv3_go<KS, S, MODE, MT, TW, NT, EPI, true>(a); return; }
     }
     a.stat_rows_per_block = 1;
     if (conv3_go_pc<KS, S, MODE, MT, TW, NT, EPI, X2>(a)) return;
-    static int occ = 0;
-    if (!occ) {
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv_igemm_kernel<KS, S, MODE, MT, TW, NT, EPI, X2, true>, 256, 0) != hipSuccess || n < 1) {
-            (void)hipGetLastError();
-            n = 2;
-        }
-        occ = n;
-    }
+    static const int occ = ctl_resident_blocks(conv_igemm_kernel<KS, S, MODE, MT, TW, NT, EPI, X2, true>, 2);
     const ctl_conv* d = a.d;
     const int ntiles = d->n * a.c.tiles_h * a.c.tiles_w;
     a.grid_x = ctl_conv_grid_x(ntiles, (a.c.cot / NT) * d->nsub, occ);
     if (a.query) return;
     const dim3 grid((unsigned)a.grid_x, (unsigned)(a.c.cot / NT), (unsigned)d->nsub);
     conv_igemm_kernel<KS, S, MODE, MT, TW, NT, EPI, X2, true><<<grid, dim3(256), 0, a.stream>>>(
-        *d, a.x, a.wpack, a.bias, a.pro_scale, a.pro_shift, a.res, a.res_scale, a.res_shift, a.y, a.stats_partial, a.c.tiles_h,
-        a.c.tiles_w, a.c.g, (int64_t)ctl_conv_wpack_floats_x3(d->cin, d->cout, d->ks), ntiles, a.res2, a.x2, a.pool, a.xout);
+        *d, ctl_f(a.x), ctl_f(a.wpack), a.bias, a.pro_scale, a.pro_shift, ctl_f(a.res), a.res_scale, a.res_shift, ctl_f(a.y), a.stats_partial, a.c.tiles_h,
+        a.c.tiles_w, a.c.g, (int64_t)ctl_conv_wpack_floats_x3(d->cin, d->cout, d->ks), ntiles, ctl_f(a.res2), ctl_f(a.x2), ctl_f(a.pool), ctl_f(a.xout));
 }
 template <int KS, int S, int MODE>
 constexpr bool conv3_tail_ok() { return KS == 2 || (KS == 3 && S == 1 && MODE == CTL_IN_ZINS2); }
 template <int KS, int S, int MODE, int MT, int TW>
-static void conv3_go_nt(conv3_call& a) {
+static void conv3_go_nt(ctl_conv_call& a) {
     constexpr bool NT2 = !(S == 2 && KS >= 3);          // (conv3_pick_cfg: the stride-2 3x3 / 4x4 forms run one cout tile per block)
     const bool epi = (a.d->epi_flags & (CTL_EPI_RES | CTL_EPI_ACCUM | CTL_EPI_BNBWD)) != 0;
     const bool two = NT2 && a.c.nt == 2;
@@ -207,21 +190,21 @@ static void conv3_go_nt(conv3_call& a) {
     if (epi) go(std::integral_constant<int, 1>{}); else go(std::integral_constant<int, 0>{});
 }
 template <int KS, int S, int MODE>
-static void conv3_go_tile(conv3_call& a) {
+static void conv3_go_tile(ctl_conv_call& a) {
     if (S == 1 && a.c.mt == 4 && a.c.tw == 32) conv3_go_nt<KS, S, MODE, (S == 1 ? 4 : 2), (S == 1 ? 32 : 16)>(a);
     else if (a.c.mt == 2) conv3_go_nt<KS, S, MODE, 2, 16>(a);
     else conv3_go_nt<KS, S, MODE, 1, 16>(a);
 }
-static int conv3_dispatch(conv3_call& a) {
+static int conv3_dispatch(ctl_conv_call& a) {
     const int k = a.d->ks, s = a.d->stride, m = a.d->in_mode;
-    if (k == 3 && s == 1 && m == CTL_IN_PLAIN) conv3_go_tile<3, 1, CTL_IN_PLAIN>(a);
-    else if (k == 3 && s == 1 && m == CTL_IN_UP2) conv3_go_tile<3, 1, CTL_IN_UP2>(a);
-    else if (k == 3 && s == 1 && m == CTL_IN_ZINS2) conv3_go_tile<3, 1, CTL_IN_ZINS2>(a);
-    else if (k == 3 && s == 2) conv3_go_tile<3, 2, CTL_IN_PLAIN>(a);
-    else if (k == 2 && s == 2) conv3_go_tile<2, 2, CTL_IN_PLAIN>(a);
-    else if (k == 2 && s == 1) conv3_go_tile<2, 1, CTL_IN_PLAIN>(a);
-    else if (k == 4 && s == 2) conv3_go_nt<4, 2, CTL_IN_PLAIN, 1, 16>(a);
-    else CTL_FAIL(CTL_EUNSUPPORTED, "conv_forward(x3): no kernel for ks/stride/in_mode %d/%d/%d", k, s, m);
+    const bool built = ctl_visit_shape(k, s, m, [&](auto K, auto S, auto M) {
+        if constexpr (K == 1 || M == CTL_IN_C4) return false;      // (HBM-bound: they stay on the fp32 pipe)
+        else {
+            if constexpr (K == 4) conv3_go_nt<4, 2, CTL_IN_PLAIN, 1, 16>(a); else conv3_go_tile<K, S, M>(a);
+            return true;
+        }
+    });
+    if (!built) CTL_FAIL(CTL_EUNSUPPORTED, "conv_forward(x3): no kernel for ks/stride/in_mode %d/%d/%d", k, s, m);
     return CTL_OK;
 }
 
@@ -279,7 +262,7 @@ int ctl_conv_x3_ok(const ctl_conv* d) {
     return d->cin % 16 == 0 && (d->cout % 16 == 0 || (d->cout < 16 && d->cout % 4 == 0)) && d->ks >= 2 && d->in_mode != CTL_IN_C4 && !(d->dt & (CTL_DT_BF16 | CTL_DT_X16 | CTL_DT_Y16 | CTL_DT_RES16));
 }
 int ctl_conv_x3_stats_blocks(const ctl_conv* d) {
-    conv3_call a = {};
+    ctl_conv_call a = {};
     a.d = d;
     if (!ctl_conv_x3_ok(d) || conv3_pick_cfg(d, &a.c) != CTL_OK) return -1;
     a.query = true;
@@ -293,7 +276,7 @@ int ctl_conv_forward_x3(const ctl_conv* d, const float* x, const float* wpack, c
     CTL_REQUIRE(ctl_conv_x3_ok(d), "conv_forward(x3): CTL_DT_X3 needs fp32-stored tensors, cin %% 16 == 0, cout %% 16 == 0 (or 4 / 8 / 12) and a 2x2 / 3x3 / 4x4 kernel "
                                    "(got cin %d, cout %d, ks %d, in_mode %d, dt %d)", d->cin, d->cout, d->ks, d->in_mode, d->dt);
     CTL_REQUIRE(!pool, "conv_forward(x3): `pool` belongs to the 1x1 hosts, which stay on the fp32 pipe");
-    conv3_call a = {};
+    ctl_conv_call a = {};
     a.d = d;
     int rc = conv3_pick_cfg(d, &a.c);
     if (rc != CTL_OK) return rc;

@@ -28,6 +28,7 @@
 #include <string.h>
 
 #include "ctl_common.h"
+#include "ctl_conv_host.h"
 
 static thread_local char g_err[512] = "";
 
@@ -56,6 +57,21 @@ hipEvent_t prof_event() {
     hipEvent_t e = nullptr;
     return hipEventCreate(&e) == hipSuccess ? e : nullptr;
 }
+// the common end of the begin functions: filter, sampling, the two events, record; the token of the bracket or -1
+int prof_push(const char* id, double flops, double bytes, hipStream_t stream) {
+    if (!g_prof_filter.empty() && std::string(id).find(g_prof_filter) == std::string::npos) return -1;
+    if (g_prof_every > 1 && (g_prof_seen++ % g_prof_every) != 0) return -1;
+    ProfRec r;
+    r.id = id;
+    r.stream = (void*)stream;
+    r.flops = flops; r.bytes = bytes;
+    r.a = prof_event();
+    r.b = prof_event();
+    if (!r.a || !r.b) return -1;
+    (void)hipEventRecord(r.a, stream);
+    g_prof.push_back(r);
+    return (int)g_prof.size() - 1;
+}
 }  // namespace
 
 int ctl_prof_begin(const char* kind, const ctl_conv* d, const ctl_conv_cfg* c, int nt, hipStream_t stream, bool dy2) {
@@ -79,42 +95,18 @@ int ctl_prof_begin(const char* kind, const ctl_conv* d, const ctl_conv_cfg* c, i
                  d->hout, d->cin, d->cout, d->epi_flags);
     else
         snprintf(id, sizeof(id), "%s<ks%d,s%d,in%d,mt%d,tw%d,nt%d%s>", kind, d->ks, d->stride, d->in_mode, c->mt, c->tw, nt, sfx);
-    if (!g_prof_filter.empty() && std::string(id).find(g_prof_filter) == std::string::npos) return -1;
-    if (g_prof_every > 1 && (g_prof_seen++ % g_prof_every) != 0) return -1;
-    ProfRec r;
-    r.id = id;
-    r.stream = (void*)stream;
-    r.a = prof_event();
-    r.b = prof_event();
-    if (!r.a || !r.b) return -1;
+    double flops, bytes;
+    ctl_conv_work(d, dy2, &flops, &bytes);
+    // the operands of the epilogue: u / the residual, the block output and the BatchNorm input of the tail, the accumulated output read back
     const double pix = (double)d->n * d->hout * d->wout * d->nsub;
-    r.flops = 2.0 * pix * d->cout * d->cin * d->ks * d->ks;
-    const double in_b = ((d->dt & CTL_DT_X16) ? 2.0 : 4.0) * d->n * d->hin * d->win * d->cin, out_b = ((d->dt & CTL_DT_Y16) ? 2.0 : 4.0) * pix * d->cout;
-    r.bytes = in_b + out_b;
-    if (d->pro_affine == 2) r.bytes += in_b;             // the second tensor of the BatchNorm-backward prologue
-    if (dy2) r.bytes += out_b;                           // ... of the weight gradient's virtual output gradient
-    if (d->epi_flags & (CTL_EPI_RES | CTL_EPI_BNBWD)) r.bytes += ((d->dt & CTL_DT_RES16) ? 2.0 : 4.0) * pix * d->cout;
-    if (d->epi_flags & CTL_EPI_TAILBWD) r.bytes += 2.0 * 4.0 * pix * d->cout;            // the block output and the BatchNorm input of the tail
-    if (d->epi_flags & CTL_EPI_ACCUM) r.bytes += out_b;
-    (void)hipEventRecord(r.a, stream);
-    g_prof.push_back(r);
-    return (int)g_prof.size() - 1;
+    if (d->epi_flags & (CTL_EPI_RES | CTL_EPI_BNBWD)) bytes += ((d->dt & CTL_DT_RES16) ? 2.0 : 4.0) * pix * d->cout;
+    if (d->epi_flags & CTL_EPI_TAILBWD) bytes += 2.0 * 4.0 * pix * d->cout;
+    if (d->epi_flags & CTL_EPI_ACCUM) bytes += ((d->dt & CTL_DT_Y16) ? 2.0 : 4.0) * pix * d->cout;
+    return prof_push(id, flops, bytes, stream);
 }
 // a launch that serves several problems (grouped weight gradients): the caller sums the members' algorithmic work
 int ctl_prof_begin_raw(const char* id, double flops, double bytes, hipStream_t stream) {
-    if (!g_prof_on) return -1;
-    if (!g_prof_filter.empty() && std::string(id).find(g_prof_filter) == std::string::npos) return -1;
-    if (g_prof_every > 1 && (g_prof_seen++ % g_prof_every) != 0) return -1;
-    ProfRec r;
-    r.id = id;
-    r.stream = (void*)stream;
-    r.a = prof_event();
-    r.b = prof_event();
-    if (!r.a || !r.b) return -1;
-    r.flops = flops; r.bytes = bytes;
-    (void)hipEventRecord(r.a, stream);
-    g_prof.push_back(r);
-    return (int)g_prof.size() - 1;
+    return g_prof_on ? prof_push(id, flops, bytes, stream) : -1;
 }
 // HBM-bound plan ops (BatchNorm backward passes, bn_act, sum-pool): bracketed with their ALGORITHMIC bytes (every tensor argument once,
 // at its storage width); the other non-conv ops (finalizes, copies) only for the timeline dump of a -DCTL_TUNING build
@@ -154,19 +146,7 @@ static int prof_begin_op(const ctl_op& op, hipStream_t stream) {
             if (!timeline) return -1;
             snprintf(id, sizeof(id), "op%d", op.kind);
     }
-    if (!g_prof_filter.empty() && std::string(id).find(g_prof_filter) == std::string::npos) return -1;
-    if (g_prof_every > 1 && (g_prof_seen++ % g_prof_every) != 0) return -1;
-    ProfRec r;
-    r.id = id;
-    r.stream = (void*)stream;
-    r.flops = 0.0;
-    r.bytes = bytes;
-    r.a = prof_event();
-    r.b = prof_event();
-    if (!r.a || !r.b) return -1;
-    (void)hipEventRecord(r.a, stream);
-    g_prof.push_back(r);
-    return (int)g_prof.size() - 1;
+    return prof_push(id, 0.0, bytes, stream);
 }
 void ctl_prof_end(int token, hipStream_t stream) {
     if (token >= 0 && token < (int)g_prof.size()) (void)hipEventRecord(g_prof[token].b, stream);
@@ -228,6 +208,20 @@ extern "C" size_t ctl_sizeof_conv(void) { return sizeof(ctl_conv); }
 
 static_assert(sizeof(ctl_conv) == 24 * 4, "ctl_conv must be 24 32-bit words (it is embedded in ctl_op.i[0..23]; i[24] and i[25] are taken)");
 
+// the first n tensor slots of a record as pointers (member >= 0: the record is that member of the WGRAD_GROUP record k)
+static int resolve(const ctl_op& op, void* const* bases, int n_bases, void** t, int n, int k, int member) {
+    for (int a = 0; a < n; ++a) {
+        const int s = op.slot[a];
+        if (s < 0) { t[a] = nullptr; continue; }
+        if (!(s < n_bases && bases[s])) {
+            if (member < 0) CTL_FAIL(CTL_EINVAL, "plan_run: op %d arg %d uses empty slot %d", k, a, s);
+            CTL_FAIL(CTL_EINVAL, "plan_run: op %d member %d arg %d uses empty slot %d", k, member, a, s);
+        }
+        t[a] = (char*)bases[s] + op.off[a];
+    }
+    return CTL_OK;
+}
+
 extern "C" int ctl_plan_run(const ctl_op* ops, int32_t n_ops, void* const* bases, int32_t n_bases, ctl_stream stream_) {
     CTL_REQUIRE(ops && bases && n_ops >= 0, "plan_run: null arguments");
     const ctl_stream stream = stream_;
@@ -244,16 +238,11 @@ extern "C" int ctl_plan_run(const ctl_op* ops, int32_t n_ops, void* const* bases
             continue;
 #endif
         void* t[CTL_OP_MAX_T];
-        for (int a = 0; a < CTL_OP_MAX_T; ++a) {
-            const int s = op.slot[a];
-            if (s < 0) { t[a] = nullptr; continue; }
-            CTL_REQUIRE(s < n_bases && bases[s], "plan_run: op %d arg %d uses empty slot %d", k, a, s);
-            t[a] = (char*)bases[s] + op.off[a];
-        }
+        int rc = resolve(op, bases, n_bases, t, CTL_OP_MAX_T, k, -1);
+        if (rc != CTL_OK) return rc;
 #define F(a) ((float*)t[a])
 #define NG(v) ((v) > 0 ? (v) : 1)      /* BatchNorm groups: 0 in a record means one group */
 #define CF(a) ((const float*)t[a])
-        int rc = CTL_OK;
         ctl_conv d;
         const int ptok = (op.kind == CTL_OP_CONV || op.kind == CTL_OP_WGRAD) ? -1 : prof_begin_op(op, (hipStream_t)stream);
         switch (op.kind) {
@@ -279,12 +268,8 @@ extern "C" int ctl_plan_run(const ctl_op* ops, int32_t n_ops, void* const* bases
                     const ctl_op& mo = ops[k + 1 + j];
                     CTL_REQUIRE(mo.kind == CTL_OP_WGRAD, "plan_run: op %d: member %d of a WGRAD_GROUP is not a WGRAD record", k, j);
                     void* mt[8];
-                    for (int a = 0; a < 8; ++a) {
-                        const int s = mo.slot[a];
-                        if (s < 0) { mt[a] = nullptr; continue; }
-                        CTL_REQUIRE(s < n_bases && bases[s], "plan_run: op %d member %d arg %d uses empty slot %d", k, j, a, s);
-                        mt[a] = (char*)bases[s] + mo.off[a];
-                    }
+                    rc = resolve(mo, bases, n_bases, mt, 8, k, j);
+                    if (rc != CTL_OK) return rc;
                     memcpy(&ds[j], mo.i, sizeof(ctl_conv));
                     sp[j] = mo.i[24];
                     mx[j] = (const float*)mt[0]; mps[j] = (const float*)mt[1]; mpb[j] = (const float*)mt[2]; mdy[j] = (const float*)mt[3];

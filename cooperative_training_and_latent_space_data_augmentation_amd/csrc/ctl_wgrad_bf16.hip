@@ -1,5 +1,6 @@
 // bf16 weight-gradient kernels for gfx950 (MI355X), the second half of the bf16 family (see ctl_conv_bf16.hip for the arithmetic contract).
 #include "ctl_conv_bf16_common.h"
+#include "ctl_conv_host.h"
 
 // ------------------------------------------------------------------------------------------------ weight gradient (bf16 operands)
 // dW[tap][ci][co] = sum_pixels x_virtual[pixel*S + tap - pad][ci] * dy[pixel][co]:  D[ci][co] += A[ci][k = pixel] B[pixel][co], K = 32 pixels.
@@ -327,38 +328,17 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_group_kernel(const wg16_g
                                                     M.ntiles, M.cin_p, M.cout_p, bx, t % M.gy, t / M.gy, M.gx);
 }
 
-struct wgrad16_call {
-    const ctl_conv* d; ctl_conv_cfg c; int ntw, splits, ntiles, cin_p, cout_p;
-    const void *x, *dy, *dy2; const float *pro_scale, *pro_shift, *dy_coef; float *w_partial, *b_partial;
-    hipStream_t stream; bool query;
-    int key;                       // the instantiation the dispatch ends in (members of a grouped launch must agree)
-    int cap;                       // blocks of this instantiation the chip holds at once
-    const wg16_group* grp;         // launch this stacked group instead of the single problem
-    int grp_blocks;
-};
 static inline int wg16_key(int ks, int s, int mode, int mt, int ntw, int dy2, int xk, int dyk) {
     return ks | (s << 3) | (mode << 5) | (mt << 7) | (ntw << 10) | (dy2 << 12) | (xk << 13) | (dyk << 15);
 }
 template <int KS, int S, int MODE, int MT, int NTW, bool DY2, int XK, int DYK>
-static void wgrad16_go_f(wgrad16_call& a) {
-    static int occ = 0;
-    if (!occ) {
-        int n = 0;
-        // (of the plain instantiation, also for DY2: the split count is queried at plan time from the descriptor alone and sizes the partials)
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv_wgrad_bf16_kernel<KS, S, MODE, MT, NTW, false, 0, 0>, 256, 0) != hipSuccess || n < 1) {
-            (void)hipGetLastError();
-            n = 2;
-        }
-        occ = n;
-    }
+static void wgrad16_go_f(ctl_wgrad_call& a) {
+    // (of the plain instantiation, also for DY2: the split count is queried at plan time from the descriptor alone and sizes the partials)
+    static const int occ = ctl_resident_blocks(conv_wgrad_bf16_kernel<KS, S, MODE, MT, NTW, false, 0, 0>, 2);
     const int par = a.c.g * (a.c.cot / NTW);
     static const int cap = ctl_tune_int("CTL16_WGRAD_SPLITS", 1024);      // tuning hook (measured: 512 -> 768/1024 splits = 28.7 -> 24.5 us on the 16->16 3x3 layer at 256^2)
-    int splits = (ctl_num_cus() * (occ < 4 ? occ : 4)) / par;
-    if (splits > cap) splits = cap;
-    if (splits > a.ntiles) splits = a.ntiles;
-    if (splits < 1) splits = 1;
-    a.splits = splits;
     a.cap = ctl_num_cus() * (occ < 4 ? occ : 4);
+    const int splits = a.splits = ctl_wgrad_clamp_splits(a.cap, par, cap, a.ntiles);
     a.key = wg16_key(KS, S, MODE, MT, NTW, DY2, XK, DYK);
     if (a.query) return;
     if (a.grp) {
@@ -371,7 +351,7 @@ static void wgrad16_go_f(wgrad16_call& a) {
                                                                                         a.cin_p, a.cout_p);
 }
 template <int KS, int S, int MODE, int MT, int NTW>
-static void wgrad16_go(wgrad16_call& a) {
+static void wgrad16_go(ctl_wgrad_call& a) {
     if constexpr (KS == 3 && S == 1) {      // the two-tensor output gradient: the 3x3 convs of the residual blocks
         if (a.dy2) {      // (bf16-stored dy / dy2 by contract; x is fp32 with 1 or 4 channels in the encoders' first layer)
             if ((a.d->dt & CTL_DT_X16) && a.d->cin % 16 == 0) wgrad16_go_f<KS, S, MODE, MT, NTW, true, 1, 1>(a);
@@ -396,25 +376,22 @@ static void wgrad16_go(wgrad16_call& a) {
     wgrad16_go_f<KS, S, MODE, MT, NTW, false, 0, 0>(a);
 }
 template <int KS, int S, int MODE>
-static void wgrad16_go_tile(wgrad16_call& a) {
+static void wgrad16_go_tile(ctl_wgrad_call& a) {
     if constexpr (S == 1 && (KS == 3 || KS == 1)) {
         if (a.c.mt == 4) { if (a.ntw == 2) wgrad16_go<KS, S, MODE, 4, 2>(a); else wgrad16_go<KS, S, MODE, 4, 1>(a); return; }
     }
     if (a.c.mt == 2) { if (a.ntw == 2) wgrad16_go<KS, S, MODE, 2, 2>(a); else wgrad16_go<KS, S, MODE, 2, 1>(a); }
     else { if (a.ntw == 2) wgrad16_go<KS, S, MODE, 1, 2>(a); else wgrad16_go<KS, S, MODE, 1, 1>(a); }
 }
-static int wgrad16_dispatch(wgrad16_call& a) {
-    const int k = a.d->ks, s = a.d->stride, m = a.d->in_mode == CTL_IN_C4 ? CTL_IN_PLAIN : a.d->in_mode;
-    if (k == 3 && s == 1 && m == CTL_IN_PLAIN) wgrad16_go_tile<3, 1, CTL_IN_PLAIN>(a);
-    else if (k == 3 && s == 1 && m == CTL_IN_UP2) wgrad16_go_tile<3, 1, CTL_IN_UP2>(a);
-    else if (k == 3 && s == 2) wgrad16_go_tile<3, 2, CTL_IN_PLAIN>(a);
-    else if (k == 1 && m == CTL_IN_PLAIN) wgrad16_go_tile<1, 1, CTL_IN_PLAIN>(a);
-    else if (k == 1 && m == CTL_IN_UP2) wgrad16_go_tile<1, 1, CTL_IN_UP2>(a);
-    else if (k == 2 && s == 2) wgrad16_go_tile<2, 2, CTL_IN_PLAIN>(a);
-    else CTL_FAIL(CTL_EUNSUPPORTED, "conv_wgrad(bf16): no kernel for this combination");
+static int wgrad16_dispatch(ctl_wgrad_call& a) {
+    const bool built = ctl_visit_shape(a.d->ks, a.d->stride, a.d->in_mode == CTL_IN_C4 ? CTL_IN_PLAIN : a.d->in_mode, [&](auto K, auto S, auto M) {
+        if constexpr (K == 4 || (K == 2 && S == 1) || M == CTL_IN_ZINS2 || M == CTL_IN_C4) return false;
+        else { wgrad16_go_tile<K, S, M>(a); return true; }
+    });
+    if (!built) CTL_FAIL(CTL_EUNSUPPORTED, "conv_wgrad(bf16): no kernel for this combination");
     return CTL_OK;
 }
-static int wgrad16_pick(const ctl_conv* d, wgrad16_call* a) {
+static int wgrad16_pick(const ctl_conv* d, ctl_wgrad_call* a) {
     CTL_REQUIRE(d->nsub == 1 && d->in_mode != CTL_IN_ZINS2, "wgrad(bf16): nsub must be 1, no zero-insert input");
     CTL_REQUIRE(!(d->dt & CTL_DT_X16) || d->cin % 16 == 0, "wgrad(bf16): bf16-stored x needs cin %% 16 == 0");
     CTL_REQUIRE(!(d->dt & CTL_DT_Y16) || d->cout % 16 == 0, "wgrad(bf16): bf16-stored dy needs cout %% 16 == 0");
@@ -429,17 +406,14 @@ static int wgrad16_pick(const ctl_conv* d, wgrad16_call* a) {
         a->c.mt = 4; a->c.th = 16;
         a->c.tiles_h = ctl_cdiv(d->hout, 16);
     }
-    a->ntw = (a->c.cot >= 2 && a->c.cot % 2 == 0) ? 2 : 1;
-    a->ntiles = d->n * a->c.tiles_h * a->c.tiles_w;
-    a->cin_p = a->c.g * 16;
-    a->cout_p = a->c.cot * 16;
+    ctl_wgrad_geometry(*a);
     a->query = true;
     rc = wgrad16_dispatch(*a);
     a->query = false;
     return rc;
 }
 int ctl_wgrad_bf16_splits(const ctl_conv* d) {
-    wgrad16_call a = {};
+    ctl_wgrad_call a = {};
     return wgrad16_pick(d, &a) == CTL_OK ? a.splits : -1;
 }
 int ctl_conv_wgrad_bf16(const ctl_conv* d, const void* x, const float* pro_scale, const float* pro_shift, const void* dy, const void* dy2,
@@ -447,7 +421,7 @@ int ctl_conv_wgrad_bf16(const ctl_conv* d, const void* x, const float* pro_scale
     CTL_REQUIRE(!dy2 || (dy_coef && d->ks == 3 && d->stride == 1 && (d->dt & CTL_DT_Y16) && d->cout % 16 == 0 &&
                          (d->groups > 1 ? d->groups : 1) * d->cout <= CTL_PRO_MAX),
                 "wgrad(bf16): the two-tensor output gradient needs coefficients, a 3x3 stride-1 conv, bf16-stored dy / dy2 with cout %% 16 == 0 and groups * cout <= %d", CTL_PRO_MAX);
-    wgrad16_call a = {};
+    ctl_wgrad_call a = {};
     int rc = wgrad16_pick(d, &a);
     if (rc != CTL_OK) return rc;
     a.x = x; a.dy = dy; a.dy2 = dy2; a.dy_coef = dy_coef; a.pro_scale = pro_scale; a.pro_shift = pro_shift; a.w_partial = w_partial; a.b_partial = b_partial;
@@ -463,7 +437,7 @@ int ctl_wgrad_bf16_group_class(const ctl_conv* d, int has_dy2) {
     static const int on = ctl_tune_int("CTL16_WGRAD_GROUP", 1);
     if (!on) return -1;
     if (has_dy2 && !(d->ks == 3 && d->stride == 1 && (d->dt & CTL_DT_Y16) && d->cout % 16 == 0)) return -1;
-    wgrad16_call a = {};
+    ctl_wgrad_call a = {};
     if (wgrad16_pick(d, &a) != CTL_OK) return -1;
     int dummy = 0;
     a.dy2 = has_dy2 ? &dummy : nullptr;       // (only its presence selects the instantiation)
@@ -477,18 +451,19 @@ int ctl_conv_wgrad_bf16_group(int n, const ctl_conv* descs, const int32_t* split
     CTL_REQUIRE(n >= 1 && n <= CTL_WG16_MAX, "conv_wgrad_group(bf16): 1..%d members", CTL_WG16_MAX);
     wg16_group g = {};
     g.n = n;
-    wgrad16_call first = {};
+    ctl_wgrad_call first = {};
     int blocks = 0, key = -1;
     double flops = 0.0, bytes = 0.0;
     for (int i = 0; i < n; ++i) {
         const ctl_conv* d = &descs[i];
         const bool two = dy2 && dy2[i];
-        CTL_REQUIRE(x[i] && dy[i] && w_partial[i] && (!d->pro_affine || (pro_scale && pro_shift && pro_scale[i] && pro_shift[i])) && (!two || (dy_coef && dy_coef[i])),
-                    "conv_wgrad_group(bf16): member %d misses a tensor", i);
+        int rc = ctl_wgrad_check(d, x[i], pro_scale ? pro_scale[i] : nullptr, pro_shift ? pro_shift[i] : nullptr, dy[i], two ? dy2[i] : nullptr,
+                                 dy_coef ? dy_coef[i] : nullptr, w_partial[i], "conv_wgrad_group(bf16)", i);
+        if (rc != CTL_OK) return rc;
         CTL_REQUIRE(!two || (d->ks == 3 && d->stride == 1 && (d->dt & CTL_DT_Y16) && d->cout % 16 == 0 && (d->groups > 1 ? d->groups : 1) * d->cout <= CTL_PRO_MAX),
                     "conv_wgrad_group(bf16): member %d: the two-tensor output gradient needs a 3x3 stride-1 conv, bf16-stored dy / dy2, groups * cout <= %d", i, CTL_PRO_MAX);
-        wgrad16_call a = {};
-        int rc = wgrad16_pick(d, &a);
+        ctl_wgrad_call a = {};
+        rc = wgrad16_pick(d, &a);
         if (rc != CTL_OK) return rc;
         a.dy2 = two ? dy2[i] : nullptr;
         a.query = true;
@@ -506,9 +481,9 @@ int ctl_conv_wgrad_bf16_group(int n, const ctl_conv* descs, const int32_t* split
         m.gx = a.splits; m.gy = a.c.g; m.gz = a.c.cot / a.ntw; m.block0 = blocks;
         blocks += m.gx * m.gy * m.gz;
         if (i == 0) first = a;
-        const double pix = (double)d->n * d->hout * d->wout;
-        flops += 2.0 * pix * d->cout * d->cin * d->ks * d->ks;
-        bytes += ((d->dt & CTL_DT_X16) ? 2.0 : 4.0) * d->n * d->hin * d->win * d->cin + ((d->dt & CTL_DT_Y16) ? 2.0 : 4.0) * pix * d->cout * (two ? 2 : 1);
+        double f = 0.0, b = 0.0;
+        ctl_conv_work(d, two, &f, &b);
+        flops += f; bytes += b;
     }
     char kind[64];
     snprintf(kind, sizeof(kind), "conv_wgrad_bf16grp<ks%d,s%d,in%d,mt%d,nt%d%s>", key & 7, (key >> 3) & 3, (key >> 5) & 3, (key >> 7) & 7, (key >> 10) & 3, ((key >> 12) & 1) ? ",x2" : "");
@@ -529,7 +504,7 @@ int ctl_wgrad_bf16_group_plan(const ctl_conv* descs, int n, int32_t* splits) {
     int64_t work[CTL_WG16_MAX], total = 0;
     int par[CTL_WG16_MAX], ntiles[CTL_WG16_MAX], own[CTL_WG16_MAX], cap = 0;
     for (int i = 0; i < n; ++i) {
-        wgrad16_call a = {};
+        ctl_wgrad_call a = {};
         int rc = wgrad16_pick(&descs[i], &a);
         if (rc != CTL_OK) return rc;
         par[i] = a.c.g * (a.c.cot / a.ntw);

@@ -13,6 +13,7 @@
 #include <type_traits>
 
 #include "ctl_conv_x3_stage.h"
+#include "ctl_conv_host.h"
 
 typedef short x3_s16x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ x3_bf16x8 x3_tr_read8(const unsigned char* a0, const unsigned char* a1) {
@@ -555,45 +556,27 @@ __global__ __launch_bounds__(1024, 4) void conv_wgrad_x3pc16_kernel(const wg_gro
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-struct wgrad3_call {
-    const ctl_conv* d; ctl_conv_cfg c; int ntw, splits, ntiles, cin_p, cout_p;
-    const float *x, *dy, *dy2, *pro_scale, *pro_shift, *dy_coef; float *w_partial, *b_partial;
-    hipStream_t stream; bool query;
-    int pc;      // the producer / consumer kernel (32 x 32 blocks) was chosen
-};
 template <int KS, int S, int MODE, int MT, int NTW, bool DY2>
-static void wgrad3_go_f(wgrad3_call& a) {
-    static int occ = 0;
-    if (!occ) {
-        int n = 0;
-        // (of the plain instantiation, also for DY2: the split count is queried at plan time from the descriptor alone and sizes the partials)
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv_wgrad_x3_kernel<KS, S, MODE, MT, NTW, false>, 256, 0) != hipSuccess || n < 1) {
-            (void)hipGetLastError();
-            n = 1;
-        }
-        occ = n;
-    }
+static void wgrad3_go_f(ctl_wgrad_call& a) {
+    // (of the plain instantiation, also for DY2: the split count is queried at plan time from the descriptor alone and sizes the partials)
+    static const int occ = ctl_resident_blocks(conv_wgrad_x3_kernel<KS, S, MODE, MT, NTW, false>, 1);
     const int par = a.c.g * (a.c.cot / NTW);
     static const int per_cu = ctl_tune_int("CTL_X3W_PERSIST", 2);      // tuning hook: resident blocks per CU
-    int splits = (ctl_num_cus() * (occ < per_cu ? occ : per_cu)) / par;
-    if (splits > 512) splits = 512;
-    if (splits > a.ntiles) splits = a.ntiles;
-    if (splits < 1) splits = 1;
-    a.splits = splits;
+    const int splits = a.splits = ctl_wgrad_clamp_splits(ctl_num_cus() * (occ < per_cu ? occ : per_cu), par, 512, a.ntiles);
     if (a.query) return;
     const dim3 grid((unsigned)splits, (unsigned)a.c.g, (unsigned)(a.c.cot / NTW));
-    conv_wgrad_x3_kernel<KS, S, MODE, MT, NTW, DY2><<<grid, dim3(256), 0, a.stream>>>(*a.d, a.x, a.pro_scale, a.pro_shift, a.dy, a.dy2, a.dy_coef, a.w_partial,
-                                                                                    a.b_partial, a.c.tiles_h, a.c.tiles_w, a.ntiles, a.cin_p, a.cout_p);
+    conv_wgrad_x3_kernel<KS, S, MODE, MT, NTW, DY2><<<grid, dim3(256), 0, a.stream>>>(*a.d, ctl_f(a.x), a.pro_scale, a.pro_shift, ctl_f(a.dy), ctl_f(a.dy2), a.dy_coef,
+                                                                                    a.w_partial, a.b_partial, a.c.tiles_h, a.c.tiles_w, a.ntiles, a.cin_p, a.cout_p);
 }
 template <int KS, int S, int MODE, int MT, int NTW>
-static void wgrad3_go(wgrad3_call& a) {
+static void wgrad3_go(ctl_wgrad_call& a) {
     if constexpr (KS == 3 && S == 1) {
         if (a.dy2) { wgrad3_go_f<KS, S, MODE, MT, NTW, true>(a); return; }
     }
     wgrad3_go_f<KS, S, MODE, MT, NTW, false>(a);
 }
 template <int KS, int S, int MODE>
-static void wgrad3_go_tile(wgrad3_call& a) {
+static void wgrad3_go_tile(ctl_wgrad_call& a) {
     if (a.c.mt == 2) { if (a.ntw == 2) wgrad3_go<KS, S, MODE, 2, 2>(a); else wgrad3_go<KS, S, MODE, 2, 1>(a); }
     else { if (a.ntw == 2) wgrad3_go<KS, S, MODE, 1, 2>(a); else wgrad3_go<KS, S, MODE, 1, 1>(a); }
 }
@@ -603,9 +586,9 @@ static void wgrad3_go_tile(wgrad3_call& a) {
 #ifndef CTL_X3W_PC_MIN_TILES
 #define CTL_X3W_PC_MIN_TILES 4
 #endif
-static void wgrad3_fill_member(wg_member& m, const wgrad3_call& a, int job0) {
+static void wgrad3_fill_member(wg_member& m, const ctl_wgrad_call& a, int job0) {
     m.d = *a.d;
-    m.x = a.x; m.pro_scale = a.pro_scale; m.pro_shift = a.pro_shift; m.dy = a.dy; m.dy2 = a.dy2; m.dy_coef = a.dy_coef;
+    m.x = ctl_f(a.x); m.pro_scale = a.pro_scale; m.pro_shift = a.pro_shift; m.dy = ctl_f(a.dy); m.dy2 = ctl_f(a.dy2); m.dy_coef = a.dy_coef;
     m.w_partial = a.w_partial; m.b_partial = a.b_partial;
     m.tiles_h = a.c.tiles_h; m.tiles_w = a.c.tiles_w; m.ntiles = a.ntiles; m.cin_p = a.cin_p; m.cout_p = a.cout_p;
     m.splits = a.splits; m.job0 = job0; m.pad_ = 0;
@@ -621,7 +604,7 @@ static void wgrad3_launch_group(const wg_group& g, int jobs, int mode, bool dy2,
     }
 }
 template <int MODE>
-static void wgrad3_go_pc(wgrad3_call& a) {      // a single problem = a group of one
+static void wgrad3_go_pc(ctl_wgrad_call& a) {      // a single problem = a group of one
     wg_group g = {};
     g.n = 1;
     wgrad3_fill_member(g.m[0], a, 0);
@@ -632,7 +615,7 @@ static bool wgrad3_pc_shape_ok(const ctl_conv* d) {
     return ctl_wgrad_x3_ok(d) && d->ks == 3 && d->stride == 1 && (d->in_mode == CTL_IN_PLAIN || d->in_mode == CTL_IN_UP2) && d->cin % 32 == 0 && d->cout % 32 == 0 &&
            d->hout >= 8;
 }
-static bool wgrad3_pc_pick(const ctl_conv* d, wgrad3_call* a) {
+static bool wgrad3_pc_pick(const ctl_conv* d, ctl_wgrad_call* a) {
     static const int pc_on = ctl_tune_int("CTL_X3W_PC", CTL_X3W_PC_DEFAULT), min_tiles = ctl_tune_int("CTL_X3W_PC_MIN_TILES", CTL_X3W_PC_MIN_TILES);
     if (!pc_on || !wgrad3_pc_shape_ok(d) || a->c.mt != 2) return false;
     const int par = (d->cin / 32) * (d->cout / 32);
@@ -643,18 +626,18 @@ static bool wgrad3_pc_pick(const ctl_conv* d, wgrad3_call* a) {
     a->splits = splits;
     return true;
 }
-static int wgrad3_dispatch(wgrad3_call& a) {
+static int wgrad3_dispatch(ctl_wgrad_call& a) {
     const int k = a.d->ks, s = a.d->stride, m = a.d->in_mode;
     if (a.pc) {
         if (a.query) return CTL_OK;
         if (m == CTL_IN_PLAIN) wgrad3_go_pc<CTL_IN_PLAIN>(a); else wgrad3_go_pc<CTL_IN_UP2>(a);
         return CTL_OK;
     }
-    if (k == 3 && s == 1 && m == CTL_IN_PLAIN) wgrad3_go_tile<3, 1, CTL_IN_PLAIN>(a);
-    else if (k == 3 && s == 1 && m == CTL_IN_UP2) wgrad3_go_tile<3, 1, CTL_IN_UP2>(a);
-    else if (k == 3 && s == 2 && m == CTL_IN_PLAIN) wgrad3_go_tile<3, 2, CTL_IN_PLAIN>(a);
-    else if (k == 2 && s == 2 && m == CTL_IN_PLAIN) wgrad3_go_tile<2, 2, CTL_IN_PLAIN>(a);
-    else CTL_FAIL(CTL_EUNSUPPORTED, "conv_wgrad(x3): no kernel for ks/stride/in_mode %d/%d/%d", k, s, m);
+    const bool built = ctl_visit_shape(k, s, m, [&](auto K, auto S, auto M) {
+        if constexpr (K == 3 ? (M == CTL_IN_ZINS2 || M == CTL_IN_C4) : !(K == 2 && S == 2)) return false;      // (ctl_wgrad_x3_ok)
+        else { wgrad3_go_tile<K, S, M>(a); return true; }
+    });
+    if (!built) CTL_FAIL(CTL_EUNSUPPORTED, "conv_wgrad(x3): no kernel for ks/stride/in_mode %d/%d/%d", k, s, m);
     return CTL_OK;
 }
 int ctl_wgrad_x3_ok(const ctl_conv* d) {
@@ -662,7 +645,7 @@ int ctl_wgrad_x3_ok(const ctl_conv* d) {
     const bool combo = (k == 3 && s == 1 && (m == CTL_IN_PLAIN || m == CTL_IN_UP2)) || (k == 3 && s == 2 && m == CTL_IN_PLAIN) || (k == 2 && s == 2 && m == CTL_IN_PLAIN);
     return combo && d->cin % 16 == 0 && d->cout % 16 == 0 && d->nsub == 1 && !(d->dt & (CTL_DT_BF16 | CTL_DT_X16 | CTL_DT_Y16 | CTL_DT_RES16));
 }
-static int wgrad3_pick(const ctl_conv* d, wgrad3_call* a) {
+static int wgrad3_pick(const ctl_conv* d, ctl_wgrad_call* a) {
     CTL_REQUIRE(ctl_wgrad_x3_ok(d), "wgrad(x3): CTL_DT_X3 needs fp32-stored tensors, cin %% 16 == 0, cout %% 16 == 0 and a 3x3 (stride 1 / 2) or 2x2 stride-2 "
                                     "kernel (got cin %d, cout %d, ks %d, stride %d, in_mode %d, dt %d)", d->cin, d->cout, d->ks, d->stride, d->in_mode, d->dt);
     a->d = d;
@@ -670,7 +653,7 @@ static int wgrad3_pick(const ctl_conv* d, wgrad3_call* a) {
     if (rc != CTL_OK) return rc;
     // (16x16-pixel tiles for the full-resolution 16-channel layers, the bf16 family's choice, measured slower here at two resident blocks per
     //  CU: 16->16 @256^2 45.0 vs 47.6 us, up-sampled 16->16 @128^2 42.4 vs 44.7 us, tools/sweep_wgrad_x3.sh -- the 8x16 tile stays)
-    a->ntw = (a->c.cot >= 2 && a->c.cot % 2 == 0) ? 2 : 1;
+    ctl_wgrad_geometry(*a);
     // stride-2 3x3 with two cout tiles: the 17x33-pixel input tile of an 8x16 output tile costs 238 + 126 registers -> ONE resident block per
     // CU; the 4x16 tile (194 registers, two blocks) is 7-15 % faster (tools/sweep_wgrad_x3_s2.sh: 16->32 @256^2 35.5 -> 33.2 us,
     // 32->64 @128^2 37.6 -> 32.1, 64->128 @64^2 35.0 -> 31.5); with one cout tile the 8x16 tile fits twice and stays (25.6 vs 27.6 us)
@@ -678,11 +661,11 @@ static int wgrad3_pick(const ctl_conv* d, wgrad3_call* a) {
     if (d->ks == 3 && d->stride == 2) {
         if (s2_ntw) a->ntw = s2_ntw;
         const int mt = s2_mt ? s2_mt : (a->ntw == 2 ? 1 : a->c.mt);
-        if (mt != a->c.mt) { a->c.mt = mt; a->c.th = 4 * mt; a->c.tiles_h = ctl_cdiv(d->hout, a->c.th); }
+        if (mt != a->c.mt) {
+            a->c.mt = mt; a->c.th = 4 * mt; a->c.tiles_h = ctl_cdiv(d->hout, a->c.th);
+            a->ntiles = d->n * a->c.tiles_h * a->c.tiles_w;
+        }
     }
-    a->ntiles = d->n * a->c.tiles_h * a->c.tiles_w;
-    a->cin_p = a->c.g * 16;
-    a->cout_p = a->c.cot * 16;
     a->pc = wgrad3_pc_pick(d, a) ? 1 : 0;
     a->query = true;
     rc = wgrad3_dispatch(*a);
@@ -690,12 +673,12 @@ static int wgrad3_pick(const ctl_conv* d, wgrad3_call* a) {
     return rc;
 }
 int ctl_wgrad_x3_splits(const ctl_conv* d) {
-    wgrad3_call a = {};
+    ctl_wgrad_call a = {};
     return wgrad3_pick(d, &a) == CTL_OK ? a.splits : -1;
 }
 int ctl_conv_wgrad_x3(const ctl_conv* d, const float* x, const float* pro_scale, const float* pro_shift, const float* dy, const float* dy2,
                       const float* dy_coef, float* w_partial, float* b_partial, ctl_stream stream) {
-    wgrad3_call a = {};
+    ctl_wgrad_call a = {};
     int rc = wgrad3_pick(d, &a);
     if (rc != CTL_OK) return rc;
     a.x = x; a.dy = dy; a.dy2 = dy2; a.dy_coef = dy_coef; a.pro_scale = pro_scale; a.pro_shift = pro_shift; a.w_partial = w_partial; a.b_partial = b_partial;
@@ -756,31 +739,22 @@ extern "C" int ctl_conv_wgrad_group(int32_t n, const ctl_conv* descs, const int3
     for (int i = 0; i < n; ++i) {
         const ctl_conv* d = &descs[i];
         CTL_REQUIRE(ctl_wgrad_group_class(d, dy2 && dy2[i]) == cls, "conv_wgrad_group: member %d is of another class than member 0", i);
-        CTL_REQUIRE(x[i] && dy[i] && w_partial[i] && (!d->pro_affine || (pro_scale && pro_shift && pro_scale[i] && pro_shift[i])) && (!(cls & 2) || (dy_coef && dy_coef[i])),
-                    "conv_wgrad_group: member %d misses a tensor", i);
-        // the coefficient tables a member actually stages (as in ctl_conv_wgrad_ex): the prologue's over groups * cin, the virtual output gradient's over groups * cout
-        {
-            const int ng = d->groups > 1 ? d->groups : 1;
-            CTL_REQUIRE((!d->pro_affine || ng * d->cin <= CTL_PRO_MAX) && (!(cls & 2) || ng * d->cout <= CTL_PRO_MAX),
-                        "conv_wgrad_group: member %d: groups * channels of a staged coefficient table > %d", i, CTL_PRO_MAX);
-        }
-        CTL_REQUIRE((int64_t)d->n * d->hin * d->win * d->cin * 4 < (1ll << 31) && (int64_t)d->n * d->hout * d->wout * d->cout * 4 < (1ll << 31),
-                    "conv_wgrad_group: tensors must stay below 2 GiB (32-bit buffer offsets)");
-        wgrad3_call a = {};
+        ctl_wgrad_call a = {};
         a.d = d;
-        int rc = ctl_conv_pick_cfg(d, &a.c, 1);
-        if (rc != CTL_OK) return rc;
-        a.ntiles = d->n * a.c.tiles_h * a.c.tiles_w;
-        a.cin_p = a.c.g * 16; a.cout_p = a.c.cot * 16;
-        CTL_REQUIRE(splits[i] >= 1 && splits[i] <= a.ntiles && a.c.mt == 2, "conv_wgrad_group: member %d: splits %d of %d tiles", i, splits[i], a.ntiles);
-        a.splits = splits[i];
         a.x = x[i]; a.pro_scale = pro_scale ? pro_scale[i] : nullptr; a.pro_shift = pro_shift ? pro_shift[i] : nullptr; a.dy = dy[i];
         a.dy2 = dy2 ? dy2[i] : nullptr; a.dy_coef = dy_coef ? dy_coef[i] : nullptr; a.w_partial = w_partial[i]; a.b_partial = b_partial ? b_partial[i] : nullptr;
+        int rc = ctl_wgrad_check(d, a.x, a.pro_scale, a.pro_shift, a.dy, a.dy2, a.dy_coef, a.w_partial, "conv_wgrad_group", i);
+        if (rc != CTL_OK) return rc;
+        rc = ctl_conv_pick_cfg(d, &a.c, 1);
+        if (rc != CTL_OK) return rc;
+        ctl_wgrad_geometry(a);
+        CTL_REQUIRE(splits[i] >= 1 && splits[i] <= a.ntiles && a.c.mt == 2, "conv_wgrad_group: member %d: splits %d of %d tiles", i, splits[i], a.ntiles);
+        a.splits = splits[i];
         wgrad3_fill_member(g.m[i], a, jobs);
         jobs += a.splits * (a.cin_p / 32) * (a.cout_p / 32);
-        const double pix = (double)d->n * d->hout * d->wout;
-        flops += 2.0 * pix * d->cout * d->cin * 9;
-        bytes += 4.0 * d->n * d->hin * d->win * d->cin + 4.0 * pix * d->cout * ((cls & 2) ? 2 : 1);
+        double f = 0.0, b = 0.0;
+        ctl_conv_work(d, a.dy2 != nullptr, &f, &b);
+        flops += f; bytes += b;
     }
     char kind[48];
     snprintf(kind, sizeof(kind), "conv_wgrad_x3grp<in%d%s>", cls & 1, (cls & 2) ? ",x2" : "");

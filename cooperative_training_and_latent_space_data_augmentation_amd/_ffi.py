@@ -4,6 +4,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import namedtuple
 
 import numpy as np
 
@@ -32,6 +33,98 @@ PACK_X3 = 16                         # or-ed into the mode word of a pack record
 LOSS_WCE, LOSS_FOCAL, LOSS_DICE, LOSS_FG_DICE = 0, 1, 2, 3      # CTL_LOSS_* kinds of ctl_seg_loss_fwd / ctl_seg_loss_bwd
 OP_DTYPE = np.dtype([("kind", "<i4"), ("i", "<i4", (27,)), ("f", "<f4", (4,)), ("slot", "<i4", (OP_MAX_T,)),
                      ("off", "<i8", (OP_MAX_T,)), ("l", "<i8", (4,))], align=True)
+
+# Where ctl_plan_run (csrc/ctl_plan.cpp) reads each operand of a record, per kind -- the lines of the "plan record layout" table of
+# include/ctl_hip.h, word for word (tests/test_plan_layout_cpu.py compares the two).  `KIND -> entry`: the entry the fields are handed to
+# under these, its parameter names.  Banks: i (int32 words: in order from 0, or `k=name` at word k; `conv` = a ctl_conv in i[0..23]),
+# l (int64), f (float), t (tensor slots: (slot, byte offset) pairs, slot -1 = NULL).  For READERS and hand-built records (tests, tools):
+# the emitters of nets.PlanBuilder still write these positions by hand.
+_OP_LAYOUT = """
+CONV -> ctl_conv_forward_ex | i: conv | t: x wpack bias pro_scale pro_shift res res_scale res_shift y stats_partial res2 x2 pool xout
+WGRAD -> ctl_conv_wgrad_ex | i: conv 24=group_splits | t: x pro_scale pro_shift dy w_partial b_partial dy2 dy_coef
+WGRAD_GROUP | i: members
+WGRAD_REDUCE -> ctl_wgrad_reduce | i: conv 24=accumulate | l: s_co s_ci s_kh s_kw | t: w_partial b_partial dw dbias
+PACK -> ctl_pack_weights | i: cout cin ks flip | l: s_co s_ci s_kh s_kw | t: src dst
+BN_FINALIZE -> ctl_bn_finalize_ex | i: blocks c update_running groups | l: count | f: eps momentum | t: partial gamma beta running_mean running_var num_batches_tracked scale shift save_mean save_invstd save_uvar
+BN_REPLAY -> ctl_bn_replay_running | i: n_rec | f: momentum | t: act buffers num_batches_tracked table
+BN_EVAL -> ctl_bn_eval_coeffs | i: c groups | f: eps | t: gamma beta running_mean running_var scale shift
+BN_ACT -> ctl_bn_act_dt | i: c groups 25=bf16_mask | l: pixels | f: slope | t: x scale shift y
+BWD_REDUCE -> ctl_bwd_reduce_dt | i: mode c groups 25=bf16_mask | l: pixels | f: slope | t: dy act_src bn_src scale shift partial ds
+BN_BWD_FINALIZE -> ctl_bn_bwd_finalize_ex | i: c accumulate groups blocks affine_groups | l: count | t: partial gamma save_mean save_invstd coef dgamma dbeta
+BWD_APPLY -> ctl_bwd_apply_dt | i: mode c groups 25=bf16_mask | l: pixels | f: slope | t: dy act_src bn_src scale shift coef ds dx
+CHAN_SUM_FINALIZE -> ctl_chan_sum_finalize | i: c accumulate | t: partial out
+SUMPOOL2 -> ctl_sumpool2_dt | i: n h w c accumulate 25=bf16_mask | t: dup dx
+SIGMOID_BWD -> ctl_sigmoid_bwd | l: count | t: dy y dx
+ZERO | l: nbytes | t: dst
+COPY | l: nbytes | t: src dst
+PACK_BATCH -> ctl_pack_weights_batched | i: n_rec form | l: max_total | t: params wpack table
+WGRAD_REDUCE_BATCH -> ctl_wgrad_reduce_batched | i: n_rec | l: max_blocks | t: scratch grad table
+DROPOUT2D -> ctl_dropout2d_dt | i: n hw c 25=bf16_mask | l: seed_or_salt | f: p | t: z keep state out keep_out
+"""
+OpLayout = namedtuple("OpLayout", "name entry conv fields")      # fields: {name: (bank, index)} in the line's order
+
+
+def _parse_op_layout(text: str) -> dict:
+    table = {}
+    for ln in text.strip().splitlines():
+        head, *banks = [s.strip() for s in ln.split("|")]
+        name, _, entry = [s.strip() for s in head.partition("->")]
+        fields, conv = {}, False
+        for bank, _, names in (b.partition(":") for b in banks):
+            k = 0
+            for tok in names.split():
+                if tok == "conv":
+                    conv = True
+                elif "=" in tok:
+                    fields[tok.split("=")[1]] = (bank, int(tok.split("=")[0]))
+                else:
+                    fields[tok] = (bank, k)
+                    k += 1
+        table[globals()["OP_" + name]] = OpLayout(name, entry or None, conv, fields)
+    return table
+
+
+OP_LAYOUT = _parse_op_layout(_OP_LAYOUT)
+
+
+def op_field(record, name: str):
+    """The field `name` of one plan record by OP_LAYOUT: an int (i, l), a float (f), the (slot, byte offset) of a tensor -- slot -1 = NULL --
+    or, for `conv`, the ctl_conv record at the head of i."""
+    lay = OP_LAYOUT[int(record["kind"])]
+    if name == "conv" and lay.conv:
+        return np.frombuffer(np.ascontiguousarray(record["i"]).tobytes()[:CONV_DTYPE.itemsize], dtype=CONV_DTYPE)[0]
+    if name not in lay.fields:
+        raise KeyError(f"a {lay.name} record has no field {name!r} (it has: {' '.join(lay.fields)})")
+    bank, k = lay.fields[name]
+    if bank == "t":
+        return int(record["slot"][k]), int(record["off"][k])
+    return float(record["f"][k]) if bank == "f" else int(record[bank][k])
+
+
+def new_op(kind: int, conv=None, **fields) -> np.ndarray:
+    """One plan record of `kind` from named fields (OP_LAYOUT): conv = a ctl_conv record, a tensor field = a (slot, byte offset) pair or
+    None; what is not named stays 0 / NULL.  A name the kind does not have raises."""
+    lay = OP_LAYOUT[kind]
+    unknown = [n for n in fields if n not in lay.fields]
+    if unknown or (conv is not None and not lay.conv):
+        raise KeyError(f"a {lay.name} record has no field {' '.join(unknown) or 'conv'!r} (it has: {' '.join(lay.fields)})")
+    r = np.zeros((), dtype=OP_DTYPE)
+    r["kind"] = kind
+    r["slot"][:] = -1
+    if conv is not None:
+        words = np.frombuffer(conv.tobytes(), dtype="<i4")
+        r["i"][:len(words)] = words
+    for name, v in fields.items():
+        bank, k = lay.fields[name]
+        if bank != "t":
+            r[bank][k] = v
+        elif v is not None:
+            r["slot"][k], r["off"][k] = v
+    return r
+
+
+# One row of the int64 table behind WGRAD_REDUCE_BATCH, columns in the word order ctl_hip.h documents ("reduce record")
+ReduceRow = namedtuple("ReduceRow", "w_off b_off dw_off db_off splits taps_ks cin cout cin_p cout_p s_co s_ci s_kh s_kw accumulate reserved")
 
 
 class CtlError(RuntimeError):

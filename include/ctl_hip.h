@@ -183,10 +183,12 @@ int ctl_wgrad_reduce(const ctl_conv* d, const float* w_partial, const float* b_p
                      float* dbias, int32_t accumulate, ctl_stream stream);
 
 /* Batched forms (one launch for a whole network): `table` is a device array of int64 records.
- * pack record   (12 words): src_off, dst_off (floats into params / wpack), cout, cin, ks, flip, s_co, s_ci, s_kh, s_kw, total, 0
+ * pack record   (12 words): src_off, dst_off (floats into params / wpack), cout, cin, ks, flip, s_co, s_ci, s_kh, s_kw, total, mode;
+ *                           total = the float count of the record's packed buffer, max_total the largest; mode = the layout (0 plain, 1 the 4x4 kernel
+ *                           summed from 3x3 taps, 2 / 3 a 2x2 phase with the phase in `flip`, 4 K-packed first layer), | CTL_PACK_X3
  * reduce record (16 words): w_off, b_off (floats into scratch; b_off < 0: none), dw_off, db_off (floats into grad; db_off < 0:
- *                           none), splits, taps|ks<<8, cin, cout, cin_p, cout_p, s_co, s_ci, s_kh, s_kw, accumulate, 0;
- *                           max_blocks = max over records of ceil((elements + cout) / (splits <= 64 ? 64 : 8)) */
+ *                           none), splits, taps_ks (taps | ks << 8), cin, cout, cin_p, cout_p, s_co, s_ci, s_kh, s_kw, accumulate,
+ *                           reserved (0); max_blocks = max over records of ceil((elements + cout) / (splits <= 64 ? 64 : 8)) */
 int ctl_pack_weights_batched(const float* params, float* wpack, const int64_t* table, int32_t n_rec, int64_t max_total,
                              ctl_stream stream);
 int ctl_wgrad_reduce_batched(const float* scratch, float* grad, const int64_t* table, int32_t n_rec, int64_t max_blocks,
@@ -223,8 +225,9 @@ int ctl_bn_finalize_ex(const float* partial, int32_t blocks, int32_t c, int64_t 
                        float* save_invstd, float* save_uvar, int32_t groups, ctl_stream stream);
 /* The running-statistics update of n_rec BatchNorm layers replayed from saved batch statistics (save_mean / save_uvar of a forward pass
  * whose activations are re-used instead of recomputed: the saliency pass of the targeted latent masks decodes, in training mode, the very
- * code the standard pass has just decoded -- util.py:214 after model.py:444 / 436-440).  table: n_rec x 6 int64 {save_mean byte offset in
- * `act`, save_uvar byte offset in `act`, running_mean / running_var float offsets in `buffers`, num_batches_tracked index, c}.
+ * code the standard pass has just decoded -- util.py:214 after model.py:444 / 436-440).  table: n_rec int64 records,
+ * replay record (6 words): save_mean_off, save_uvar_off (bytes into `act`), running_mean_off, running_var_off (floats into `buffers`),
+ *                           nbt_idx (index into num_batches_tracked), c;
  * Bit-identical to running the pass again: the same two floats enter the same momentum update. */
 int ctl_bn_replay_running(const void* act, float* buffers, int64_t* num_batches_tracked, const int64_t* table, int32_t n_rec,
                           float momentum, ctl_stream stream);
@@ -753,7 +756,37 @@ int ctl_adam_dev(float* p, const float* g, float* m, float* v, int64_t count, fl
 
 /* ------------------------------------------------------------------------------------------------ plans
  * A plan is an array of ctl_op executed in order on one stream: one C call per network pass (the Python host builds
- * it once per (network, shape, mode)).  Tensor arguments are (slot, byte offset) pairs resolved against `bases`. */
+ * it once per (network, shape, mode)).  Tensor arguments are (slot, byte offset) pairs resolved against `bases`.
+ *
+ * Plan record layout: where ctl_plan_run reads each operand of a record, one line per kind.  `KIND -> entry`: the fields are handed to
+ * that entry under these, its parameter names (a `groups` word of 0 is passed as 1).  Banks: `i:` int32 words i[0], i[1], ... in order,
+ * `k=name` = word i[k], `conv` = a ctl_conv in i[0..23]; `l:` l[0..]; `f:` f[0..]; `t:` tensor slots slot[0] / off[0], ... (slot -1 =
+ * NULL).  What a line does not name is not read to run the record (the in-process profiler also looks at i[25] and slot[6] of any
+ * non-conv record).  The binding keeps the same table (_ffi.OP_LAYOUT; tests/test_plan_layout_cpu.py compares them).
+ *   CONV -> ctl_conv_forward_ex | i: conv | t: x wpack bias pro_scale pro_shift res res_scale res_shift y stats_partial res2 x2 pool xout
+ *   WGRAD -> ctl_conv_wgrad_ex | i: conv 24=group_splits | t: x pro_scale pro_shift dy w_partial b_partial dy2 dy_coef
+ *   WGRAD_GROUP | i: members
+ *   WGRAD_REDUCE -> ctl_wgrad_reduce | i: conv 24=accumulate | l: s_co s_ci s_kh s_kw | t: w_partial b_partial dw dbias
+ *   PACK -> ctl_pack_weights | i: cout cin ks flip | l: s_co s_ci s_kh s_kw | t: src dst
+ *   BN_FINALIZE -> ctl_bn_finalize_ex | i: blocks c update_running groups | l: count | f: eps momentum | t: partial gamma beta running_mean running_var num_batches_tracked scale shift save_mean save_invstd save_uvar
+ *   BN_REPLAY -> ctl_bn_replay_running | i: n_rec | f: momentum | t: act buffers num_batches_tracked table
+ *   BN_EVAL -> ctl_bn_eval_coeffs | i: c groups | f: eps | t: gamma beta running_mean running_var scale shift
+ *   BN_ACT -> ctl_bn_act_dt | i: c groups 25=bf16_mask | l: pixels | f: slope | t: x scale shift y
+ *   BWD_REDUCE -> ctl_bwd_reduce_dt | i: mode c groups 25=bf16_mask | l: pixels | f: slope | t: dy act_src bn_src scale shift partial ds
+ *   BN_BWD_FINALIZE -> ctl_bn_bwd_finalize_ex | i: c accumulate groups blocks affine_groups | l: count | t: partial gamma save_mean save_invstd coef dgamma dbeta
+ *   BWD_APPLY -> ctl_bwd_apply_dt | i: mode c groups 25=bf16_mask | l: pixels | f: slope | t: dy act_src bn_src scale shift coef ds dx
+ *   CHAN_SUM_FINALIZE -> ctl_chan_sum_finalize | i: c accumulate | t: partial out
+ *   SUMPOOL2 -> ctl_sumpool2_dt | i: n h w c accumulate 25=bf16_mask | t: dup dx
+ *   SIGMOID_BWD -> ctl_sigmoid_bwd | l: count | t: dy y dx
+ *   ZERO | l: nbytes | t: dst
+ *   COPY | l: nbytes | t: src dst
+ *   PACK_BATCH -> ctl_pack_weights_batched | i: n_rec form | l: max_total | t: params wpack table
+ *   WGRAD_REDUCE_BATCH -> ctl_wgrad_reduce_batched | i: n_rec | l: max_blocks | t: scratch grad table
+ *   DROPOUT2D -> ctl_dropout2d_dt | i: n hw c 25=bf16_mask | l: seed_or_salt | f: p | t: z keep state out keep_out
+ * Not parameters of the entry named: group_splits (0: a launch of its own; else the record is a member of the WGRAD_GROUP record in front
+ * of it, with that many pixel splits), members (the next `members` records are WGRAD records served by one ctl_conv_wgrad_group launch),
+ * form (bit 0: bf16 fragments, ctl_pack_weights_bf16_batched instead; bit 1: the table has CTL_PACK_X3 records, ctl_pack_weights_x3_batched
+ * as well), and the ZERO / COPY fields (hipMemsetAsync of nbytes at dst / device-to-device hipMemcpyAsync of nbytes from src to dst). */
 enum ctl_op_kind {
     CTL_OP_CONV = 1, CTL_OP_WGRAD = 2, CTL_OP_WGRAD_REDUCE = 3, CTL_OP_PACK = 4, CTL_OP_BN_FINALIZE = 5,
     CTL_OP_BN_EVAL = 6, CTL_OP_BN_ACT = 7, CTL_OP_BWD_REDUCE = 8, CTL_OP_BN_BWD_FINALIZE = 9, CTL_OP_BWD_APPLY = 10,
@@ -767,8 +800,9 @@ enum ctl_op_kind {
 #define CTL_OP_MAX_T 14
 typedef struct ctl_op {
     int32_t kind;
-    int32_t i[27];                    /* CONV/WGRAD/WGRAD_REDUCE: i[0..23] = ctl_conv as int32 words, i[24] = accumulate; i[25] = bf16
-                                         storage mask of the element-wise ops; others: see ctl_plan.cpp */
+    int32_t i[27];                    /* per kind: the "plan record layout" table above.  CONV / WGRAD / WGRAD_REDUCE: i[0..23] = ctl_conv as
+                                         int32 words; i[24] = the group's split count on a WGRAD record, accumulate on a WGRAD_REDUCE
+                                         record; i[25] = bf16 storage mask of the element-wise ops */
     float   f[4];
     int32_t slot[CTL_OP_MAX_T];       /* -1 = NULL */
     int64_t off[CTL_OP_MAX_T];

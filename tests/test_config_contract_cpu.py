@@ -4,7 +4,6 @@ allocated; every other one compiles every plan the engine can ask for, and its n
 state-dict keys, same output shapes).  Plans are compiled on device="cpu"; no kernel runs here (tests/test_config_engine_gpu.py does that)."""
 import itertools
 
-import numpy as np
 import pytest
 import torch
 
@@ -13,7 +12,6 @@ from oracle import ref_cpu as O
 
 GRID = list(itertools.product([1, 3, 4], [1, 2, 3, 4, 8, 12, 16, 20], [1, 2, 4, 8, 16], ["fp32", "bf16"]))
 SIZES = [(2, 48, 64), (3, 80, 112)]                          # encoder inputs; the latents are 16 x smaller
-CW = nets.CONV_WORDS
 
 
 def the_rules(image_ch, num_classes, reduce_factor, dtype):
@@ -40,22 +38,18 @@ def compile_backward(net, fwd, groups, mask, need_dx):
     return net._compile_backward(fwd, "A", mask, need_dx, True, True)
 
 
-def conv_of(op):
-    return np.frombuffer(np.ascontiguousarray(op["i"][:CW]).tobytes(), dtype=_ffi.CONV_DTYPE)[0]
-
-
 def check_records(plan, dtype):
     """what the conv records of a plan may ask of the library at a width off the 16-grid"""
     ops, k, entries = plan.ops, 0, 0
     while k < len(ops):
         kind = int(ops[k]["kind"])
         if kind == _ffi.OP_WGRAD_GROUP:
-            for m in ops[k + 1:k + 1 + int(ops[k]["i"][0])]:
-                d = conv_of(m)
+            for m in ops[k + 1:k + 1 + _ffi.op_field(ops[k], "members")]:
+                d = _ffi.op_field(m, "conv")
                 assert int(m["kind"]) == _ffi.OP_WGRAD
                 assert d["cin"] % 16 == 0 and d["cout"] % 16 == 0, f"a {d['cin']} -> {d['cout']} weight gradient rides in a grouped launch"
         if kind in (_ffi.OP_CONV, _ffi.OP_WGRAD):
-            d = conv_of(ops[k])
+            d = _ffi.op_field(ops[k], "conv")
             cin, cout, dt = int(d["cin"]), int(d["cout"]), int(d["dt"])
             if dtype == "fp32":
                 assert not dt & ~_ffi.DT_X3
@@ -133,7 +127,7 @@ def test_every_grid_point_is_refused_at_construction_or_compiles_every_plan(imag
                 bwd = compile_backward(net, fwd, groups, (True,) * len(want), name != "image_encoder")
                 fits(net, bwd, check_records(bwd, dtype), groups)
                 if reduce_factor == 8 and groups == 1:
-                    members = sum(int(o["i"][0]) for o in bwd.ops if int(o["kind"]) == _ffi.OP_WGRAD_GROUP)
+                    members = sum(_ffi.op_field(o, "members") for o in bwd.ops if int(o["kind"]) == _ffi.OP_WGRAD_GROUP)
                     print(f"  {name} {n}x{h}x{w}: {members} grouped weight gradients")
     print(f"{cfg + (dtype,)}: compiled")
 

@@ -43,7 +43,7 @@ def test_plans_compile_for_all_modes():
         kinds = [int(o["kind"]) for o in p.ops]
         assert (_ffi.OP_BN_EVAL in kinds) == (mode == "C") and (_ffi.OP_BN_FINALIZE in kinds) == (mode != "C")
         if mode != "C":
-            upd = [int(o["i"][2]) for o in p.ops if int(o["kind"]) == _ffi.OP_BN_FINALIZE]
+            upd = [_ffi.op_field(o, "update_running") for o in p.ops if int(o["kind"]) == _ffi.OP_BN_FINALIZE]
             assert all(u == (1 if mode == "A" else 0) for u in upd) and len(upd) == 13       # 11 + 2 BatchNorm layers
     f = dec._compile_forward(2, 3, 4, "A")
     assert f.out_shapes == [(2, 48, 64, 4)]
@@ -74,17 +74,18 @@ def test_deferred_weight_gradients_are_grouped_at_the_end_of_a_backward_plan():
     table = b.table_np
     n_members = 0
     for k in groups:
-        n = int(b.ops[k]["i"][0])
+        n = _ffi.op_field(b.ops[k], "members")
         assert 2 <= n <= _ffi.WGRAD_GROUP_MAX
         cls = set()
         for m in b.ops[k + 1:k + 1 + n]:
             assert int(m["kind"]) == _ffi.OP_WGRAD
-            d = np.frombuffer(np.ascontiguousarray(m["i"][:nets.CONV_WORDS]).tobytes(), dtype=_ffi.CONV_DTYPE)[0]
-            sp = int(m["i"][nets.CONV_WORDS])
+            d = _ffi.op_field(m, "conv")
+            sp = _ffi.op_field(m, "group_splits")
             assert sp >= 1 and d["cin"] % 32 == 0 and d["cout"] % 32 == 0 and d["ks"] == 3 and d["stride"] == 1 and d["dt"] == _ffi.DT_X3
-            cls.add((int(d["in_mode"]), int(m["slot"][6]) >= 0))
-            rec = [r for r in table if int(r[0]) * 4 == int(m["off"][4])]          # the reduction record of this member's partial buffer
-            assert len(rec) == 1 and int(rec[0][4]) == sp
+            cls.add((int(d["in_mode"]), _ffi.op_field(m, "dy2")[0] >= 0))
+            # the reduction record of this member's partial buffer
+            rec = [r for r in map(_ffi.ReduceRow._make, table) if int(r.w_off) * 4 == _ffi.op_field(m, "w_partial")[1]]
+            assert len(rec) == 1 and int(rec[0].splits) == sp
         assert len(cls) == 1                                                       # one kernel instantiation per launch
         n_members += n
     assert n_members >= 8
@@ -109,19 +110,19 @@ def test_bf16_weight_gradients_are_stacked_by_kernel_instantiation():
     groups = [k for k, v in enumerate(kinds) if v == _ffi.OP_WGRAD_GROUP]
     assert len(groups) >= 3 and kinds[-1] == _ffi.OP_WGRAD_REDUCE_BATCH
     for k in groups:
-        n = int(b.ops[k]["i"][0])
+        n = _ffi.op_field(b.ops[k], "members")
         cls = set()
         for m in b.ops[k + 1:k + 1 + n]:
             assert int(m["kind"]) == _ffi.OP_WGRAD
-            d = np.frombuffer(np.ascontiguousarray(m["i"][:nets.CONV_WORDS]).tobytes(), dtype=_ffi.CONV_DTYPE)[0]
+            d = _ffi.op_field(m, "conv")
             assert d["dt"] & _ffi.DT_BF16
-            c = int(_ffi.lib.ctl_wgrad_group_class(_ffi.desc_ptr(np.atleast_1d(d)), 1 if int(m["slot"][6]) >= 0 else 0))
+            c = int(_ffi.lib.ctl_wgrad_group_class(_ffi.desc_ptr(np.atleast_1d(d)), 1 if _ffi.op_field(m, "dy2")[0] >= 0 else 0))
             assert c >= 0x100
             cls.add(c)
-            sp = int(m["i"][nets.CONV_WORDS])
+            sp = _ffi.op_field(m, "group_splits")
             assert 1 <= sp <= int(_ffi.lib.ctl_wgrad_splits(_ffi.desc_ptr(np.atleast_1d(d))))
-            rec = [r for r in b.table_np if int(r[0]) * 4 == int(m["off"][4])]
-            assert len(rec) == 1 and int(rec[0][4]) == sp
+            rec = [r for r in map(_ffi.ReduceRow._make, b.table_np) if int(r.w_off) * 4 == _ffi.op_field(m, "w_partial")[1]]
+            assert len(rec) == 1 and int(rec[0].splits) == sp
         assert len(cls) == 1
     nets.GROUP_WGRAD_BF16 = False
     try:

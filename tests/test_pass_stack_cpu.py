@@ -82,9 +82,9 @@ def test_mode_b_passes_are_masked_out_of_the_affine_gradients():
     fin = [o for o in b.ops if int(o["kind"]) == _ffi.OP_BN_BWD_FINALIZE]
     assert len(fin) >= 10
     for o in fin:
-        assert int(o["i"][2]) == 2 and int(o["i"][4]) == 0b01 and int(o["slot"][5]) >= 0      # two groups, group 0 only adds to dgamma / dbeta
+        assert _ffi.op_field(o, "groups") == 2 and _ffi.op_field(o, "affine_groups") == 0b01 and _ffi.op_field(o, "dgamma")[0] >= 0      # two groups, group 0 only adds to dgamma / dbeta
     b_all = compile_backward(net, view, 2, (True, True), False, amask=0)
-    assert all(int(o["i"][4]) == 0 for o in b_all.ops if int(o["kind"]) == _ffi.OP_BN_BWD_FINALIZE)
+    assert all(_ffi.op_field(o, "affine_groups") == 0 for o in b_all.ops if int(o["kind"]) == _ffi.OP_BN_BWD_FINALIZE)
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
@@ -109,14 +109,14 @@ def test_nothing_of_one_compile_reaches_the_next(name, h, dtype):
     f2 = net._compile_forward(2, h, h, "A", groups=2, pp=(1, 2))
     b2 = net._compile_backward(f2, "A", mask, True, True, True, affine_mask=1, split_tail=True)
     assert f2.groups == b2.groups == 2 and b2.main_ops is not None
-    assert any(int(o["i"][4]) == 1 for o in b2.ops if int(o["kind"]) == _ffi.OP_BN_BWD_FINALIZE)
+    assert any(_ffi.op_field(o, "affine_groups") == 1 for o in b2.ops if int(o["kind"]) == _ffi.OP_BN_BWD_FINALIZE)
     used = default_pair(net)
     torch.manual_seed(0)
     fresh = default_pair(nets.build_networks(device="cpu", dtype=dtype)[name])
     for a, b in zip(used, fresh):
         same(a, b)
     assert used[0].groups == used[1].groups == 1 and used[0].act_bytes < f2.act_bytes       # (one slot of one group, not two stacked ones)
-    assert all(int(o["i"][4]) == 0 for o in used[1].ops if int(o["kind"]) == _ffi.OP_BN_BWD_FINALIZE)
+    assert all(_ffi.op_field(o, "affine_groups") == 0 for o in used[1].ops if int(o["kind"]) == _ffi.OP_BN_BWD_FINALIZE)
 
 
 def test_gather_stacked_uses_views_of_one_allocation_without_a_copy():
@@ -161,6 +161,6 @@ def test_split_backward_plan_is_the_plan_with_the_weight_gradient_family_moved_b
     assert int(b.main_ops[0]["kind"]) == _ffi.OP_ZERO                    # the gradient buffer is cleared before either part writes into it
     for k, o in enumerate(b.tail_ops):
         if int(o["kind"]) == _ffi.OP_BWD_REDUCE:                         # only as the reduction of a channel sum, directly in front of its finalize
-            assert int(o["i"][0]) == 2 and int(b.tail_ops[k + 1]["kind"]) == _ffi.OP_CHAN_SUM_FINALIZE
+            assert _ffi.op_field(o, "mode") == 2 and int(b.tail_ops[k + 1]["kind"]) == _ffi.OP_CHAN_SUM_FINALIZE
     # an unsplit compile of the same view carries no parts
     assert compile_backward(net, view, 2, mask, name != "image_encoder").main_ops is None

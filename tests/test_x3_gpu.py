@@ -427,12 +427,7 @@ def test_member_record_without_its_group_record_is_refused():
     sized for the group's splits."""
     import ctypes
     d = _ffi.conv_desc(n=2, hin=16, win=16, cin=32, hout=16, wout=16, cout=32, ks=3, dt=_ffi.DT_X3)
-    op = np.zeros(1, dtype=_ffi.OP_DTYPE)
-    op["kind"] = _ffi.OP_WGRAD
-    op["slot"][:] = -1
-    words = np.frombuffer(d.tobytes(), dtype="<i4")
-    op["i"][0, :len(words)] = words
-    op["i"][0, len(words)] = 3
+    op = _ffi.new_op(_ffi.OP_WGRAD, d, group_splits=3)
     bases = (ctypes.c_void_p * 17)()
     rc = lib.ctl_plan_run(op.ctypes.data, 1, bases, 17, ops.stream_ptr())
     assert rc != 0 and "WGRAD_GROUP" in lib.ctl_last_error().decode()

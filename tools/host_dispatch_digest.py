@@ -223,39 +223,28 @@ def refusals():
         said(f"{fam} group splits above the tiles", group_call([m(), m()], splits=[1, 1000]))
     # ---- ctl_plan_run
     d = _ffi.conv_desc(**base, dt=_ffi.DT_X3)
-    words = np.frombuffer(d.tobytes(), dtype="<i4")
 
     def wgrad_op(splits, slots):
-        op = np.zeros((), dtype=_ffi.OP_DTYPE)
-        op["kind"] = _ffi.OP_WGRAD
-        op["i"][:len(words)] = words
-        op["i"][len(words)] = splits
-        op["slot"][:] = -1
-        for a, s in slots.items():
-            op["slot"][a] = s
-        return op
+        """slots: tensor name -> slot (at byte offset 0)"""
+        return _ffi.new_op(_ffi.OP_WGRAD, d, group_splits=splits, **{name: (s, 0) for name, s in slots.items()})
 
     def group_op(n):
-        op = np.zeros((), dtype=_ffi.OP_DTYPE)
-        op["kind"] = _ffi.OP_WGRAD_GROUP
-        op["i"][0] = n
-        op["slot"][:] = -1
-        return op
+        return _ffi.new_op(_ffi.OP_WGRAD_GROUP, members=n)
 
     def run(label, ops, bases):
         arr = np.ascontiguousarray(np.concatenate([np.atleast_1d(o) for o in ops]))
         said(label, lib.ctl_plan_run(arr.ctypes.data, len(ops), ptrs(bases), len(bases), None))
 
-    full = {0: 0, 3: 0, 4: 0, 5: 0}
+    full = dict(x=0, dy=0, w_partial=0, b_partial=0)
     run("plan member record without its GROUP record", [wgrad_op(3, full)], [DUMMY])
-    run("plan op uses an empty slot", [wgrad_op(0, {**full, 3: 1})], [DUMMY, None])
-    run("plan op uses a slot past the table", [wgrad_op(0, {**full, 4: 2})], [DUMMY, None])
-    run("plan group member uses an empty slot", [group_op(2), wgrad_op(1, full), wgrad_op(1, {**full, 0: 1})], [DUMMY, None])
+    run("plan op uses an empty slot", [wgrad_op(0, {**full, "dy": 1})], [DUMMY, None])
+    run("plan op uses a slot past the table", [wgrad_op(0, {**full, "w_partial": 2})], [DUMMY, None])
+    run("plan group member uses an empty slot", [group_op(2), wgrad_op(1, full), wgrad_op(1, {**full, "x": 1})], [DUMMY, None])
     run("plan group of 0", [group_op(0), wgrad_op(1, full)], [DUMMY])
     run("plan group of 9", [group_op(9)] + [wgrad_op(1, full)] * 9, [DUMMY])
     run("plan group past the end", [group_op(2), wgrad_op(1, full)], [DUMMY])
     run("plan group member is not a WGRAD record", [group_op(2), wgrad_op(1, full), group_op(1)], [DUMMY])
-    run("plan group member misses a tensor", [group_op(2), wgrad_op(1, full), wgrad_op(1, {0: 0, 4: 0})], [DUMMY])
+    run("plan group member misses a tensor", [group_op(2), wgrad_op(1, full), wgrad_op(1, dict(x=0, w_partial=0))], [DUMMY])
     run("plan unknown kind", [np.zeros((), dtype=_ffi.OP_DTYPE)], [DUMMY])
 
 

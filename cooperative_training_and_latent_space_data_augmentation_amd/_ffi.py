@@ -218,6 +218,8 @@ def _signatures() -> dict:
         "ctl_cc_ws_bytes": (sz, [i32] * 5),
         "ctl_cc_label": (int_, [p] + [i32] * 6 + [p, p]),
         "ctl_cc_keep_largest": (int_, [p] + [i32] * 6 + [p, p, p, sz, p]),
+        "ctl_predictive_stats_ws_bytes": (sz, [i32, i32, i64, i32, i32]),
+        "ctl_predictive_stats": (int_, [p, p, i32, i32, i64, i32, i32, f32, i32] + [p] * 9),
         "ctl_aug_ws_bytes": (sz, [i32, i32, i32]),
         "ctl_aug_warp_ws_bytes": (sz, [i32] * 5),
         "ctl_aug_field": (int_, [p] * 4 + [i32, i32, i32, p, p, sz, p]),

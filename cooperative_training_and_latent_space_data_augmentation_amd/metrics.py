@@ -253,31 +253,50 @@ class runningMySegmentationScore(object):
     readback of their small tables per patient: no label volume leaves the device.  numpy inputs run scipy on the host, as upstream.
     'HD95' (`hd95_2D_stack`, with the conventions of 'HD') and 'ASSD' (`assd`, with those of 'ASD') are this project's additions to the
     table: 'HD95' comes from `ops.surface_quantiles`, in the same launches as 'HD' when both are asked for, 'ASSD' from the table of
-    'ASD'."""
-    SUPPORTED = ("Dice", "VolError", "VolSim", "HD", "ASD", "HD95", "ASSD")
+    'ASD'.
+    'ECE', 'NLL', 'Brier' and 'Entropy' (also additions) are PATIENT-level columns, named exactly so and appended after the per-class
+    columns: expected calibration error over `calibration_bins` equal-width confidence bins, mean negative log-likelihood (nats), mean
+    Brier score and mean predictive entropy (bits) of the logits handed to `update` (uncertainty.py).  Device logits: one
+    `ops.predictive_stats` call whose two small tables join the voxel counts' readback; numpy logits: the float64 host statement."""
+    SUPPORTED = ("Dice", "VolError", "VolSim", "HD", "ASD", "HD95", "ASSD")      # one column per foreground class
+    PATIENT_LEVEL = ("ECE", "NLL", "Brier", "Entropy")                          # one column per patient, accepted in metrics_list as well
 
-    def __init__(self, n_classes, idx2cls_dict=None, metrics_list=("Dice",), foreground_only=False):
+    def __init__(self, n_classes, idx2cls_dict=None, metrics_list=("Dice",), foreground_only=False, calibration_bins=15):
         self.n_classes, self.metrics, self.foreground_only = n_classes, list(metrics_list), foreground_only
         if idx2cls_dict is None:
             idx2cls_dict = {1: "foreground"} if foreground_only else {c: str(c) for c in range(n_classes)}
         self.idx2cls_dict = idx2cls_dict
         self.multi_scores, self.tables, self.header = {}, [], ["patient_id"]
+        for m in self.metrics:
+            if m not in self.SUPPORTED + self.PATIENT_LEVEL:
+                raise NotImplementedError(f"metric {m!r}: only {self.SUPPORTED + self.PATIENT_LEVEL} are computed by this build")
+        self.calibration_bins = int(calibration_bins)
+        self.patient_metrics = [m for m in self.metrics if m in self.PATIENT_LEVEL]
+        self.metrics = [m for m in self.metrics if m not in self.PATIENT_LEVEL]
         for c, name in idx2cls_dict.items():
             if c > 0:
                 for m in self.metrics:
-                    if m not in self.SUPPORTED:
-                        raise NotImplementedError(f"metric {m!r}: only {self.SUPPORTED} are computed by this build")
                     self.multi_scores[name + "_" + m] = []
                     self.header.append(name + "_" + m)
+        for m in self.patient_metrics:
+            self.multi_scores[m] = []
+            self.header.append(m)
 
-    def _counts(self, preds, gts):
+    def _counts(self, preds, gts, extra=None):
         """-> (pred_count[c], gt_count[c], intersection[c]) as the reference's per-class binarisation counts them
-        (metrics.py:205-223): a ground-truth label outside [0, n) belongs to no class, the predicted voxel under it still counts."""
+        (metrics.py:205-223): a ground-truth label outside [0, n) belongs to no class, the predicted voxel under it still counts.
+        extra: flat int64 device tensors that ride along in the device branch's readback; their host copy is left in self._readback."""
         import torch
         n = self.n_classes
+        self._readback = None
         if torch.is_tensor(preds) and torch.is_tensor(gts) and preds.is_cuda and gts.is_cuda:
             from . import ops
-            both = torch.stack([ops.confusion_hist(gts, preds, n), ops.confusion_hist(preds, preds, n)]).cpu().numpy()
+            both = torch.stack([ops.confusion_hist(gts, preds, n), ops.confusion_hist(preds, preds, n)])
+            if extra:
+                flat = torch.cat([both.reshape(-1)] + list(extra)).cpu().numpy()
+                both, self._readback = flat[:2 * n * n].reshape(2, n, n), flat[2 * n * n:]
+            else:
+                both = both.cpu().numpy()
             h, hp = both[0], both[1]
             if self.foreground_only and int(h.sum()) != gts.numel():
                 raise ValueError("foreground_only with labels outside [0, n_classes): pass host arrays")
@@ -322,13 +341,68 @@ class runningMySegmentationScore(object):
             lo += t.numel()
         return out
 
-    def update(self, pid, preds, gts, voxel_spacing=None):
-        """preds / gts: integer volumes [n_slices, H, W] (numpy, or both torch tensors on the GPU); returns the patient's row."""
+    def calibration_tables(self, logits, gts, members=1):
+        """The (stats, bins) tables of one chunk of slices (uncertainty.py): logits [members * n, C, H, W], gts [n, H, W].  Device logits
+        -> ops.PredictiveStats with device tables (2 launches, nothing read back); numpy logits -> the float64 host statement.  The
+        tables are per slice, so the chunks of a patient concatenate: `update(logits=[...])` takes a list of these."""
+        import torch
+        if torch.is_tensor(logits) and logits.is_cuda:
+            from . import ops
+            label = torch.as_tensor(gts).to(device=logits.device, dtype=torch.int64).contiguous()
+            return ops.predictive_stats(logits.float(), label, members=members, n_bins=self.calibration_bins, want=())
+        from . import uncertainty
+        host = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)      # noqa: E731
+        return uncertainty.predictive_stats_host(host(logits), host(gts), members=members, n_bins=self.calibration_bins)
+
+    def _calibration(self, logits, gts, members):
+        """-> (chunk tables, flat int64 device tensors for the joined readback): `logits` is one array / tensor of the whole volume, or a
+        list of chunks along the slice axis, each an array / tensor or the result of `calibration_tables`."""
+        import torch
+        chunks, lo, tabs = (list(logits) if isinstance(logits, (list, tuple)) and not hasattr(logits, "stats") else [logits]), 0, []
+        for ch in chunks:
+            if not hasattr(ch, "stats"):
+                n = int(ch.shape[0]) // int(members)
+                ch = self.calibration_tables(ch, gts[lo:lo + n], members)
+            lo += int(ch.stats.shape[0])
+            tabs.append(ch)
+        if lo != int(gts.shape[0]):
+            raise ValueError(f"the logits cover {lo} slices, the volume has {int(gts.shape[0])}")
+        on_device = [torch.is_tensor(t.stats) for t in tabs]
+        if any(on_device) and not all(on_device):
+            raise ValueError("the chunks of one patient's logits must all be on the device or all on the host")
+        extra = [q for t in tabs for q in (t.stats.reshape(-1).view(torch.int64), t.bins.reshape(-1))] if all(on_device) else []
+        return tabs, extra      # (fp64 bits ride as int64)
+
+    def _calibration_scores(self, tabs, extra, readback, pixels):
+        """the four columns from the chunk tables; `readback`: the host copy of `extra` when it rode along with the voxel counts"""
+        from . import uncertainty
+        import torch
+        if extra:
+            flat = readback if readback is not None else torch.cat(extra).cpu().numpy()
+            stats, bins, lo = [], [], 0
+            for t in tabs:
+                ns, nb = t.stats.numel(), t.bins.numel()
+                stats.append(flat[lo:lo + ns].view(np.float64).reshape(-1, 6))
+                bins.append(flat[lo + ns:lo + ns + nb].reshape(tuple(t.bins.shape)))
+                lo += ns + nb
+        else:
+            stats, bins = [np.asarray(t.stats) for t in tabs], [np.asarray(t.bins) for t in tabs]
+        return uncertainty.calibration_from_tables(np.concatenate(stats), np.concatenate(bins), pixels=pixels)
+
+    def update(self, pid, preds, gts, voxel_spacing=None, logits=None, members=1):
+        """preds / gts: integer volumes [n_slices, H, W] (numpy, or both torch tensors on the GPU); returns the patient's row.
+        logits (for 'ECE' / 'NLL' / 'Brier' / 'Entropy'): the volume's logits [members * n_slices, C, H, W], member-major, on the device
+        or as numpy, or a list of chunks along the slice axis (see `calibration_tables`)."""
         if tuple(preds.shape) != tuple(gts.shape):
             raise AssertionError(f"pid :{pid} shape not consistent: pred {tuple(preds.shape)} vs gt {tuple(gts.shape)}")
         if voxel_spacing is not None and len(voxel_spacing) != 3:
             raise AssertionError(f"check voxel spacing, {voxel_spacing}")
-        pc, gc, ic = self._counts(preds, gts)
+        cal_tabs, extra = None, None
+        if self.patient_metrics:
+            if logits is None:
+                raise ValueError(f"{self.patient_metrics} need the logits of the volume: update(..., logits=, members=)")
+            cal_tabs, extra = self._calibration(logits, gts, members)
+        pc, gc, ic = self._counts(preds, gts, extra)
         surf = [m for m in self.metrics if m in ("HD", "ASD", "HD95", "ASSD")]
         if surf:
             if voxel_spacing is None:
@@ -376,6 +450,11 @@ class runningMySegmentationScore(object):
                     score = float(1 - np.abs(v1 - v2) / np.abs(float(v2 + v1)))
                 self.multi_scores[name + "_" + m].append(score)
                 row.append(score)
+        if cal_tabs is not None:
+            cal = self._calibration_scores(cal_tabs, extra, self._readback, int(np.prod(tuple(gts.shape))))
+            for m in self.patient_metrics:
+                self.multi_scores[m].append(cal[m])
+                row.append(cal[m])
         self.tables.append(row)
         return row
 

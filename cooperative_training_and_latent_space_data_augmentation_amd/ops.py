@@ -6,6 +6,7 @@ PyTorch is used here only for device memory and the stream handle.  4-D activati
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 from typing import Optional
 
 import numpy as np
@@ -303,6 +304,47 @@ def argmax_c(logit: torch.Tensor) -> torch.Tensor:
     out = torch.empty((n, h, w), dtype=torch.uint8, device=logit.device)
     call("ctl_argmax_c", ptr(logit), ptr(out), n * h * w, c, stream_ptr())
     return out
+
+
+# ---------------------------------------------------------------------------------------------- predictive uncertainty
+PredictiveStats = namedtuple("PredictiveStats", "entropy mi conf pred mean_prob stats bins")      # maps that were not asked for are None
+UNCERT_MAPS = PredictiveStats._fields[:5]
+
+
+def predictive_stats(logits: torch.Tensor, label: Optional[torch.Tensor] = None, members: int = 1, n_bins: int = 15, eps: float = 1e-7,
+                     is_prob: bool = False, want=("entropy",)) -> PredictiveStats:
+    """Uncertainty maps and calibration tables of an ensemble of `members` predictions (include/ctl_hip.h "predictive uncertainty"; the
+    float64 statement is uncertainty.predictive_stats_host).  logits: fp32 device tensor [members * n, C, H, W], member-major, C <= 16
+    (is_prob: probabilities, the softmax is skipped); label: int64 device tensor [n, H, W] or None, a value outside 0..C-1 = unlabelled.
+    want: which of 'entropy', 'mi', 'conf' (fp32 [n,H,W]; entropies in bits), 'pred' (uint8 [n,H,W]) and 'mean_prob' (fp32 [n,C,H,W],
+    channels_last) to write.  Always returned: stats, fp64 [n,6] = per slice (labelled pixels, correct, sum H, sum MI, sum nll, sum brier)
+    and bins, int64 [n,n_bins,3] = per slice and reliability bin (labelled pixels, correct, sum of conf * 2^32); uncertainty.
+    calibration_from_tables finishes ECE / NLL / Brier from them on the host.  2 launches, no readback, the same bits on every call."""
+    who = "predictive_stats"
+    want = (want,) if isinstance(want, str) else tuple(want)
+    unknown = [m for m in want if m not in UNCERT_MAPS]
+    if unknown:
+        raise ValueError(f"{who}: unknown map {unknown[0]!r} (one of {', '.join(UNCERT_MAPS)})")
+    require_gpu(logits, label)
+    _arg(logits, torch.float32, (None, None, None, None), who, "logits")
+    tn, c, h, w = (int(v) for v in logits.shape)
+    t = int(members)
+    if t < 1 or tn % t:
+        raise ValueError(f"{who}: {tn} logit slices do not divide into {members} members")
+    n = tn // t
+    if label is not None:
+        _arg(label, torch.int64, (n, h, w), who, "label", dense=True)
+    x, dev = as_nhwc(logits), logits.device
+    outs = {m: None for m in UNCERT_MAPS}
+    for m in want:
+        outs[m] = (empty_nhwc(n, c, h, w, dev) if m == "mean_prob" else
+                   torch.empty((n, h, w), dtype=torch.uint8 if m == "pred" else torch.float32, device=dev))
+    stats = torch.empty((n, 6), dtype=torch.float64, device=dev)
+    bins = torch.empty((n, max(int(n_bins), 1), 3), dtype=torch.int64, device=dev)
+    ws, _ = _workspace("ctl_predictive_stats_ws_bytes", t, n, h * w, c, int(n_bins), device=dev, floor=8)      # 0 bytes: the call names the reason
+    call("ctl_predictive_stats", ptr(x), ptr(label), t, n, h * w, c, int(n_bins), float(eps), int(bool(is_prob)), *[ptr(outs[m]) for m in UNCERT_MAPS],
+         ptr(stats), ptr(bins), ptr(ws), stream_ptr())
+    return PredictiveStats(stats=stats, bins=bins, **outs)
 
 
 # ---------------------------------------------------------------------------------------------- latent masking

@@ -9,7 +9,10 @@ full-volume `.cpu().numpy()` copies per chunk.  The dataset only has to offer wh
 device (prepare.prepare_patient: no upload at all).  Writing nrrd files (SimpleITK) is outside the path and not offered.
 With native_grid=True (a project addition, off by default) the logits are put back on the patient's native grid on the device
 (ops.restore_scores) and post-processing and the metrics run there; the packs then carry 'geometry' and 'native_label'
-(prepare.prepare_patient(want_geometry=True))."""
+(prepare.prepare_patient(want_geometry=True)).
+With 'ECE' / 'NLL' / 'Brier' / 'Entropy' in metrics_list (project additions, metrics.runningMySegmentationScore) every chunk's logits go through
+ops.predictive_stats while they are on the device and only its small per-slice tables are kept; uncertainty_maps=True adds the 'entropy' and
+'conf' maps of the volume to the patient's result."""
 import os
 
 import numpy as np
@@ -68,7 +71,8 @@ class TestSegmentationNetwork(object):
 
     def __init__(self, test_dataset, crop_size, segmentation_model, use_gpu=True, save_path="", summary_report_file_name="result.csv",
                  detailed_report_file_name="details.csv", patient_wise=True, metrics_list=("Dice", "HD"), foreground_only=False,
-                 save_soft_prediction=False, keep_results=True, post_process=None, native_grid=False, restore_mode="logit"):
+                 save_soft_prediction=False, keep_results=True, post_process=None, native_grid=False, restore_mode="logit",
+                 uncertainty_maps=False):
         if not use_gpu:
             raise ValueError("this build has no CPU path")
         if post_process not in POST_PROCESS:
@@ -76,6 +80,11 @@ class TestSegmentationNetwork(object):
         if restore_mode not in ops.RESTORE_MODES:
             raise ValueError("restore_mode {!r}: one of {}".format(restore_mode, sorted(ops.RESTORE_MODES)))
         self.post_process, self.native_grid, self.restore_mode = post_process, bool(native_grid), restore_mode
+        self.calibration = any(m in runningMySegmentationScore.PATIENT_LEVEL for m in metrics_list)
+        self.uncertainty_maps = bool(uncertainty_maps)
+        if self.native_grid and (self.calibration or self.uncertainty_maps):
+            raise ValueError("native_grid=True with {} or uncertainty_maps: the logits live on the window grid, calibration on the native grid "
+                             "is not offered".format(list(runningMySegmentationScore.PATIENT_LEVEL)))
         self.test_dataset, self.crop_size, self.segmentation_model = test_dataset, crop_size, segmentation_model
         self.num_classes = segmentation_model.num_classes
         self.segmentation_metric = runningMySegmentationScore(n_classes=self.num_classes,
@@ -93,7 +102,7 @@ class TestSegmentationNetwork(object):
         for i in range(n):
             pack = self.test_dataset.get_patient_data_for_testing(i, crop_size=self.crop_size) if self.patient_wise else self.test_dataset[i]
             pid, result = self.evaluate(i, pack, n)
-            if self.keep_results:
+            if self.keep_results or self.uncertainty_maps:
                 self.result_dict[pid] = result
         join = os.path.join
         self.segmentation_metric.get_scores(save_path=join(self.save_path, self.summary_report_file_name) if self.save_path else None)
@@ -113,7 +122,10 @@ class TestSegmentationNetwork(object):
         native_grid: the pack carries 'geometry' (prepare.Geometry) and 'native_label' [n,h,w]; every chunk's logits are restored into one
         native uint8 volume (ops.restore_scores, mode `restore_mode`: one more launch per chunk), `post_process` and the metric update
         take that volume and the native label, and get_voxel_spacing() is then the native spacing.  The four keys of the result keep
-        their meaning (window grid); 'native_pred' and 'native_label' are added."""
+        their meaning (window grid); 'native_pred' and 'native_label' are added.
+        Calibration columns: one ops.predictive_stats call per chunk on the logits `predict` just returned (2 launches); the per-slice
+        tables join the metric's one readback, no logits are kept for it.  uncertainty_maps: the same call also writes the chunk's
+        'entropy' and 'conf' maps, which are added to the result (the only keys when nothing else is kept)."""
         dev = torch.device("cuda", torch.cuda.current_device())
         image = data_tensor_pack["image"]
         if image.dim() == 5:                              # DataLoader(batch_size=1) adds a leading axis upstream
@@ -141,6 +153,7 @@ class TestSegmentationNetwork(object):
             native_d = torch.empty((total,) + tuple(geo.native_hw), dtype=torch.uint8, device=dev)
         pred_d = torch.empty((total, image_d.shape[-2], image_d.shape[-1]), dtype=torch.uint8, device=dev)
         soft = [] if (self.save_soft_prediction or self.keep_results) else None
+        uncert = [] if (self.calibration or self.uncertainty_maps) else None
         for lo in range(0, total, maximum_batch_size):
             hi = min(total, lo + maximum_batch_size)
             logit = self.segmentation_model.predict(input=image_d[lo:hi], softmax=False)
@@ -150,6 +163,9 @@ class TestSegmentationNetwork(object):
                 pred_d[lo:hi] = ops.argmax_c(logit)
             if soft is not None:
                 soft.append(logit)
+            if uncert is not None:
+                uncert.append(ops.predictive_stats(logit, label_d[lo:hi], n_bins=self.segmentation_metric.calibration_bins,
+                                                   want=("entropy", "conf") if self.uncertainty_maps else ()))
         scored_d, scored_label_d = (pred_d, label_d) if native_d is None else (native_d, native_label_d)
         if self.post_process is not None:                 # largest component of every class (post_process.py:5-22), in place on the device
             per_slice = POST_PROCESS[self.post_process]
@@ -157,7 +173,8 @@ class TestSegmentationNetwork(object):
             if native_d is not None and soft is not None:
                 ops.keep_largest_components(pred_d, self.num_classes, per_slice=per_slice, out=pred_d)
         spacing = self.test_dataset.get_voxel_spacing() if hasattr(self.test_dataset, "get_voxel_spacing") else None
-        self.segmentation_metric.update(pid=pid, preds=scored_d, gts=scored_label_d, voxel_spacing=spacing)
+        self.segmentation_metric.update(pid=pid, preds=scored_d, gts=scored_label_d, voxel_spacing=spacing,
+                                        logits=uncert if self.calibration else None)
         result = None
         if soft is not None:
             soft_np = torch.cat(soft, 0).float().cpu().numpy()
@@ -166,8 +183,12 @@ class TestSegmentationNetwork(object):
                       "pred": pred_d.cpu().numpy(), "soft_pred": soft_np}
             if native_d is not None:
                 result["native_pred"], result["native_label"] = native_d.cpu().numpy(), native_label_d.cpu().numpy()
-            if total == 1:
-                result = {k: v[0] for k, v in result.items()}
+        if self.uncertainty_maps:
+            result = {} if result is None else result
+            result["entropy"] = torch.cat([u.entropy for u in uncert], 0).cpu().numpy()
+            result["conf"] = torch.cat([u.conf for u in uncert], 0).cpu().numpy()
+        if result is not None and total == 1:
+            result = {k: v[0] for k, v in result.items()}
         if self.save_soft_prediction and self.save_path:
             out = os.path.join(self.save_path, "pred_npy")
             os.makedirs(out, exist_ok=True)

@@ -496,6 +496,46 @@ int ctl_cc_label(const uint8_t* labelmap, int32_t d, int32_t h, int32_t w, int32
 int ctl_cc_keep_largest(const uint8_t* labelmap, int32_t d, int32_t h, int32_t w, int32_t n_class, int32_t mode, int32_t connectivity,
                         uint8_t* out, int64_t* table, void* workspace, size_t workspace_bytes, ctl_stream stream);
 
+/* ------------------------------------------------------------------------------------------------ predictive uncertainty
+ * Entropy maps (medseg/common_utils/uncertainty.py:7-54) and the sums behind ECE / NLL / Brier (medseg/models/custom_loss.py:495-511 is the
+ * Brier double sum) of logits the device already holds, for an ensemble of T members (ctl_uncert.hip).
+ *   logits  fp32 NHWC [T][n][hw][C], member-major: member t of slice b is row t * n + b.  1 <= T <= CTL_UNCERT_MAX_MEMBERS, 1 <= C <= 16.
+ *           is_prob != 0: the rows already are probabilities (what upstream's entropy functions take) and the softmax is skipped.
+ *   label   int64 [n][hw] or NULL.  A label outside 0..C-1 (and every pixel when label is NULL) is unlabelled: it gets its maps and enters
+ *           none of the labelled sums, the rule of the losses above.
+ * Per pixel, in fp32:  p_t = softmax(x_t) with a true division (uniform logits give exactly float(1) / float(C));
+ *   pbar = (sum_t p_t) / float(T);  conf = max_k pbar_k;  yhat = argmax_k pbar_k, a tie -> the lowest index (ctl_argmax_c);
+ *   H  = -sum_k pbar_k log2(pbar_k + eps)                    predictive entropy, in BITS (upstream's form has eps = 1e-7; a term whose
+ *                                                            pbar_k + eps is 0 contributes 0, so eps = 0 is allowed)
+ *   E  = (1/T) sum_t -sum_k p_tk log2(p_tk + eps)            expected entropy
+ *   MI = H - E                                               mutual information; exactly 0 for T = 1
+ *   labelled pixels (label y):  nll = -ln pbar_y, formed as a log-sum-exp over the members of x_ty - max_k x_tk - ln sum_k exp(..), so a
+ *   class 160 logits below the maximum still has a finite nll (is_prob: from ln p_ty; +inf where every member gives 0);
+ *   brier = sum_k (pbar_k - [k == y])^2;  correct = [yhat == y].
+ * Reliability bins: B equal-width bins, 1 <= B <= CTL_UNCERT_MAX_BINS.  The bin of a labelled pixel is the number of edges
+ *   e_j = float(j) / float(B), j = 1..B-1, with conf > e_j, an fp32 comparison against the fp32 edge: every conf has exactly one bin.
+ * Outputs, each may be NULL:
+ *   entropy, mi, conf   fp32 [n][hw]        pred  uint8 [n][hw] (yhat)        mean_prob  fp32 NHWC [n][hw][C] (pbar)
+ *   stats   double [n][6] per slice: labelled pixels, correct pixels, sum H over ALL pixels, sum MI over all pixels, sum nll, sum brier
+ *   bins    int64 [n][B][3] per slice and bin: labelled pixels, correct pixels, sum of conf * 2^32.  The last is an exact integer (an fp32
+ *           conf >= 2^-8 is a multiple of 2^-31, and conf >= 1/16 up to rounding), so the sum does not depend on the order of the adds
+ *           and cannot overflow below 2^31 pixels per slice.
+ *   ECE = sum_b (n_b / N) |correct_b / n_b - (sum conf)_b / n_b| over the non-empty bins is finished on the host in fp64 from `bins`.
+ * Two launches: a streaming pass, grid (blocks of a slice, slice), that reads every pixel once, keeps a block's bins in LDS (integer LDS
+ * atomics) and writes one row of fp64 sums and one of bin sums per block to the workspace; and one finalize block per slice that adds
+ * the rows in a fixed order (skipped when stats and bins are both NULL).  No float atomics, no global atomics, nothing read back, no
+ * argument that changes from call to call: the same bits on every call and in a graph replay.  Rows of C == 4 in 16-byte aligned
+ * tensors move as 16 bytes; any other case takes the runtime-count kernel, same arithmetic in the same order, same bits.
+ * workspace: ctl_predictive_stats_ws_bytes(T, n, hw, C, B) bytes, 8-byte aligned, caller-owned.
+ * A NULL logits or workspace pointer, T, C or B out of range, non-positive sizes, more than 65535 slices, a tensor at or past 2 GiB and
+ * an eps that is not finite and >= 0 are refused with CTL_EINVAL before any launch; ctl_predictive_stats_ws_bytes returns 0 for them. */
+#define CTL_UNCERT_MAX_MEMBERS 64
+#define CTL_UNCERT_MAX_BINS 64
+size_t ctl_predictive_stats_ws_bytes(int32_t T, int32_t n, int64_t hw, int32_t C, int32_t B);
+int ctl_predictive_stats(const float* logits, const int64_t* label, int32_t T, int32_t n, int64_t hw, int32_t C, int32_t B, float eps,
+                         int32_t is_prob, float* entropy, float* mi, float* conf, uint8_t* pred, float* mean_prob, double* stats,
+                         int64_t* bins, void* workspace, ctl_stream stream);
+
 /* ------------------------------------------------------------------------------------------------ training augmentation
  * The per-slice host chain of medseg/dataset_loader/transform.py:46-86 (flip, contrast / brightness, random affine, choice rotation,
  * elastic deformation, centre crop) for a whole batch that is already on the device: image float [n,1,Hp,Wp] and label int64 [n,Hp,Wp]

@@ -31,6 +31,7 @@ CONV_DTYPE = np.dtype([
 DT_BF16, DT_X16, DT_Y16, DT_RES16, DT_X3 = 1, 2, 4, 8, 16
 PACK_X3 = 16                         # or-ed into the mode word of a pack record (CTL_PACK_X3)
 LOSS_WCE, LOSS_FOCAL, LOSS_DICE, LOSS_FG_DICE = 0, 1, 2, 3      # CTL_LOSS_* kinds of ctl_seg_loss_fwd / ctl_seg_loss_bwd
+TTA_LOGIT, TTA_PROB, TTA_MAX_VIEWS = 0, 1, 8                    # CTL_TTA_* of ctl_tta_merge
 OP_DTYPE = np.dtype([("kind", "<i4"), ("i", "<i4", (27,)), ("f", "<f4", (4,)), ("slot", "<i4", (OP_MAX_T,)),
                      ("off", "<i8", (OP_MAX_T,)), ("l", "<i8", (4,))], align=True)
 
@@ -220,6 +221,8 @@ def _signatures() -> dict:
         "ctl_cc_keep_largest": (int_, [p] + [i32] * 6 + [p, p, p, sz, p]),
         "ctl_predictive_stats_ws_bytes": (sz, [i32, i32, i64, i32, i32]),
         "ctl_predictive_stats": (int_, [p, p, i32, i32, i64, i32, i32, f32, i32] + [p] * 9),
+        "ctl_tta_views": (int_, [p, i32, i32, i32, i32, p, i32, p, p]),
+        "ctl_tta_merge": (int_, [p] + [i32] * 5 + [p, i32, p, p, p, p]),
         "ctl_aug_ws_bytes": (sz, [i32, i32, i32]),
         "ctl_aug_warp_ws_bytes": (sz, [i32] * 5),
         "ctl_aug_field": (int_, [p] * 4 + [i32, i32, i32, p, p, sz, p]),

@@ -347,6 +347,66 @@ def predictive_stats(logits: torch.Tensor, label: Optional[torch.Tensor] = None,
     return PredictiveStats(stats=stats, bins=bins, **outs)
 
 
+# ---------------------------------------------------------------------------------------------- test-time augmentation
+TtaMerge = namedtuple("TtaMerge", "aligned merged pred")      # outputs that were not asked for are None
+TTA_MODES = {"logit": _ffi.TTA_LOGIT, "prob": _ffi.TTA_PROB}
+
+
+def _tta_codes(views, h: int, w: int):
+    """(codes, the int32 host array ctl_tta_* reads) of a view set for an h x w plane (tta.parse_views: ValueError)"""
+    from .tta import parse_views
+    codes = parse_views(views, (h, w))
+    return codes, (C.c_int32 * len(codes))(*codes)
+
+
+def tta_views(image: torch.Tensor, views) -> torch.Tensor:
+    """The D4 views of a device batch (include/ctl_hip.h "test-time augmentation"; the numpy statement is tta.views_host).  image: fp32
+    [n, c, H, W], c <= 4; views: "flips", "d4" or a tuple of distinct codes 0..7 (bit 0 transpose, bit 1 flip H, bit 2 flip W, in that
+    order) -> fp32 [T * n, c, H, W] (channels_last), member-major: rows t * n .. t * n + n - 1 are view views[t] of every slice.  A
+    transposing code needs H == W (ValueError), so every member has the input's extent.  One launch, no readback."""
+    who = "tta_views"
+    require_gpu(image)
+    _arg(image, torch.float32, (None, None, None, None), who, "image")
+    n, c, h, w = (int(v) for v in image.shape)
+    codes, arr = _tta_codes(views, h, w)
+    x = as_nhwc(image)
+    out = empty_nhwc(len(codes) * n, c, h, w, image.device)
+    call("ctl_tta_views", ptr(x), n, h, w, c, arr, len(codes), ptr(out), stream_ptr())
+    return out
+
+
+def tta_merge(logits: torch.Tensor, views, hw, mode: str = "prob", want=("merged",)) -> TtaMerge:
+    """The network's logits on the views of tta_views, back on the native grid (the numpy statement is tta.merge_host).  logits: fp32
+    [T * n, C, H, W], member-major, C <= 16; views as in tta_views; hw: the native (H, W).  want: any of
+      'aligned'  fp32 [T * n, C, H, W] (channels_last): every member on the native grid, what predictive_stats(members=T) reads;
+      'merged'   fp32 [n, C, H, W] (channels_last): mode "logit" -> the fp32 mean of the members' logits, added in member order;
+                 mode "prob" -> the mean of the members' softmax, the arithmetic of predictive_stats' mean_prob;
+      'pred'     uint8 [n, H, W]: the arg-max of merged, first maximum.
+    -> TtaMerge(aligned, merged, pred), None for what was not asked for.  One launch, no readback, the same bits on every call."""
+    who = "tta_merge"
+    want = (want,) if isinstance(want, str) else tuple(want)
+    unknown = [m for m in want if m not in TtaMerge._fields]
+    if unknown or not want:
+        raise ValueError(f"{who}: want {want!r}: at least one of {', '.join(TtaMerge._fields)}")
+    if mode not in TTA_MODES:
+        raise ValueError(f"{who}: mode {mode!r}, one of {sorted(TTA_MODES)}")
+    require_gpu(logits)
+    h, w = (int(v) for v in hw)
+    _arg(logits, torch.float32, (None, None, h, w), who, "logits")
+    tn, c = int(logits.shape[0]), int(logits.shape[1])
+    codes, arr = _tta_codes(views, h, w)
+    t = len(codes)
+    if tn % t:
+        raise ValueError(f"{who}: {tn} logit slices do not divide into {t} views")
+    n, dev = tn // t, logits.device
+    x = as_nhwc(logits)
+    outs = {"aligned": empty_nhwc(tn, c, h, w, dev) if "aligned" in want else None,
+            "merged": empty_nhwc(n, c, h, w, dev) if "merged" in want else None,
+            "pred": torch.empty((n, h, w), dtype=torch.uint8, device=dev) if "pred" in want else None}
+    call("ctl_tta_merge", ptr(x), t, n, h, w, c, arr, TTA_MODES[mode], ptr(outs["aligned"]), ptr(outs["merged"]), ptr(outs["pred"]), stream_ptr())
+    return TtaMerge(**outs)
+
+
 # ---------------------------------------------------------------------------------------------- latent masking
 def latent_score(grad: torch.Tensor, mode: int) -> torch.Tensor:
     """mode 0: [N,C] signed mean over H*W; mode 1: [N,H*W] signed mean over C (model_util.py:224-225 / 285-286)."""

@@ -12,13 +12,16 @@ With native_grid=True (a project addition, off by default) the logits are put ba
 (prepare.prepare_patient(want_geometry=True)).
 With 'ECE' / 'NLL' / 'Brier' / 'Entropy' in metrics_list (project additions, metrics.runningMySegmentationScore) every chunk's logits go through
 ops.predictive_stats while they are on the device and only its small per-slice tables are kept; uncertainty_maps=True adds the 'entropy' and
-'conf' maps of the volume to the patient's result."""
+'conf' maps of the volume to the patient's result.
+With tta="flips" / "d4" / a tuple of view codes (a project addition, off by default: tta.py) every chunk is predicted as T flipped / rotated
+views in one pass and the members are merged on the device (ops.tta_views, ops.tta_merge: two more launches per chunk); the merged scores
+take the place of the logits everywhere and the calibration columns become those of the T-member ensemble."""
 import os
 
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, tta as tta_mod
 from .metrics import runningMySegmentationScore
 
 
@@ -40,7 +43,8 @@ def max_slices_per_pass(h: int, w: int, widest_channels: int = 16, device=None) 
 COALESCE_CHUNKS = True      # run consecutive <= `maximum_batch_size`-slice chunks of a volume as one pass (see predict_volume)
 
 
-def predict_volume(segmentation_model, image_d: torch.Tensor, n_iter=None, chunk=None, out: torch.Tensor = None, coalesce=None) -> torch.Tensor:
+def predict_volume(segmentation_model, image_d: torch.Tensor, n_iter=None, chunk=None, out: torch.Tensor = None, coalesce=None, tta=None,
+                   tta_mode="prob") -> torch.Tensor:
     """uint8 label volume [n,H,W] of a device volume [n,1,H,W]: `predict` (model.py:375-394) + arg-max on the device.
     chunk = 10 is the reference's loop (test_basic_segmentation_solver.py:85-114): a GPU-MEMORY workaround, not part of the computation --
     `predict` puts every network in eval mode (running BatchNorm statistics), so slices are independent and batching changes nothing but
@@ -48,9 +52,14 @@ def predict_volume(segmentation_model, image_d: torch.Tensor, n_iter=None, chunk
     With `coalesce` (default: tester.COALESCE_CHUNKS = True) consecutive chunks therefore run as ONE pass, as many as the 2 GiB
     addressing limit of a tensor AND half of the currently free device memory allow (max_slices_per_pass); coalesce=False is the
     reference's literal loop.  chunk = None:
-    the whole volume per pass either way."""
+    the whole volume per pass either way.
+    tta (None: today's path, no extra launch): a view set of tta.parse_views; a chunk then holds limit // T slices, so that the T * n pass
+    respects max_slices_per_pass, and the labels are the arg-max of the merged scores (tta.predict_tta, mode `tta_mode`)."""
     n, _, h, w = image_d.shape
     limit = max_slices_per_pass(h, w, device=image_d.device)
+    codes = None if tta is None else tta_mod.parse_views(tta, (h, w))
+    if codes is not None:
+        limit = max(1, limit // len(codes))
     coalesce = COALESCE_CHUNKS if coalesce is None else bool(coalesce)
     if chunk is not None and int(chunk) < 1:
         raise ValueError("chunk must be positive")
@@ -58,7 +67,10 @@ def predict_volume(segmentation_model, image_d: torch.Tensor, n_iter=None, chunk
     pred = out if out is not None else torch.empty((n, h, w), dtype=torch.uint8, device=image_d.device)
     for lo in range(0, n, chunk):
         hi = min(n, lo + chunk)
-        pred[lo:hi] = ops.argmax_c(segmentation_model.predict(input=image_d[lo:hi], softmax=False, n_iter=n_iter))
+        if codes is None:
+            pred[lo:hi] = ops.argmax_c(segmentation_model.predict(input=image_d[lo:hi], softmax=False, n_iter=n_iter))
+        else:
+            pred[lo:hi] = tta_mod.predict_tta(segmentation_model, image_d[lo:hi], codes, mode=tta_mode, n_iter=n_iter, want=("pred",)).pred
     return pred
 
 
@@ -72,7 +84,7 @@ class TestSegmentationNetwork(object):
     def __init__(self, test_dataset, crop_size, segmentation_model, use_gpu=True, save_path="", summary_report_file_name="result.csv",
                  detailed_report_file_name="details.csv", patient_wise=True, metrics_list=("Dice", "HD"), foreground_only=False,
                  save_soft_prediction=False, keep_results=True, post_process=None, native_grid=False, restore_mode="logit",
-                 uncertainty_maps=False):
+                 uncertainty_maps=False, tta=None, tta_mode="prob"):
         if not use_gpu:
             raise ValueError("this build has no CPU path")
         if post_process not in POST_PROCESS:
@@ -80,6 +92,10 @@ class TestSegmentationNetwork(object):
         if restore_mode not in ops.RESTORE_MODES:
             raise ValueError("restore_mode {!r}: one of {}".format(restore_mode, sorted(ops.RESTORE_MODES)))
         self.post_process, self.native_grid, self.restore_mode = post_process, bool(native_grid), restore_mode
+        self.tta = None if tta is None else tta_mod.parse_views(tta)      # (duplicate or unknown codes: ValueError here)
+        if tta_mode not in ops.TTA_MODES:
+            raise ValueError("tta_mode {!r}: one of {}".format(tta_mode, sorted(ops.TTA_MODES)))
+        self.tta_mode = tta_mode
         self.calibration = any(m in runningMySegmentationScore.PATIENT_LEVEL for m in metrics_list)
         self.uncertainty_maps = bool(uncertainty_maps)
         if self.native_grid and (self.calibration or self.uncertainty_maps):
@@ -125,12 +141,22 @@ class TestSegmentationNetwork(object):
         their meaning (window grid); 'native_pred' and 'native_label' are added.
         Calibration columns: one ops.predictive_stats call per chunk on the logits `predict` just returned (2 launches); the per-slice
         tables join the metric's one readback, no logits are kept for it.  uncertainty_maps: the same call also writes the chunk's
-        'entropy' and 'conf' maps, which are added to the result (the only keys when nothing else is kept)."""
+        'entropy' and 'conf' maps, which are added to the result (the only keys when nothing else is kept).
+        tta (TestSegmentationNetwork(tta=, tta_mode=)): a chunk holds limit // T slices and is predicted as its T views in one pass
+        (tta.predict_tta).  The merged scores take the place of the logits for the arg-max, for restore_scores and for 'soft_pred': with
+        tta_mode="prob" (the default) 'soft_pred' holds the mean PROBABILITIES of the members, not logits, and
+        restore_scores(mode="logit") is then the bilinear interpolation of those probabilities; with "logit" it holds the mean logits.
+        The calibration columns and uncertainty_maps read the members put back on the native grid (predictive_stats(members=T)) and
+        are those of the ensemble's mean probability in either mode; uncertainty_maps then also returns 'mi', the mutual information.
+        native_grid works with tta as long as no calibration column is asked for (the refusal above stands)."""
         dev = torch.device("cuda", torch.cuda.current_device())
         image = data_tensor_pack["image"]
         if image.dim() == 5:                              # DataLoader(batch_size=1) adds a leading axis upstream
             image = image[0]
         limit = max_slices_per_pass(image.shape[-2], image.shape[-1], device=dev)
+        codes = None if self.tta is None else tta_mod.parse_views(self.tta, image.shape[-2:])      # a transposing view: square windows only
+        if codes is not None:
+            limit = max(1, limit // len(codes))
         assert maximum_batch_size is None or int(maximum_batch_size) > 0
         if maximum_batch_size is None or (COALESCE_CHUNKS if coalesce is None else coalesce):
             maximum_batch_size = min(int(image.shape[0]), limit)
@@ -154,18 +180,29 @@ class TestSegmentationNetwork(object):
         pred_d = torch.empty((total, image_d.shape[-2], image_d.shape[-1]), dtype=torch.uint8, device=dev)
         soft = [] if (self.save_soft_prediction or self.keep_results) else None
         uncert = [] if (self.calibration or self.uncertainty_maps) else None
+        want_pred = native_d is None or soft is not None          # native grid: the window arg-max is only a kept result
         for lo in range(0, total, maximum_batch_size):
             hi = min(total, lo + maximum_batch_size)
-            logit = self.segmentation_model.predict(input=image_d[lo:hi], softmax=False)
+            if codes is None:
+                logit = members = self.segmentation_model.predict(input=image_d[lo:hi], softmax=False)
+                if want_pred:
+                    pred_d[lo:hi] = ops.argmax_c(logit)
+            else:                                                 # `logit`: the merged scores; `members`: the T aligned members
+                want = (("merged",) if (native_d is not None or soft is not None) else ()) + (("pred",) if want_pred else ()) + \
+                       (("aligned",) if uncert is not None else ())
+                merge = tta_mod.predict_tta(self.segmentation_model, image_d[lo:hi], codes, mode=self.tta_mode, want=want)
+                logit, members = merge.merged, merge.aligned
+                if want_pred:
+                    pred_d[lo:hi] = merge.pred
             if native_d is not None:
                 ops.restore_scores(logit, geo, mode=self.restore_mode, out=native_d[lo:hi])
-            if native_d is None or soft is not None:      # native grid: the window arg-max is only a kept result
-                pred_d[lo:hi] = ops.argmax_c(logit)
             if soft is not None:
                 soft.append(logit)
             if uncert is not None:
-                uncert.append(ops.predictive_stats(logit, label_d[lo:hi], n_bins=self.segmentation_metric.calibration_bins,
-                                                   want=("entropy", "conf") if self.uncertainty_maps else ()))
+                maps = ("entropy", "conf") + (("mi",) if codes is not None else ())
+                uncert.append(ops.predictive_stats(members, label_d[lo:hi], members=1 if codes is None else len(codes),
+                                                   n_bins=self.segmentation_metric.calibration_bins,
+                                                   want=maps if self.uncertainty_maps else ()))
         scored_d, scored_label_d = (pred_d, label_d) if native_d is None else (native_d, native_label_d)
         if self.post_process is not None:                 # largest component of every class (post_process.py:5-22), in place on the device
             per_slice = POST_PROCESS[self.post_process]
@@ -187,6 +224,8 @@ class TestSegmentationNetwork(object):
             result = {} if result is None else result
             result["entropy"] = torch.cat([u.entropy for u in uncert], 0).cpu().numpy()
             result["conf"] = torch.cat([u.conf for u in uncert], 0).cpu().numpy()
+            if self.tta is not None:
+                result["mi"] = torch.cat([u.mi for u in uncert], 0).cpu().numpy()
         if result is not None and total == 1:
             result = {k: v[0] for k, v in result.items()}
         if self.save_soft_prediction and self.save_path:

@@ -8,6 +8,7 @@ holds what sits around it:
                                               kernel is tested against, called by nothing on the device path
   calibration_from_tables                     ECE / NLL / Brier / Entropy / accuracy from the two small tables, in float64
   cooperative_members                         the FTN / STN two-member ensemble of a cooperative model, ready for members=2
+  tta_members                                 the T-member ensemble over D4 views of the input (tta.py), ready for members=T
 """
 from collections import namedtuple
 
@@ -171,3 +172,12 @@ def cooperative_members(solver, image):
         _, first = solver.fast_predict(image)
         refined, _ = solver.slow_refinement(first, n_steps=1)
     return ops.as_nhwc(torch.cat([first.float(), refined.float()], dim=0))
+
+
+# ---------------------------------------------------------------------------------------------- the test-time augmentation ensemble
+def tta_members(solver, image, views, n_iter=None):
+    """The T-member ensemble of a model over the D4 views `views` (tta.parse_views) of a device batch `image` [n,1,H,W]: every view's
+    logits put back on the native grid, stacked member-major -> [T * n, C, H, W] (channels_last), for ops.predictive_stats(members=T).
+    Two launches around one `predict` over the T * n stack (tta.predict_tta)."""
+    from . import tta
+    return tta.predict_tta(solver, image, views, n_iter=n_iter, want=("aligned",)).aligned

@@ -536,6 +536,39 @@ int ctl_predictive_stats(const float* logits, const int64_t* label, int32_t T, i
                          int32_t is_prob, float* entropy, float* mi, float* conf, uint8_t* pred, float* mean_prob, double* stats,
                          int64_t* bins, void* workspace, ctl_stream stream);
 
+/* ------------------------------------------------------------------------------------------------ test-time augmentation
+ * Predict several flipped / rotated views of a batch of slices, put the logits back on the native grid and average them (ctl_tta.hip).  A
+ * project addition: upstream has no counterpart.
+ * A view is an element of the dihedral group of the square, coded v = 0..7: bit 0 = transpose, bit 1 = flip along H, bit 2 = flip
+ * along W, applied in that order.  For a plane X [H][W]: A = X^T if bit 0 else X, (Ho, Wo) = the shape of A, and
+ *   view_v(X)[y][x] = A[bit1 ? Ho-1-y : y][bit2 ? Wo-1-x : x].
+ * Native pixel (i, j) is found in view v at (y, x): (a, b) = bit0 ? (j, i) : (i, j), y = bit1 ? Ho-1-a : a, x = bit2 ? Wo-1-b : b.
+ * codes: T distinct view codes (HOST array, read during the call: launch constants), 1 <= T <= CTL_TTA_MAX_VIEWS; the identity need
+ * not be among them.  A code with bit 0 needs h == w.
+ * ctl_tta_views: x fp32 NHWC [n][h][w][c], 1 <= c <= 4 -> out fp32 [T][n][Ho][Wo][c], member-major: member t is view codes[t] of every
+ *   slice.  A pure permutation.
+ * ctl_tta_merge: logits fp32 NHWC [T][n][Ho][Wo][c], the network's output on those views, 1 <= c <= 16; (h, w) is the NATIVE grid.
+ *   Outputs, each may be NULL, at least one is not:
+ *   aligned  fp32 [T][n][h][w][c]   every member on the native grid: a pure permutation, what ctl_predictive_stats reads with T members
+ *   merged   fp32 [n][h][w][c]      mode CTL_TTA_LOGIT: (((x_0 + x_1) + ..) + x_T-1) / float(T) in fp32, in member order, plain adds and one
+ *                                   true division;  mode CTL_TTA_PROB: pbar of "predictive uncertainty" above with the same arithmetic
+ *                                   in the same order (per member: subtract the maximum, expf, sum, divide; T-1 adds; divide by float(T))
+ *   pred     uint8 [n][h][w]        arg-max of merged, a tie -> the lowest index (ctl_argmax_c)
+ *   An output that is not asked for changes no bit of the others.
+ * One launch each over square pixel tiles (32 x 32 up to 4 channels, else 16 x 16); a pixel is c contiguous floats and moves as 16
+ * bytes when c == 4 and every tensor is 16-byte aligned (the same bits either way).  A view without a transpose is read along its rows,
+ * forwards or backwards; a transposed one goes through a padded LDS tile so that neither side of the copy is strided by a row per lane.
+ * No workspace, no atomics, nothing read back, no argument that changes from call to call: the same bits on every call and in a graph
+ * replay.  Refused with CTL_EINVAL before any launch: T outside 1..8, a code outside 0..7, a duplicate code, c out of range, non-positive
+ * sizes, a transposing code with h != w, a tensor at or past 2 GiB, a NULL x / out / logits / codes, all three outputs NULL, an unknown
+ * mode. */
+#define CTL_TTA_MAX_VIEWS 8
+#define CTL_TTA_LOGIT 0
+#define CTL_TTA_PROB 1
+int ctl_tta_views(const float* x, int32_t n, int32_t h, int32_t w, int32_t c, const int32_t* codes, int32_t T, float* out, ctl_stream stream);
+int ctl_tta_merge(const float* logits, int32_t T, int32_t n, int32_t h, int32_t w, int32_t c, const int32_t* codes, int32_t mode,
+                  float* aligned, float* merged, uint8_t* pred, ctl_stream stream);
+
 /* ------------------------------------------------------------------------------------------------ training augmentation
  * The per-slice host chain of medseg/dataset_loader/transform.py:46-86 (flip, contrast / brightness, random affine, choice rotation,
  * elastic deformation, centre crop) for a whole batch that is already on the device: image float [n,1,Hp,Wp] and label int64 [n,Hp,Wp]

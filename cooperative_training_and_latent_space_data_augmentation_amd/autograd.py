@@ -184,6 +184,56 @@ class _DiceSegLoss(torch.autograd.Function):
         return ops.seg_loss_bwd(logit, label, ctx.kind, g.float().contiguous(), ws), None, None
 
 
+class LabelFields:
+    """The class fields of ONE label map [B,H,W] in the training forms of ops.class_fields, each computed on first use and kept: the losses
+    of a step that compare different predictions with the same labels share them.  `event` orders a consumer on another stream behind
+    the launch that wrote a form (the two launch chains of solver.cooperative_step)."""
+
+    def __init__(self, label: torch.Tensor, n_class: int):
+        ops.require_gpu(label)
+        self.label, self.n_class = label if label.dtype == torch.uint8 else label.long().contiguous(), int(n_class)
+        self._forms = {}
+
+    def get(self, form: str) -> torch.Tensor:
+        cur = torch.cuda.current_stream()
+        if form not in self._forms:
+            f = ops.class_fields(self.label, self.n_class, form)
+            ev = torch.cuda.Event()
+            ev.record(cur)
+            self._forms[form] = (f, ev, cur)
+        f, ev, stream = self._forms[form]
+        if stream != cur:
+            cur.wait_event(ev)
+            f.record_stream(cur)
+        return f
+
+    def get_all(self, loss_type) -> None:
+        """Compute, on the current stream, every form the loss name or {name: weight} mapping `loss_type` reads."""
+        for name in (loss_type if isinstance(loss_type, dict) else (loss_type,)):
+            if name in ops.DIST_LOSS_FORM:
+                self.get(ops.DIST_LOSS_FORM[name])
+
+
+class _DistSegLoss(torch.autograd.Function):
+    """'boundary' / 'hausdorff dt' (losses.py): the label's field arrives as an input; 'hausdorff dt' thresholds the prediction and
+    transforms it here, once, and the backward treats that field as the constant the published loss makes it."""
+
+    @staticmethod
+    def forward(ctx, logit, label, kind, field):
+        logit = _nhwc(logit)
+        label = label.long().contiguous()
+        pred = ops.class_fields(ops.confident_label(logit), logit.shape[1], "squared") if kind == "hausdorff dt" else None
+        ctx.kind, ctx.two = kind, pred is not None
+        ctx.save_for_backward(*((logit, label, field) + ((pred,) if ctx.two else ())))
+        return ops.dist_loss_fwd(logit, label, kind, field, pred)
+
+    @staticmethod
+    def backward(ctx, g):
+        logit, label, field = ctx.saved_tensors[:3]
+        pred = ctx.saved_tensors[3] if ctx.two else None
+        return ops.dist_loss_bwd(logit, label, ctx.kind, g.float().contiguous(), field, pred), None, None, None
+
+
 class _ScaledMSE(torch.autograd.Function):
     """scale * mean((a-b)^2)"""
 
@@ -221,11 +271,22 @@ def cross_entropy_2D(logit, label):
     return _CrossEntropy2D.apply(logit, label)
 
 
-def segmentation_loss(logit, label, kind, class_weights=None, gamma=2.0):
-    """One of the fused segmentation losses of ops.LOSS_KINDS on logits [B,C,H,W] and a label map [B,H,W].  `class_weights`: a host
-    sequence of C numbers, used by 'weighted cross entropy' only ('weighted dice' ignores it, as upstream does); `gamma`: 'focal' only."""
+def segmentation_loss(logit, label, kind, class_weights=None, gamma=2.0, fields=None):
+    """One of the fused segmentation losses of ops.LOSS_KINDS / ops.DIST_LOSS_KINDS on logits [B,C,H,W] and a label map [B,H,W].
+    `class_weights`: a host sequence of C numbers, used by 'weighted cross entropy' only ('weighted dice' ignores it, as upstream does);
+    `gamma`: 'focal' only.  `fields` ('boundary', 'hausdorff dt'): the class fields of `label`, a LabelFields or the fp32 NHWC tensor of
+    the form the loss reads (ops.DIST_LOSS_FORM); computed here when absent."""
+    if kind in ops.DIST_LOSS_KINDS:
+        if logit.size(1) < 2:
+            raise ValueError(f"{kind!r} needs at least 2 classes")
+        ops.require_gpu(logit, label)
+        if fields is None:
+            fields = LabelFields(label, logit.size(1))
+        if isinstance(fields, LabelFields):
+            fields = fields.get(ops.DIST_LOSS_FORM[kind])
+        return _DistSegLoss.apply(logit, label, kind, fields)
     if kind not in ops.LOSS_KINDS:
-        raise NotImplementedError(f"segmentation loss {kind!r} (one of {', '.join(ops.LOSS_KINDS)})")
+        raise NotImplementedError(f"segmentation loss {kind!r} (one of {', '.join(tuple(ops.LOSS_KINDS) + tuple(ops.DIST_LOSS_KINDS))})")
     ops.require_gpu(logit, label)
     if ops.LOSS_KINDS[kind] in (ops._ffi.LOSS_DICE, ops._ffi.LOSS_FG_DICE):
         return _DiceSegLoss.apply(logit, label, kind)

@@ -1,5 +1,5 @@
 // Helpers shared by the feature kernels (ctl_elem, ctl_io, ctl_mask, ctl_aug, ctl_surface, ctl_cc, ctl_prep, ctl_restore, ctl_corrupt,
-// ctl_batch, ctl_loss); the conv / weight-gradient families and the plan compiler need none of this and include ctl_common.h alone.
+// ctl_batch, ctl_loss, ctl_dist); the conv / weight-gradient families and the plan compiler need none of this and include ctl_common.h alone.
 //   host    S_                       the launchers' stream argument as a hipStream_t
 //           ctl_align256             workspace sections start on 256 bytes
 //           ctl_blocks               1-D launch sizing: clamp(cdiv(items, threads), 1, cap)
@@ -8,6 +8,7 @@
 //   device  CTL_MIX_*, ctl_mix64     the counter-hash generator (splitmix64)
 //           ctl_block_minmax<T>      min / max (float) over a block of T threads, every thread gets both
 //           ctl_block_sum_double<W>  sum over a block of W waves, thread 0 gets it
+//           ctl_wave_prefix_max / ctl_wave_suffix_min   inclusive integer scans over the 64 lanes of a wave (row passes of the distance transforms)
 // (wave_sum_double, the wave step of the sums, is in ctl_common.h.)
 #pragma once
 #include "ctl_common.h"
@@ -66,4 +67,22 @@ template <int WAVES> __device__ __forceinline__ double ctl_block_sum_double(doub
     double r = 0.0;
     if (threadIdx.x == 0) for (int i = 0; i < WAVES; ++i) r += sm[i];
     return r;
+}
+
+// Inclusive scans over the 64 lanes of a wave: lane l gets max(v[0..l]) / min(v[l..63]).  Every lane of the wave must call them.
+__device__ __forceinline__ int ctl_wave_prefix_max(int v) {
+    const int lane = threadIdx.x & 63;
+    for (int d = 1; d < 64; d <<= 1) {
+        const int t = __shfl_up(v, d);
+        if (lane >= d) v = max(v, t);
+    }
+    return v;
+}
+__device__ __forceinline__ int ctl_wave_suffix_min(int v) {
+    const int lane = threadIdx.x & 63;
+    for (int d = 1; d < 64; d <<= 1) {
+        const int t = __shfl_down(v, d);
+        if (lane + d < 64) v = min(v, t);
+    }
+    return v;
 }

@@ -5,6 +5,9 @@
 // the same bits on every call.  Nothing is read back; no launch argument changes from step to step.
 //
 // A label outside 0..c-1 is no class: one-hot 0 for every k, weight 0.  Labels are only ever compared with a class index.
+//
+// The distance-map losses ('boundary', 'hausdorff dt'; no upstream counterpart) stream the same way with one or two fp32 NHWC field tensors
+// beside the logits (ctl_dist.hip writes them); ctl_confident_label is the thresholding of a prediction whose fields 'hausdorff dt' needs.
 #include <cmath>
 #include "ctl_device.h"
 
@@ -323,5 +326,157 @@ extern "C" int ctl_seg_loss_bwd(int32_t kind, const float* logit, const int64_t*
     if (ctl_vec4(c, logit, dlogit)) seg_loss_bwd_kernel<4><<<grid, dim3(EB), 0, S_>>>(logit, label, gout, coef, hw, c, kind, w, gamma, pixels_f, dlogit);
     else seg_loss_bwd_kernel<0><<<grid, dim3(EB), 0, S_>>>(logit, label, gout, coef, hw, c, kind, w, gamma, pixels_f, dlogit);
     CTL_LAUNCH_CHECK("seg_loss_bwd");
+    return CTL_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ distance-map losses
+// p = softmax(x) as the kernels above form it (exp(x - max) * (1 / sum), fp32); everything behind it is fp64.  Classes 1..c-1, div = b (c-1) hw.
+//   boundary      g_k = a_k / div                          (a = the signed map of the label),            term = sum_k p_k a_k
+//   hausdorff dt  g_k = 2 (p_k - t_k) (a_k + b_k) / div    (a, b = squared fields of label / prediction), term = sum_k (p_k - t_k)^2 (a_k + b_k)
+// and dL/dx_j = p_j (g_j S - sum_k p_k g_k) with S the sum of the rounded p_k, as the Dice backward has it.
+template <int CT>
+__device__ __forceinline__ void dl_fields(int kind, const float* __restrict__ fa, const float* __restrict__ fb, int64_t i, int c, double* d) {
+    constexpr int NC = CT ? CT : MAXC;
+    float a[NC], b[NC];
+    lrow_load<CT>(fa, i, c, a);
+    if (kind == CTL_DLOSS_HAUSDORFF_DT) lrow_load<CT>(fb, i, c, b);
+#pragma unroll
+    for (int k = 0; k < NC; ++k) if (k < c) d[k] = k == 0 ? 0.0 : (kind == CTL_DLOSS_HAUSDORFF_DT ? (double)a[k] + (double)b[k] : (double)a[k]);
+}
+template <int CT>
+__global__ __launch_bounds__(EB) void dist_loss_partial_kernel(const float* __restrict__ logit, const int64_t* __restrict__ label,
+                                                                const float* __restrict__ fa, const float* __restrict__ fb, int64_t pixels,
+                                                                int c_rt, int kind, double* __restrict__ partial) {
+#pragma clang fp contract(off)
+    constexpr int NC = CT ? CT : MAXC;
+    __shared__ double sm[EB / 64];
+    const int c = CT ? CT : c_rt;
+    const int64_t stride = (int64_t)gridDim.x * EB;
+    double acc = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x; i < pixels; i += stride) {
+        float v[NC];
+        double d[NC];
+        lrow_load<CT>(logit, i, c, v);
+        float s;
+        lrow_exp<CT>(v, c, s);
+        const float r = 1.f / s;
+        dl_fields<CT>(kind, fa, fb, i, c, d);
+        const int64_t l = kind == CTL_DLOSS_HAUSDORFF_DT ? label[i] : -1;
+#pragma unroll
+        for (int k = 1; k < NC; ++k) if (k < c) {
+            const double p = (double)(v[k] * r);
+            if (kind == CTL_DLOSS_HAUSDORFF_DT) {
+                const double e = p - (l == (int64_t)k ? 1.0 : 0.0);
+                acc += e * e * d[k];
+            } else {
+                acc += p * d[k];
+            }
+        }
+    }
+    acc = ctl_block_sum_double<EB / 64>(acc, sm);
+    if (threadIdx.x == 0) partial[blockIdx.x] = acc;
+}
+template <int CT>
+__global__ __launch_bounds__(EB) void dist_loss_bwd_kernel(const float* __restrict__ logit, const int64_t* __restrict__ label,
+                                                            const float* __restrict__ fa, const float* __restrict__ fb,
+                                                            const float* __restrict__ gout, int64_t pixels, int c_rt, int kind, double inv_div,
+                                                            float* __restrict__ dlogit) {
+#pragma clang fp contract(off)
+    constexpr int NC = CT ? CT : MAXC;
+    const int c = CT ? CT : c_rt;
+    const double go = (double)gout[0];
+    const int64_t stride = (int64_t)gridDim.x * EB;
+    for (int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x; i < pixels; i += stride) {
+        float v[NC];
+        double d[NC], g[NC];
+        lrow_load<CT>(logit, i, c, v);
+        float s;
+        lrow_exp<CT>(v, c, s);
+        const float r = 1.f / s;
+        dl_fields<CT>(kind, fa, fb, i, c, d);
+        const int64_t l = kind == CTL_DLOSS_HAUSDORFF_DT ? label[i] : -1;
+        double dot = 0.0, S = 0.0;
+#pragma unroll
+        for (int k = 0; k < NC; ++k) if (k < c) {
+            v[k] = v[k] * r;
+            const double p = (double)v[k];
+            g[k] = kind == CTL_DLOSS_HAUSDORFF_DT ? 2.0 * (p - (l == (int64_t)k ? 1.0 : 0.0)) * d[k] * inv_div : d[k] * inv_div;
+            dot += p * g[k];
+            S += p;
+        }
+#pragma unroll
+        for (int k = 0; k < NC; ++k) if (k < c) v[k] = (float)(go * ((double)v[k] * (g[k] * S - dot)));
+        lrow_store<CT>(dlogit, i, c, v);
+    }
+}
+// first class whose softmax probability exceeds 1/2 (at most one can), else 255
+template <int CT>
+__global__ __launch_bounds__(EB) void confident_label_kernel(const float* __restrict__ logit, int64_t pixels, int c_rt, uint8_t* __restrict__ out) {
+#pragma clang fp contract(off)
+    constexpr int NC = CT ? CT : MAXC;
+    const int c = CT ? CT : c_rt;
+    const int64_t stride = (int64_t)gridDim.x * EB;
+    for (int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x; i < pixels; i += stride) {
+        float v[NC];
+        lrow_load<CT>(logit, i, c, v);
+        float s;
+        lrow_exp<CT>(v, c, s);
+        const float r = 1.f / s;
+        int q = 255;
+#pragma unroll
+        for (int k = NC - 1; k >= 0; --k) if (k < c) q = v[k] * r > 0.5f ? k : q;
+        out[i] = (uint8_t)q;
+    }
+}
+
+static int dist_loss_check(const char* who, int kind, int64_t b, int64_t hw, int c) {
+    CTL_REQUIRE(kind == CTL_DLOSS_BOUNDARY || kind == CTL_DLOSS_HAUSDORFF_DT, "%s: unknown loss kind %d (0: boundary, 1: hausdorff dt)", who, kind);
+    CTL_REQUIRE(b > 0 && hw > 0, "%s: sizes must be positive (batch %lld, pixels per sample %lld)", who, (long long)b, (long long)hw);
+    CTL_REQUIRE(c >= 2 && c <= MAXC, "%s: %d classes (2 .. %d: the loss runs over the classes 1 .. c-1)", who, c, MAXC);
+    const int64_t row_bytes = c * 4 > 8 ? c * 4 : 8;
+    CTL_REQUIRE(hw < ((int64_t)1 << 31) && b * hw < ((int64_t)1 << 31) / row_bytes,
+                "%s: %lld x %lld pixels of %d classes reach the 2 GiB tensor limit", who, (long long)b, (long long)hw, c);
+    return CTL_OK;
+}
+extern "C" size_t ctl_dist_loss_ws_doubles(int32_t kind, int32_t b, int64_t hw, int32_t c) {
+    return dist_loss_check("dist_loss_ws_doubles", kind, b, hw, c) == CTL_OK ? CTL_RED_BLOCKS : 0;
+}
+extern "C" int ctl_dist_loss_fwd(int32_t kind, const float* logit, const int64_t* label, const float* field_a, const float* field_b, int32_t b,
+                                 int64_t hw, int32_t c, double* ws, float* loss, ctl_stream stream) {
+    CTL_REQUIRE(logit && field_a && ws && loss, "dist_loss_fwd: null pointer");
+    if (int rc = dist_loss_check("dist_loss_fwd", kind, b, hw, c)) return rc;
+    CTL_REQUIRE(kind != CTL_DLOSS_HAUSDORFF_DT || (label && field_b), "dist_loss_fwd: null pointer (hausdorff dt reads the label map and two fields)");
+    const int64_t pixels = (int64_t)b * hw;
+    if (ctl_vec4(c, logit, field_a, field_b))
+        dist_loss_partial_kernel<4><<<dim3(CTL_RED_BLOCKS), dim3(EB), 0, S_>>>(logit, label, field_a, field_b, pixels, c, kind, ws);
+    else dist_loss_partial_kernel<0><<<dim3(CTL_RED_BLOCKS), dim3(EB), 0, S_>>>(logit, label, field_a, field_b, pixels, c, kind, ws);
+    seg_pw_finalize_kernel<<<dim3(1), dim3(EB), 0, S_>>>(ws, CTL_RED_BLOCKS, 1.0 / ((double)pixels * (double)(c - 1)), loss);
+    ctl_count_launches(1);      // partial + finalize
+    CTL_LAUNCH_CHECK("dist_loss_fwd");
+    return CTL_OK;
+}
+extern "C" int ctl_dist_loss_bwd(int32_t kind, const float* logit, const int64_t* label, const float* field_a, const float* field_b,
+                                 const float* gout, int32_t b, int64_t hw, int32_t c, float* dlogit, ctl_stream stream) {
+    CTL_REQUIRE(logit && field_a && gout && dlogit, "dist_loss_bwd: null pointer");
+    if (int rc = dist_loss_check("dist_loss_bwd", kind, b, hw, c)) return rc;
+    CTL_REQUIRE(kind != CTL_DLOSS_HAUSDORFF_DT || (label && field_b), "dist_loss_bwd: null pointer (hausdorff dt reads the label map and two fields)");
+    const int64_t pixels = (int64_t)b * hw;
+    const double inv_div = 1.0 / ((double)pixels * (double)(c - 1));
+    const dim3 grid(ctl_blocks(pixels, EB, LOSS_MAX_STREAM_BLOCKS));
+    if (ctl_vec4(c, logit, field_a, field_b) && ((uintptr_t)dlogit & 15) == 0)
+        dist_loss_bwd_kernel<4><<<grid, dim3(EB), 0, S_>>>(logit, label, field_a, field_b, gout, pixels, c, kind, inv_div, dlogit);
+    else dist_loss_bwd_kernel<0><<<grid, dim3(EB), 0, S_>>>(logit, label, field_a, field_b, gout, pixels, c, kind, inv_div, dlogit);
+    CTL_LAUNCH_CHECK("dist_loss_bwd");
+    return CTL_OK;
+}
+extern "C" int ctl_confident_label(const float* logit, uint8_t* out, int64_t pixels, int32_t c, ctl_stream stream) {
+    CTL_REQUIRE(logit && out, "confident_label: null pointer");
+    CTL_REQUIRE(pixels > 0 && pixels < ((int64_t)1 << 31) / (c > 0 ? c * 4 : 4), "confident_label: %lld pixels (positive, below the 2 GiB tensor limit)",
+                (long long)pixels);
+    CTL_REQUIRE(c >= 1 && c <= MAXC, "confident_label: %d classes (1 .. %d)", c, MAXC);
+    const dim3 grid(ctl_blocks(pixels, EB, LOSS_MAX_STREAM_BLOCKS));
+    if (ctl_vec4(c, logit)) confident_label_kernel<4><<<grid, dim3(EB), 0, S_>>>(logit, pixels, c, out);
+    else confident_label_kernel<0><<<grid, dim3(EB), 0, S_>>>(logit, pixels, c, out);
+    CTL_LAUNCH_CHECK("confident_label");
     return CTL_OK;
 }

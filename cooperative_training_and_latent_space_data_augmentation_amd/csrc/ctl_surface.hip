@@ -96,11 +96,7 @@ __global__ __launch_bounds__(SF_THREADS) void sf_row_kernel(const uint8_t* __res
     for (int x0 = 0; x0 < W; x0 += 64) {
         const int x = x0 + lane;
         int v = (x < W && crow[x] == c) ? x : -far;
-        for (int d = 1; d < 64; d <<= 1) {
-            const int t = __shfl_up(v, d);
-            if (lane >= d) v = max(v, t);
-        }
-        v = max(v, carry);
+        v = max(ctl_wave_prefix_max(v), carry);
         carry = __shfl(v, 63);
         if (x < W) grow[x] = v >= 0 ? (uint16_t)(x - v) : (uint16_t)SF_NONE;
     }
@@ -108,11 +104,7 @@ __global__ __launch_bounds__(SF_THREADS) void sf_row_kernel(const uint8_t* __res
     for (int x0 = ((W - 1) / 64) * 64; x0 >= 0; x0 -= 64) {
         const int x = x0 + lane;
         int v = (x < W && crow[x] == c) ? x : far;
-        for (int d = 1; d < 64; d <<= 1) {
-            const int t = __shfl_down(v, d);
-            if (lane + d < 64) v = min(v, t);
-        }
-        v = min(v, carry);
+        v = min(ctl_wave_suffix_min(v), carry);
         carry = __shfl(v, 0);
         if (x < W) {                                                           // the same lane wrote grow[x] above
             const unsigned left = grow[x];

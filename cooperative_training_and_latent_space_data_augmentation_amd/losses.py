@@ -15,6 +15,17 @@ Notation: logits x[B,C,H,W], label map y[B,H,W], p = softmax(x, dim=C), t = oneh
                             the gradient is (1 - p_y)^gamma (p_k - t_k) / M, which is NOT the derivative of the value.
   'contour_smooth'          refused (upstream's own call raises TypeError).
 
+Distance-map losses (no upstream counterpart; kernels in csrc/ctl_dist.hip and csrc/ctl_loss.hip).  For a class k let S be the pixels of a
+slice with y == k (a label outside 0..C-1 belongs to no S).  The class field F_k(p) is a Euclidean distance in pixels within the slice: for
+p outside S to the nearest pixel of S, for p inside S to the nearest pixel not in S, i.e. distance_transform_edt(~S) + distance_transform_edt(S)
+when both sets are non-empty; F_k = 0 everywhere if S is empty or fills the plane.  D2_k = F_k^2 is an exact integer.  The signed map
+(Kervadec's one_hot2dist) is phi_k = F_k outside S and -(F_k - 1) inside, 0 where F_k = 0.  The confident label of a prediction is q = k where
+softmax(x)_k > 0.5 (strictly; at most one class qualifies), else 255.  Classes 1..C-1, div = B (C-1) H W, C >= 2:
+  'boundary'                L = (1/div) sum p_k phi_k (Kervadec et al., MIDL 2019);  g_k = phi_k / div, g_0 = 0.  Negative for a good prediction.
+  'hausdorff dt'            L = (1/div) sum (p_k - t_k)^2 (D2t_k + D2p_k) (Karimi & Salcudean, IEEE TMI 2019, alpha = 2) with D2t the squared
+                            field of y and D2p that of the confident label of x, a constant;  g_k = 2 (p_k - t_k)(D2t_k + D2p_k) / div, g_0 = 0.
+                            Both: dL/dx_j = p_j (g_j - sum_k p_k g_k).
+
 A label outside 0..C-1 is no class: t = 0 for every k and weight 0 (upstream would fail on it).
 `loss_type` may also be a mapping {name: weight}: sum of weight * L_name (no upstream counterpart; it exists for Dice + cross entropy)."""
 from __future__ import annotations
@@ -24,13 +35,15 @@ from collections.abc import Mapping
 import torch
 
 SMOOTH = 0.01
-LOSS_NAMES = ("cross entropy", "weighted cross entropy", "dice", "weighted dice", "foreground dice", "focal")
+DIST_LOSS_NAMES = ("boundary", "hausdorff dt")
+LOSS_NAMES = ("cross entropy", "weighted cross entropy", "dice", "weighted dice", "foreground dice", "focal") + DIST_LOSS_NAMES
+NO_CLASS = 255      # the confident label of a pixel where no class has more than half of the probability
 
 
 def parse_loss_type(loss_type, class_weights=None, num_classes=None):
     """[(name, weight)] of a loss name or a {name: weight} mapping, and the class weights as a tuple of floats (or None).  Unknown names and
-    'contour_smooth' raise NotImplementedError; class weights of the wrong length, an empty mapping and 'foreground dice' of one class
-    raise ValueError."""
+    'contour_smooth' raise NotImplementedError; class weights of the wrong length, an empty mapping and 'foreground dice', 'boundary' or
+    'hausdorff dt' of one class raise ValueError."""
     terms = [(k, float(v)) for k, v in loss_type.items()] if isinstance(loss_type, Mapping) else [(loss_type, 1.0)]
     for name, _ in terms:
         if name not in LOSS_NAMES:
@@ -43,6 +56,9 @@ def parse_loss_type(loss_type, class_weights=None, num_classes=None):
             raise ValueError(f"each class must have a weight: expected {num_classes} weights, got {len(class_weights)}")
     if num_classes is not None and num_classes < 2 and any(n == "foreground dice" for n, _ in terms):
         raise ValueError("'foreground dice' needs at least 2 classes")
+    for n, _ in terms:
+        if num_classes is not None and num_classes < 2 and n in DIST_LOSS_NAMES:
+            raise ValueError(f"{n!r} needs at least 2 classes")
     return terms, class_weights
 
 
@@ -59,7 +75,59 @@ def normalised_weights(class_weights, c):
     return w / total * c
 
 
-def _one(x, y, name, class_weights, gamma):
+def class_fields_host(label, n_class):
+    """F[B,C,H,W], float64: the class fields of a label map [B,H,W] as the module docstring defines them, with scipy's exact transform."""
+    import numpy as np
+    from scipy.ndimage import distance_transform_edt
+    y = label.detach().cpu().numpy() if isinstance(label, torch.Tensor) else np.asarray(label)
+    f = np.zeros((y.shape[0], int(n_class)) + y.shape[1:], dtype=np.float64)
+    for b in range(y.shape[0]):
+        for k in range(int(n_class)):
+            s = y[b] == k
+            if s.any() and not s.all():
+                f[b, k] = distance_transform_edt(~s) + distance_transform_edt(s)
+    return torch.from_numpy(f)
+
+
+def signed_from_fields(fields, label):
+    """phi[B,C,H,W], float64: F outside the class, -(F - 1) inside, 0 where the field is 0 (an absent or plane-filling class)."""
+    f = fields.double()
+    inside = label.detach().long().cpu().unsqueeze(1) == torch.arange(f.shape[1]).view(1, -1, 1, 1)
+    return torch.where(inside & (f > 0), -(f - 1.0), f)
+
+
+def confident_label_host(logit, margin=1e-5):
+    """(q, near): q uint8 [B,H,W] = the class whose float64 softmax probability exceeds 1/2, NO_CLASS where none does; near bool [B,H,W] =
+    the pixels where some |p_k - 1/2| < margin, whose q an fp32 softmax may decide the other way."""
+    p = torch.softmax(logit.detach().double().cpu(), 1)
+    hit = p > 0.5
+    q = torch.where(hit.any(1), hit.double().argmax(1), torch.full((), NO_CLASS, dtype=torch.long)).to(torch.uint8)
+    return q, ((p - 0.5).abs() < margin).any(1)
+
+
+def _dist_one(x, y, name, pred_fields):
+    b, c, h, w = x.shape
+    if c < 2:
+        raise ValueError(f"{name!r} needs at least 2 classes")
+    div = float(b * (c - 1) * h * w)
+    p = torch.softmax(x, 1)
+    fg = torch.ones(c, dtype=torch.float64).view(1, c, 1, 1)
+    fg[0, 0] = 0.0
+    ft = class_fields_host(y, c)
+    if name == "boundary":
+        phi = signed_from_fields(ft, y)
+        loss, g = (fg * p * phi).sum() / div, fg * phi / div
+    else:
+        t = (y.unsqueeze(1) == torch.arange(c).view(1, c, 1, 1)).double()
+        fp = class_fields_host(confident_label_host(x)[0], c) if pred_fields is None else pred_fields.detach().double().cpu()
+        d2 = torch.round(ft * ft) + torch.round(fp * fp)
+        loss, g = (fg * (p - t) ** 2 * d2).sum() / div, fg * 2.0 * (p - t) * d2 / div
+    return loss, p * (g - (p * g).sum(1, keepdim=True))
+
+
+def _one(x, y, name, class_weights, gamma, pred_fields=None):
+    if name in DIST_LOSS_NAMES:
+        return _dist_one(x, y, name, pred_fields)
     b, c, h, w = x.shape
     m = b * h * w
     p, logp = torch.softmax(x, 1), torch.log_softmax(x, 1)
@@ -84,15 +152,16 @@ def _one(x, y, name, class_weights, gamma):
     return 1.0 - (sel * num / u).sum() / div, p * (g - (p * g).sum(1, keepdim=True))
 
 
-def loss_and_grad(logit, label, loss_type="cross entropy", class_weights=None, gamma=2.0, gout=1.0):
-    """(loss, gout * dloss/dlogit), float64 CPU tensors (0-d and [B,C,H,W]) of a name or a {name: weight} mapping."""
+def loss_and_grad(logit, label, loss_type="cross entropy", class_weights=None, gamma=2.0, gout=1.0, pred_fields=None):
+    """(loss, gout * dloss/dlogit), float64 CPU tensors (0-d and [B,C,H,W]) of a name or a {name: weight} mapping.  `pred_fields`
+    ('hausdorff dt' only): the class fields F[B,C,H,W] of the prediction to use instead of those of confident_label_host(logit)."""
     x, y = logit.detach().double().cpu(), label.detach().long().cpu()
     if x.dim() != 4 or y.shape != (x.shape[0], x.shape[2], x.shape[3]):
         raise ValueError("expected logits [B,C,H,W] and a label map [B,H,W]")
     terms, class_weights = parse_loss_type(loss_type, class_weights, x.shape[1])
     loss, grad = torch.zeros((), dtype=torch.float64), torch.zeros_like(x)
     for name, weight in terms:
-        l, g = _one(x, y, name, class_weights, float(gamma))
+        l, g = _one(x, y, name, class_weights, float(gamma), pred_fields)
         loss, grad = loss + weight * l, grad + weight * g
     return loss, grad * float(gout)
 

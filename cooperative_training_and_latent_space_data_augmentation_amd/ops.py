@@ -284,6 +284,84 @@ def seg_loss_bwd(logit, label, kind, gout, ws=None, class_weights=None, gamma=2.
     return d
 
 
+# ---------------------------------------------------------------------------------------------- distance-map losses
+DIST_LOSS_KINDS = {"boundary": _ffi.DLOSS_BOUNDARY, "hausdorff dt": _ffi.DLOSS_HAUSDORFF_DT}      # name -> CTL_DLOSS_* kind
+DIST_LOSS_FORM = {"boundary": "signed", "hausdorff dt": "squared"}                               # the training form of the label fields a loss reads
+FIELD_FORMS = {"d2": _ffi.FIELD_D2, "signed": _ffi.FIELD_SIGNED, "squared": _ffi.FIELD_SQUARED}
+MAX_CLASSES = 16
+
+
+def class_fields(label: torch.Tensor, n_class: int, form: str = "d2") -> torch.Tensor:
+    """Class fields of a uint8 / int64 label map [B,H,W] (losses.class_fields_host): 'd2' = the exact squared fields, fp64 [B,C,H,W]; the
+    training forms 'signed' (Kervadec's signed map) and 'squared', fp32 logical [B,C,H,W] in NHWC memory like the logits they meet."""
+    if form not in FIELD_FORMS:
+        raise ValueError(f"class_fields: form {form!r} (one of {', '.join(FIELD_FORMS)})")
+    n_class = int(n_class)
+    if not 1 <= n_class <= MAX_CLASSES:
+        raise ValueError(f"class_fields: {n_class} classes (1 .. {MAX_CLASSES})")
+    require_gpu(label)
+    _arg(label, (torch.uint8, torch.int64), (None, None, None), "class_fields", "label", dense=True)
+    b, h, w = (int(v) for v in label.shape)
+    if form == "d2":
+        out = torch.empty((b, n_class, h, w), dtype=torch.float64, device=label.device)
+    else:
+        out = empty_nhwc(b, n_class, h, w, label.device)
+    ws, nbytes = _workspace("ctl_class_fields_ws_bytes", b, h, w, n_class, device=label.device)
+    call("ctl_class_fields", ptr(label), _ffi.LABEL_U8 if label.dtype == torch.uint8 else _ffi.LABEL_I64, b, h, w, n_class, FIELD_FORMS[form],
+         ptr(out), ptr(ws), nbytes, stream_ptr())
+    return out
+
+
+def confident_label(logit: torch.Tensor) -> torch.Tensor:
+    """uint8 [B,H,W]: the class whose softmax probability exceeds 1/2, 255 where none does (losses.confident_label_host)."""
+    require_gpu(logit)
+    logit = as_nhwc(logit)
+    n, c, h, w = logit.shape
+    out = torch.empty((n, h, w), dtype=torch.uint8, device=logit.device)
+    call("ctl_confident_label", ptr(logit), ptr(out), n * h * w, c, stream_ptr())
+    return out
+
+
+def _dist_loss_args(logit, label, kind, field_a, field_b):
+    if kind not in DIST_LOSS_KINDS:
+        raise NotImplementedError(f"distance-map loss {kind!r} (one of {', '.join(DIST_LOSS_KINDS)})")
+    two = kind == "hausdorff dt"
+    fields = (field_a, field_b) if two else (field_a,)
+    if any(f is None for f in fields):
+        raise ValueError(f"{kind!r} needs {'two field tensors (label, prediction)' if two else 'the signed map of the label'}")
+    require_gpu(logit, label, *fields)
+    if logit.dim() != 4 or logit.dtype != torch.float32 or label.dtype != torch.int64 or \
+            tuple(label.shape) != (logit.shape[0], logit.shape[2], logit.shape[3]):
+        raise ValueError("distance-map loss: expected fp32 logits [B,C,H,W] and an int64 label map [B,H,W]")
+    n, c, h, w = logit.shape
+    if c < 2:
+        raise ValueError(f"{kind!r} needs at least 2 classes")
+    for f in fields:
+        _arg(f, torch.float32, (n, c, h, w), "distance-map loss", "a field")
+    if not (all(t.permute(0, 2, 3, 1).is_contiguous() for t in (logit,) + fields) and label.is_contiguous()):
+        raise ValueError("distance-map loss: the logits and the fields must be NHWC in memory (channels_last) and the label map contiguous")
+    return DIST_LOSS_KINDS[kind], n, h * w, c
+
+
+def dist_loss_fwd(logit, label, kind, field_a, field_b=None):
+    """0-d fp32 device loss of 'boundary' (field_a = the signed map of the label) or 'hausdorff dt' (field_a / field_b = the squared fields of
+    the label / of confident_label(logit))."""
+    k, n, hw, c = _dist_loss_args(logit, label, kind, field_a, field_b)
+    ws = torch.empty(max(1, lib.ctl_dist_loss_ws_doubles(k, n, hw, c)), dtype=torch.float64, device=logit.device)
+    loss = torch.empty((), dtype=torch.float32, device=logit.device)
+    call("ctl_dist_loss_fwd", k, ptr(logit), ptr(label), ptr(field_a), ptr(field_b), n, hw, c, ptr(ws), ptr(loss), stream_ptr())
+    return loss
+
+
+def dist_loss_bwd(logit, label, kind, gout, field_a, field_b=None):
+    """gout (0-d fp32 device tensor) * dloss/dlogit; the prediction field of 'hausdorff dt' is a constant."""
+    k, n, hw, c = _dist_loss_args(logit, label, kind, field_a, field_b)
+    require_gpu(gout)
+    d = torch.empty_like(logit)
+    call("ctl_dist_loss_bwd", k, ptr(logit), ptr(label), ptr(field_a), ptr(field_b), ptr(gout), n, hw, c, ptr(d), stream_ptr())
+    return d
+
+
 def mse_fwd(a, b, scale):
     partial = torch.empty(_ffi.RED_BLOCKS, dtype=torch.float64, device=a.device)
     loss = torch.empty((), dtype=torch.float32, device=a.device)

@@ -20,8 +20,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .autograd import cross_entropy_2D, net_apply, scaled_mse, segmentation_loss, softmax_t, split_halves
-from .losses import parse_loss_type
+from .autograd import LabelFields, cross_entropy_2D, net_apply, scaled_mse, segmentation_loss, softmax_t, split_halves
+from .losses import DIST_LOSS_NAMES, parse_loss_type
 from .metrics import runningScore
 from .model_util import (_disable_tracking_bn_stats, _draw_seed, mask_latent_code_channel_wise,
                          mask_latent_code_spatial_wise, set_grad)
@@ -32,18 +32,29 @@ _DEFAULT_IMG_CFG = {"loss_name": "mse", "mask_type": "random", "max_threshold": 
 _DEFAULT_SEG_CFG = {"loss_name": "ce", "mask_type": "random", "max_threshold": 0.5, "random_threshold": True, "if_soft": True}
 
 
-def basic_loss_fn(pred, target, loss_type="cross entropy", class_weights=None, use_gpu=True):
+def needs_fields(loss_type) -> bool:
+    """Does the loss name or {name: weight} mapping contain a distance-map loss, i.e. read the class fields of the label?"""
+    names = loss_type if isinstance(loss_type, dict) else (loss_type,)
+    return any(n in DIST_LOSS_NAMES for n in names)
+
+
+def basic_loss_fn(pred, target, loss_type="cross entropy", class_weights=None, use_gpu=True, fields=None):
     """custom_loss.py:8-40 with upstream's names: 'cross entropy', 'weighted cross entropy', 'dice', 'weighted dice' (its weights are
     ignored, as upstream ignores them), 'foreground dice', 'focal' (gamma 2, upstream's detached gradient); 'contour_smooth' and unknown
     names raise NotImplementedError.  `loss_type` may also be a mapping {name: weight}: sum of weight * L_name (no upstream counterpart).
+    'boundary' and 'hausdorff dt' (no upstream counterpart either) read the class fields of `target`: `fields` is an autograd.LabelFields of
+    it to share between calls (or the tensor of the one form the spec needs); absent, the fields are computed here, once per call.
     `class_weights=None` is upstream's uniform 1/C.  Names and weights are checked before the tensors are looked at; the definitions
     are stated in losses.py."""
     if loss_type == "cross entropy" and class_weights is None:
         return cross_entropy_2D(pred, target)
     terms, class_weights = parse_loss_type(loss_type, class_weights, pred.size(1))
     total = None
+    if fields is None and any(name in DIST_LOSS_NAMES for name, _ in terms):
+        ops.require_gpu(pred, target)
+        fields = LabelFields(target, pred.size(1))
     for name, weight in terms:
-        l = cross_entropy_2D(pred, target) if name == "cross entropy" else segmentation_loss(pred, target, name, class_weights)
+        l = cross_entropy_2D(pred, target) if name == "cross entropy" else segmentation_loss(pred, target, name, class_weights, fields=fields)
         l = l if weight == 1.0 else l * weight
         total = l if total is None else total + l
     return total
@@ -82,6 +93,7 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
         _, class_weights = parse_loss_type(seg_loss_type, class_weights, num_classes)      # (NotImplementedError / ValueError likewise)
         self.seg_loss_type = dict(seg_loss_type) if isinstance(seg_loss_type, dict) else seg_loss_type
         self.class_weights = class_weights
+        self._fields_cache = None        # [(label tensor, its version, LabelFields)] of the running cooperative_step
         self.network_type, self.image_ch, self.checkpoint_dir = network_type, image_ch, checkpoint_dir
         self.num_classes, self.learning_rate, self.n_iter = num_classes, learning_rate, n_iter
         self.encoder_dropout, self.decoder_dropout = encoder_dropout, decoder_dropout
@@ -417,11 +429,38 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
         return logit
 
     # ------------------------------------------------------------------ losses of one step (model.py:414-467, 525-559)
+    @property
+    def _needs_fields(self) -> bool:
+        return needs_fields(self.seg_loss_type)
+
+    def _label_fields(self, label_l):
+        """The class fields of `label_l` for the distance-map losses of `seg_loss_type` (None when it names none: no launch, no
+        allocation).  Inside a cooperative_step they are computed once per distinct label tensor: the cache is cleared where the step
+        starts and its key holds the tensor itself, so neither a new tensor at a recycled address nor a refilled buffer of the previous
+        step is served stale.  Under graph capture the launches are part of the graph and read the static label buffer at every replay."""
+        if not self._needs_fields:
+            return None
+        if self._fields_cache is None:              # a direct call of standard_training / hard_example_training: once per call
+            return LabelFields(label_l, self.num_classes)
+        for key, version, fields in self._fields_cache:
+            if key is label_l and version == label_l._version:
+                return fields
+        fields = LabelFields(label_l, self.num_classes)
+        self._fields_cache.append((label_l, label_l._version, fields))
+        return fields
+
+    def _seg_loss(self, pred, target, fields):
+        """basic_loss_fn with the solver's loss spec; `fields` is only named where the spec reads it."""
+        if fields is None:
+            return basic_loss_fn(pred, target, self.seg_loss_type, self.class_weights)
+        return basic_loss_fn(pred, target, self.seg_loss_type, self.class_weights, fields=fields)
+
     def standard_training(self, clean_image_l, label_l, perturbed_image, separate_training=False, compute_gt_recon=True,
                           update_latent=True, disable_track_bn_stats=False, _pre=None):
         """`_pre = (z_i, z_s, image_recon_loss)`: the FTN encoder pass and the image branch were already issued by the caller
         (cooperative_step runs the image branch and the whole hard-example branch on the second stream)."""
         zero = torch.zeros((), device=clean_image_l.device)
+        fields = self._label_fields(label_l)
         if _pre is not None:
             z_i, z_s, image_recon_loss, y_0 = _pre
             if y_0 is None:
@@ -435,7 +474,7 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
             image_recon_loss = None
         if update_latent:
             self.z_i, self.z_s = z_i, z_s
-        standard_supervised_loss = basic_loss_fn(y_0, label_l.detach(), self.seg_loss_type, self.class_weights)
+        standard_supervised_loss = self._seg_loss(y_0, label_l.detach(), fields)
         if image_recon_loss is None and _pre is None:
             image_recon = self.decode_image(z_i)                       # always BN mode A, as upstream (model.py:444)
             image_recon_loss = scaled_mse(image_recon, clean_image_l, 0.5)
@@ -443,15 +482,15 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
         if compute_gt_recon and self.group_stn_passes and not disable_track_bn_stats and self.training:
             # the two STN passes are independent and share the BatchNorm mode: one grouped pass (same order: gt, then p)
             gt_recon, p_recon = self.recon_shape_pair(label_l.detach(), True, y_0_new, False)
-            gt_shape_recon_loss = basic_loss_fn(gt_recon, label_l, self.seg_loss_type, self.class_weights)
+            gt_shape_recon_loss = self._seg_loss(gt_recon, label_l, fields)
         else:
             if compute_gt_recon:
                 gt_recon = self.recon_shape(label_l.detach(), is_label_map=True)
-                gt_shape_recon_loss = basic_loss_fn(gt_recon, label_l, self.seg_loss_type, self.class_weights)
+                gt_shape_recon_loss = self._seg_loss(gt_recon, label_l, fields)
             else:
                 gt_shape_recon_loss = zero
             p_recon = self.recon_shape(y_0_new, is_label_map=False, disable_track_bn_stats=disable_track_bn_stats)
-        pred_shape_recon_loss = basic_loss_fn(p_recon, label_l, self.seg_loss_type, self.class_weights)
+        pred_shape_recon_loss = self._seg_loss(p_recon, label_l, fields)
         self._join_side()
         return standard_supervised_loss, image_recon_loss, gt_shape_recon_loss, pred_shape_recon_loss
 
@@ -459,19 +498,20 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
         dev = clean_image_l.device
         zero = torch.zeros((), device=dev)
         seg_loss = recon_loss = shape_loss = perturbed_p_recon_loss = zero
+        fields = self._label_fields(label_l)
         if perturbed_image is not None and perturbed_seg is not None and self.group_stn_passes and self.training:
             # FTN pass on the hard image, then both STN passes (prediction of the hard image, corrupted segmentation: independent,
             # both with frozen BatchNorm statistics tracking) as one grouped pass
             z_i, z_s = self._enc(perturbed_image.detach(), True)
             recon_loss = self._image_recon_loss(z_i, clean_image_l)              # (side stream when two_streams)
             y_0 = self._call(self.model["segmentation_decoder"], z_s, True)
-            seg_loss = basic_loss_fn(y_0, label_l.detach(), self.seg_loss_type, self.class_weights)
+            seg_loss = self._seg_loss(y_0, label_l.detach(), fields)
             if separate_training:
                 perturbed_seg = perturbed_seg.detach()
             p_recon, perturbed_p_recon = self.recon_shape_pair(y_0.detach() if separate_training else y_0, False, perturbed_seg, False,
                                                                disable_track_bn_stats=True)
-            shape_loss = basic_loss_fn(p_recon, label_l, self.seg_loss_type, self.class_weights)
-            perturbed_p_recon_loss = basic_loss_fn(perturbed_p_recon, label_l, self.seg_loss_type, self.class_weights)
+            shape_loss = self._seg_loss(p_recon, label_l, fields)
+            perturbed_p_recon_loss = self._seg_loss(perturbed_p_recon, label_l, fields)
             self._join_side()
             return seg_loss, recon_loss, shape_loss, perturbed_p_recon_loss
         if perturbed_image is not None:
@@ -482,7 +522,7 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
             if separate_training:
                 perturbed_seg = perturbed_seg.detach()
             perturbed_p_recon = self.recon_shape(perturbed_seg, is_label_map=False, disable_track_bn_stats=True)
-            perturbed_p_recon_loss = basic_loss_fn(perturbed_p_recon, label_l, self.seg_loss_type, self.class_weights)
+            perturbed_p_recon_loss = self._seg_loss(perturbed_p_recon, label_l, fields)
         return seg_loss, recon_loss, shape_loss, perturbed_p_recon_loss
 
     # ------------------------------------------------------------------ latent-space hard examples (model.py:300-350, 469-523)
@@ -638,6 +678,8 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
         if self._chain_events is not None:
             self._fork_event = torch.cuda.Event(enable_timing=True)
             self._fork_event.record(cur)
+        if self._needs_fields:                      # both chains read the label's fields: written once, in front of the fork
+            self._label_fields(label_l).get_all(self.seg_loss_type)
         side.wait_stream(cur)                       # fork point: right after the encoder
         for t in (z_i, z_s, clean_image_l, label_l):
             t.record_stream(side)
@@ -733,6 +775,7 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
         self.train()
         self._perturb_calls = 0
         self._step_schemes = []
+        self._fields_cache = [] if self._needs_fields else None
         if self._gstate is not None:
             ops.step_tick(self._gstate)           # (graph capture) RNG counter and Adam step advance on the device
         self.reset_all_optimizers()
@@ -749,6 +792,7 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
             return self._cooperative_step(clean_image_l, label_l, image_l, img_cfg, seg_cfg, latent_DA, separate_training, image_override,
                                           seg_override, do_optim, grad_hook)
         finally:
+            self._fields_cache = None
             for net in self.model.values():
                 net._defer_grads, net._deferred, net._stack = False, [], None
                 net.forget_pass()

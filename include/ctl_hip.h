@@ -318,6 +318,44 @@ int ctl_seg_loss_fwd(int32_t kind, const float* logit, const int64_t* label, con
                      int64_t hw, int32_t c, double* ws, float* loss, ctl_stream stream);
 int ctl_seg_loss_bwd(int32_t kind, const float* logit, const int64_t* label, const double* class_weights, float gamma, const float* gout,
                      const double* ws, int32_t b, int64_t hw, int32_t c, float* dlogit, ctl_stream stream);
+/* Distance-map losses (no upstream counterpart; ctl_dist.hip, ctl_loss.hip): the boundary loss of Kervadec et al. (MIDL 2019) and the
+ * distance-transform Hausdorff loss of Karimi & Salcudean (IEEE TMI 2019, alpha = 2), with the distance maps computed per step on the device.
+ *
+ * ctl_class_fields: label uint8 or int64 [b][h][w] (label_dtype CTL_LABEL_*), n_class in 1..16, unit spacing, per slice.  With S the pixels
+ *   of a slice that carry class k (a label outside 0..n_class-1 belongs to no S), the class field F_k(p) is the exact Euclidean distance from p
+ *   to the nearest pixel of S for p outside S and to the nearest pixel NOT in S for p inside S; F_k = 0 everywhere when S is empty or fills
+ *   the plane.  D2_k = F_k^2 is an integer.  out, by `form`:
+ *     CTL_FIELD_D2       double [b][n_class][h][w]   D2
+ *     CTL_FIELD_SIGNED   float  [b][h][w][n_class]   the signed map phi: F outside S, -(F - 1) inside, 0 where F = 0; the fp64 value rounded once
+ *     CTL_FIELD_SQUARED  float  [b][h][w][n_class]   D2 (exact: every D2 < 2^24)
+ *   The float forms have the layout of NHWC logits.  h, w <= 2048: the transform runs in 32-bit integers; longer axes are refused.
+ *   workspace: ctl_class_fields_ws_bytes(b, h, w, n_class) bytes (two uint16 row-distance maps per class).  Two launches whatever the sizes and
+ *   the content are; no readback, no atomics, the same bits on every call and in a graph replay.
+ * ctl_confident_label: logit float NHWC [pixels][c] -> out uint8 [pixels]: k if softmax(logit)_k > 0.5 (strictly; at most one class can), else
+ *   255.  The softmax is the fp32 one of the loss kernels.  One launch.
+ * ctl_dist_loss_fwd / _bwd: logit float NHWC [b][hw][c], c in 2..16, p = softmax over c, t = one-hot of the int64 label [b][hw] (out of range:
+ *   t = 0), classes 1..c-1, div = b (c - 1) hw.  The fields are INPUTS, float [b][hw][c] as ctl_class_fields writes them:
+ *     CTL_DLOSS_BOUNDARY      field_a = signed map of the label (field_b and label unused, NULL allowed):
+ *                             loss = (1/div) sum p_k a_k;  g_k = a_k / div
+ *     CTL_DLOSS_HAUSDORFF_DT  field_a = squared field of the label, field_b = squared field of ctl_confident_label(logit), a constant:
+ *                             loss = (1/div) sum (p_k - t_k)^2 (a_k + b_k);  g_k = 2 (p_k - t_k)(a_k + b_k) / div
+ *   g_0 = 0 and dlogit_j = gout p_j (g_j - sum_k p_k g_k).  fwd: two launches (fp64 block sums into ws, ctl_dist_loss_ws_doubles doubles, then
+ *   one finalize block in a fixed order) write loss[0]; bwd: one launch recomputes the softmax, reads gout[0] on the device and writes every
+ *   element of dlogit.
+ * Null pointers, an unknown dtype / form / kind, non-positive sizes, a class count out of range, an axis above 2048, a tensor at or past 2 GiB
+ * and a workspace that is too small are refused with CTL_EINVAL before any launch; the size queries return 0 for them. */
+enum { CTL_LABEL_U8 = 0, CTL_LABEL_I64 = 1 };
+enum { CTL_FIELD_D2 = 0, CTL_FIELD_SIGNED = 1, CTL_FIELD_SQUARED = 2 };
+enum { CTL_DLOSS_BOUNDARY = 0, CTL_DLOSS_HAUSDORFF_DT = 1 };
+size_t ctl_class_fields_ws_bytes(int32_t b, int32_t h, int32_t w, int32_t n_class);
+int ctl_class_fields(const void* label, int32_t label_dtype, int32_t b, int32_t h, int32_t w, int32_t n_class, int32_t form, void* out,
+                     void* workspace, size_t workspace_bytes, ctl_stream stream);
+int ctl_confident_label(const float* logit, uint8_t* out, int64_t pixels, int32_t c, ctl_stream stream);
+size_t ctl_dist_loss_ws_doubles(int32_t kind, int32_t b, int64_t hw, int32_t c);
+int ctl_dist_loss_fwd(int32_t kind, const float* logit, const int64_t* label, const float* field_a, const float* field_b, int32_t b,
+                      int64_t hw, int32_t c, double* ws, float* loss, ctl_stream stream);
+int ctl_dist_loss_bwd(int32_t kind, const float* logit, const int64_t* label, const float* field_a, const float* field_b, const float* gout,
+                      int32_t b, int64_t hw, int32_t c, float* dlogit, ctl_stream stream);
 /* loss = scale * mean((a-b)^2) (model.py:445-447: scale 0.5; util.py:216: scale 1); bwd: da = gout*2*scale*(a-b)/count */
 int ctl_mse_fwd(const float* a, const float* b, int64_t count, float scale, double* partial, float* loss,
                 ctl_stream stream);

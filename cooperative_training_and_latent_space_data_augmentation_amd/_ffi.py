@@ -35,6 +35,10 @@ DLOSS_BOUNDARY, DLOSS_HAUSDORFF_DT = 0, 1                       # CTL_DLOSS_* ki
 FIELD_D2, FIELD_SIGNED, FIELD_SQUARED = 0, 1, 2                 # CTL_FIELD_* forms of ctl_class_fields
 LABEL_U8, LABEL_I64 = 0, 1                                      # CTL_LABEL_* of ctl_class_fields
 TTA_LOGIT, TTA_PROB, TTA_MAX_VIEWS = 0, 1, 8                    # CTL_TTA_* of ctl_tta_merge
+# the optimizer tail's control record (CTL_OPTIM_* of ctl_hip.h): word indices of a double[OPTIM_CTRL_DOUBLES], and the pass-1 chunk
+OPTIM_CTRL_DOUBLES, OPTIM_MAX_NETS, GRAD_NORM_CHUNK = 32, 8, 16384
+OPTIM_LR, OPTIM_MAX_NORM, OPTIM_GUARD, OPTIM_EMA_OMD = 0, 8, 9, 10
+OPTIM_SUMSQ, OPTIM_NORM, OPTIM_CLIP, OPTIM_FINITE, OPTIM_SKIPPED = 16, 17, 18, 19, 20
 OP_DTYPE = np.dtype([("kind", "<i4"), ("i", "<i4", (27,)), ("f", "<f4", (4,)), ("slot", "<i4", (OP_MAX_T,)),
                      ("off", "<i8", (OP_MAX_T,)), ("l", "<i8", (4,))], align=True)
 
@@ -259,6 +263,10 @@ def _signatures() -> dict:
         "ctl_adam": (int_, [p] * 4 + [i64] + [f32] * 4 + [i32, f32, p]),
         "ctl_accumulate": (int_, [p, p, i32, i64, p]),
         "ctl_adam_dev": (int_, [p] * 4 + [i64] + [f32] * 4 + [p, f32, p]),
+        "ctl_optim_control": (int_, [p, i32, p, f32, i32, f32, p]),
+        "ctl_grad_norm_work": (sz, [p, i32]),
+        "ctl_grad_norm": (int_, [p, p, i32, f32, p, p, p]),
+        "ctl_adam_tail": (int_, [p] * 5 + [i64] + [f32] * 3 + [p, i32, f32, p, i32, p]),
         "ctl_plan_run": (int_, [p, i32, p, i32, p]),
         "ctl_prof_start": (int_, [cstr]),
         "ctl_prof_start_sampled": (int_, [cstr, i32]),

@@ -9,6 +9,9 @@ What may not be baked into a captured launch lives on the device instead:
     `ctl_adam_dev`);
   * the random thresholds k of the targeted masks: int32 device scalars the host refreshes before every replay from `np.random`, in the
     reference's draw order (model_util.py:229-230) -- so a seeded run draws the reference's k sequence;
+  * the learning rates and the EMA decay of the optimizer tail (solver.write_optim_control): the solver's device control record, which
+    `__call__` refreshes with one eager launch in front of every replay -- the captured norm and Adam-tail launches read it, so a
+    schedule or `set_lr` between replays takes effect (a captured `ctl_adam_dev` replays the rate it was captured with);
   * the masking scheme of `mask_type='random'` (python `random.shuffle`, model.py:325-329) changes the launch sequence: one graph per
     (image scheme, segmentation scheme) pair, picked per step by the same host draw.
 Inputs are copied into static buffers; the returned losses / `solver.z_i` / `last_masks` are the graph's static outputs (valid until
@@ -61,6 +64,7 @@ class CooperativeStepGraph:
         self.replays = 0
         self.k_log = []                # the k values handed to the replays, in draw order (tests compare them with the eager sequence)
         self._dev_adam_count = None    # what state[2] holds on the device after the launches issued so far
+        self._tail_captured = None     # was the solver's optimizer tail on when the graphs were captured?
 
     def _new_segments(self, graph):
         other = next((x.segments for x in self.entries.values() if x.segments is not None), None)
@@ -124,6 +128,7 @@ class CooperativeStepGraph:
         counts = self._adam_step_counts()
         if len(set(counts)) != 1:
             raise CtlError("CooperativeStepGraph: the five optimizers must be at the same step count (one device-side counter)")
+        ema_counts = (s.ema_num_updates, [o.num_updates for o in s.optimizers.values()])
         # host RNG streams and the BatchNorm buffers are put back after the warm-up: capturing must not advance the training state
         rng = (random.getstate(), np.random.get_state(), torch.get_rng_state())
         saved = {k: (m._bflat.clone(), m._nbt.clone()) for k, m in s.model.items()}
@@ -175,6 +180,9 @@ class CooperativeStepGraph:
                 dp.suspended = False
             for o, c0 in zip(s.optimizers.values(), counts):           # capturing executed nothing: undo the host-side mirror
                 o.step_count = c0
+            s.ema_num_updates = ema_counts[0]
+            for o, n0 in zip(s.optimizers.values(), ema_counts[1]):
+                o.num_updates = n0
             random.setstate(rng[0])
             np.random.set_state(rng[1])
             torch.set_rng_state(rng[2])
@@ -188,6 +196,13 @@ class CooperativeStepGraph:
             self.static_in = tuple(t.detach().clone(memory_format=torch.preserve_format) for t in (clean, label, noisy))
         elif any(a.shape != b.shape or a.dtype != b.dtype for a, b in zip(self.static_in, (clean, label, noisy))):
             raise CtlError("CooperativeStepGraph: input shapes / dtypes are fixed at the first call (build one graph object per shape)")
+        if self._tail_captured is None:
+            self._tail_captured = s._tail_on
+        elif self._tail_captured != s._tail_on:
+            raise CtlError("CooperativeStepGraph: the solver's optimizer tail was switched on after capture (set_lr on a solver built without "
+                           "it): the captured Adam launches carry their learning rate.  Build a new graph object")
+        if s._ema_in:
+            s.train()                          # a step trains the live weights: eval() had swapped the EMA shadows in
         schemes = self._draw_schemes()
         e = self.entries.get(schemes)
         if e is None:
@@ -207,6 +222,8 @@ class CooperativeStepGraph:
             raise CtlError("CooperativeStepGraph: the five optimizers must be at the same step count (one device-side counter)")
         if counts[0] != self._dev_adam_count:
             self.state[2:3].fill_(counts[0])
+        if s._tail_on:
+            s.write_optim_control()            # this step's lr and EMA decay, as launch arguments (see _draw_ks)
         if self.replay_mode == "segments":
             if e.segments is None:
                 e.segments = self._new_segments(e.graph)
@@ -218,6 +235,10 @@ class CooperativeStepGraph:
             e.adam_graph.replay()
         for o in s.optimizers.values():        # host mirrors of what the replay did on the device
             o.step_count += 1
+            if o.ema is not None:
+                o.num_updates += 1
+        if s.use_ema:
+            s.ema_num_updates += 1
         self._dev_adam_count = counts[0] + 1
         for m in s.model.values():
             m.weights_changed()

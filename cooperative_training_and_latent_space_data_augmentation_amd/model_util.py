@@ -151,3 +151,147 @@ def mask_latent_code_spatial_wise(latent_code, decoder_function, label, num_clas
     """Mask the top-k positions ranked by the signed mean of dL/dz over C; mask [N,1,H,W]."""
     return _mask(latent_code, decoder_function, label, num_classes, percentile, random, loss_type, if_detach, if_soft, 1, k,
                  soft_noise)
+
+
+# ---------------------------------------------------------------------------------------------- EMA of the weights (:21-101)
+class ExponentialMovingAverage:
+    """Upstream's class on any parameter list, plain torch: shadow <- shadow - (1 - decay_t) * (shadow - param) per update, with
+    decay_t = min(decay, (1 + n) / (10 + n)) for update number n when use_num_updates.  (The solver keeps its shadows flat on the device
+    and updates them inside the Adam pass -- optim.FlatAdam.ema; this class is the statement those are tested against.)"""
+
+    def __init__(self, parameters, decay, use_num_updates=True):
+        if not 0.0 <= decay <= 1.0:
+            raise ValueError("Decay must be between 0 and 1")
+        self.decay = decay
+        self.num_updates = 0 if use_num_updates else None
+        self.shadow_params = [p.clone().detach() for p in parameters if p.requires_grad]
+        self.collected_params = []
+
+    def update(self, parameters):
+        decay = self.decay
+        if self.num_updates is not None:
+            self.num_updates += 1
+            decay = min(decay, (1 + self.num_updates) / (10 + self.num_updates))
+        omd = 1.0 - decay
+        with torch.no_grad():
+            for s, p in zip(self.shadow_params, [p for p in parameters if p.requires_grad]):
+                s.sub_(omd * (s - p))
+
+    def copy_to(self, parameters):
+        for s, p in zip(self.shadow_params, parameters):
+            if p.requires_grad:
+                p.data.copy_(s.data)
+
+    def store(self, parameters):
+        self.collected_params = [p.clone() for p in parameters if p.requires_grad]
+
+    def restore(self, parameters):
+        if not self.collected_params:
+            print("did not find any copy, use the original params")
+            return
+        for c, p in zip(self.collected_params, parameters):
+            if p.requires_grad:
+                p.data.copy_(c.data)
+
+
+# ---------------------------------------------------------------------------------------------- learning-rate schedules (:589-671)
+def lr_poly(base_lr, iter, max_iter, power):
+    return base_lr * ((1 - float(iter) / max_iter) ** power)
+
+
+def adjust_learning_rate(optimizer, i_iter, initial_learning_rate, total_steps, power=0.985):
+    """:593-600: the polynomial rate into every param group; a second group runs at ten times it."""
+    lr = lr_poly(initial_learning_rate, i_iter, total_steps, power)
+    for group in optimizer.param_groups:
+        group["lr"] = lr
+    if len(optimizer.param_groups) > 1:
+        optimizer.param_groups[1]["lr"] = lr * 10
+    return lr
+
+
+class _FactorSchedule:
+    """lr(epoch) = base_lr * factor(epoch), the closed form of torch's LambdaLR / StepLR: the rate of epoch 0 is written at construction,
+    step() moves to the next epoch.  Works on anything with `param_groups` (FlatAdam, torch.optim.Optimizer)."""
+
+    def __init__(self, optimizer, factor):
+        self.optimizer, self.factor = optimizer, factor
+        self.base_lrs = [g["lr"] for g in optimizer.param_groups]
+        self.last_epoch = 0
+        self._write()
+
+    def _write(self):
+        for g, base in zip(self.optimizer.param_groups, self.base_lrs):
+            g["lr"] = base * self.factor(self.last_epoch)
+
+    def step(self, metric=None):
+        self.last_epoch += 1
+        self._write()
+
+    def get_last_lr(self):
+        return [g["lr"] for g in self.optimizer.param_groups]
+
+    def state_dict(self):
+        return {"base_lrs": list(self.base_lrs), "last_epoch": self.last_epoch}
+
+    def load_state_dict(self, sd):
+        self.base_lrs, self.last_epoch = list(sd["base_lrs"]), int(sd["last_epoch"])
+        self._write()
+
+
+class _PlateauSchedule:
+    """torch's ReduceLROnPlateau(mode='min', threshold_mode='rel', cooldown=0, min_lr=0, eps=1e-8): step(metric) multiplies the rate by
+    `factor` once the metric has not fallen below best * (1 - threshold) for more than `patience` calls in a row."""
+
+    def __init__(self, optimizer, factor, threshold=0.01, patience=5, eps=1e-8):
+        self.optimizer, self.factor, self.threshold, self.patience, self.eps = optimizer, factor, threshold, patience, eps
+        self.best, self.num_bad_epochs, self.last_epoch = float("inf"), 0, 0
+
+    def step(self, metric=None):
+        if metric is None:
+            raise ValueError("a plateau schedule needs the epoch's metric: step(metric)")
+        current = float(metric)
+        self.last_epoch += 1
+        if current < self.best * (1.0 - self.threshold):
+            self.best, self.num_bad_epochs = current, 0
+        else:
+            self.num_bad_epochs += 1
+        if self.num_bad_epochs > self.patience:
+            for g in self.optimizer.param_groups:
+                old = float(g["lr"])
+                new = max(old * self.factor, 0.0)
+                if old - new > self.eps:
+                    g["lr"] = new
+            self.num_bad_epochs = 0
+
+    def get_last_lr(self):
+        return [g["lr"] for g in self.optimizer.param_groups]
+
+    def state_dict(self):
+        return {"best": self.best, "num_bad_epochs": self.num_bad_epochs, "last_epoch": self.last_epoch, "lrs": self.get_last_lr()}
+
+    def load_state_dict(self, sd):
+        self.best, self.num_bad_epochs, self.last_epoch = float(sd["best"]), int(sd["num_bad_epochs"]), int(sd["last_epoch"])
+        for g, lr in zip(self.optimizer.param_groups, sd["lrs"]):
+            g["lr"] = lr
+
+
+def _warmstart(hi, lo):
+    return lambda epoch: 0.1 if epoch < 5 else (1 if epoch < hi else (0.1 if epoch < lo else 0.01))
+
+
+def get_scheduler(optimizer, lr_policy, lr_decay_iters=5, epoch_count=None, niter=None, niter_decay=None):
+    """:621-671, the seven policies as small host objects with `.step(metric=None)` that write `param_groups[*]['lr']`; they restate
+    torch's closed forms and need no torch.optim.lr_scheduler (which refuses FlatAdam).  An unknown name raises NotImplementedError
+    (upstream returns the exception object)."""
+    if lr_policy == "lambda":
+        return _FactorSchedule(optimizer, lambda epoch: 1.0 - max(0, epoch + 1 + epoch_count - niter) / float(niter_decay + 1))
+    if lr_policy in ("step", "step2"):
+        gamma = 0.5 if lr_policy == "step" else 0.1
+        return _FactorSchedule(optimizer, lambda epoch: gamma ** (epoch // lr_decay_iters))
+    if lr_policy in ("plateau", "plateau2"):
+        return _PlateauSchedule(optimizer, factor=0.1 if lr_policy == "plateau" else 0.2, threshold=0.01, patience=5)
+    if lr_policy == "step_warmstart":
+        return _FactorSchedule(optimizer, _warmstart(100, 200))
+    if lr_policy == "step_warmstart2":
+        return _FactorSchedule(optimizer, _warmstart(50, 100))
+    raise NotImplementedError("learning rate policy [%s] is not implemented" % lr_policy)

@@ -583,6 +583,74 @@ def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0, state: Op
         call("ctl_adam", ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, beta1, beta2, eps, step, grad_scale, stream_ptr())
 
 
+# ---------------------------------------------------------------------------------------------- optimizer tail (ctl_optim.hip)
+def _ctrl_arg(ctrl: torch.Tensor, who: str) -> None:
+    _arg(ctrl, torch.float64, (_ffi.OPTIM_CTRL_DOUBLES,), who, "ctrl", dense=True, on_device=True)
+
+
+def optim_ctrl(device) -> torch.Tensor:
+    """A zeroed control record (ctl_hip.h, "optimizer tail") with clip = finite = 1: neutral until optim_control / grad_norm write it."""
+    ctrl = torch.zeros(_ffi.OPTIM_CTRL_DOUBLES, dtype=torch.float64, device=device)
+    ctrl[_ffi.OPTIM_CLIP:_ffi.OPTIM_FINITE + 1] = 1.0
+    return ctrl
+
+
+def optim_control(ctrl: torch.Tensor, lrs, max_norm: float = 0.0, skip_nonfinite: bool = False, ema_omd: float = 0.0) -> None:
+    """Write the host fields of the control record: ONE launch, the values travel as launch arguments (graph.py: a replay may be
+    queued far ahead of the device, so they must not sit in host memory that the next step overwrites)."""
+    _ctrl_arg(ctrl, "optim_control")
+    lrs = [float(v) for v in lrs]
+    if not 1 <= len(lrs) <= _ffi.OPTIM_MAX_NETS:
+        raise ValueError(f"optim_control: 1 to {_ffi.OPTIM_MAX_NETS} learning rates, got {len(lrs)}")
+    arr = (C.c_float * len(lrs))(*lrs)
+    call("ctl_optim_control", ptr(ctrl), len(lrs), C.cast(arr, C.c_void_p), float(max_norm), int(bool(skip_nonfinite)), float(ema_omd), stream_ptr())
+
+
+def grad_norm_work(counts) -> int:
+    """Doubles of workspace grad_norm needs for flat buffers of these sizes."""
+    arr = (C.c_int64 * len(counts))(*[int(c) for c in counts])
+    size = lib.ctl_grad_norm_work(C.cast(arr, C.c_void_p), len(counts))
+    if size == 0:
+        raise ValueError(f"grad_norm_work: 1 to {_ffi.OPTIM_MAX_NETS} positive counts, got {list(counts)}")
+    return size
+
+
+def grad_norm(grads, grad_scale: float, ctrl: torch.Tensor, work: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Global norm of the flat fp32 gradient buffers `grads` (1 to 8) into the control record: sumsq, norm, clip, finite, skipped.
+    Two launches, no readback.  Returns the workspace (pass it back in to reuse it)."""
+    _ctrl_arg(ctrl, "grad_norm")
+    grads = list(grads)
+    if not 1 <= len(grads) <= _ffi.OPTIM_MAX_NETS:
+        raise ValueError(f"grad_norm: 1 to {_ffi.OPTIM_MAX_NETS} gradient buffers, got {len(grads)}")
+    for j, g in enumerate(grads):
+        _arg(g, torch.float32, (None,), "grad_norm", f"grads[{j}]", dense=True, on_device=True)
+    counts = [g.numel() for g in grads]
+    need = grad_norm_work(counts)
+    if work is None:
+        work = torch.empty(need, dtype=torch.float64, device=ctrl.device)
+    else:
+        _arg(work, torch.float64, (None,), "grad_norm", "work", dense=True, on_device=True)
+        if work.numel() < need:
+            raise ValueError(f"grad_norm: work holds {work.numel()} doubles, {need} needed")
+    ptrs = (C.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
+    cnts = (C.c_int64 * len(grads))(*counts)
+    call("ctl_grad_norm", C.cast(ptrs, C.c_void_p), C.cast(cnts, C.c_void_p), len(grads), float(grad_scale), ptr(work), ptr(ctrl), stream_ptr())
+    return work
+
+
+def adam_tail(p, g, m, v, ema: Optional[torch.Tensor], beta1, beta2, eps, step, grad_scale, ctrl: torch.Tensor, net: int,
+              state: Optional[torch.Tensor] = None) -> None:
+    """ctl_adam / ctl_adam_dev with lr, clip factor and skip decision read from the control record, and the EMA shadow `ema` (or None)
+    updated in the same pass."""
+    _ctrl_arg(ctrl, "adam_tail")
+    for name, t in (("p", p), ("g", g), ("m", m), ("v", v)) + ((("ema", ema),) if ema is not None else ()):
+        _arg(t, torch.float32, (p.numel(),), "adam_tail", name, dense=True, on_device=True)
+    if not 0 <= int(net) < _ffi.OPTIM_MAX_NETS:
+        raise ValueError(f"adam_tail: net must lie in 0..{_ffi.OPTIM_MAX_NETS - 1}, got {net}")
+    call("ctl_adam_tail", ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), p.numel(), beta1, beta2, eps, ptr(state), int(step), grad_scale,
+         ptr(ctrl), int(net), stream_ptr())
+
+
 # ---------------------------------------------------------------------------------------------- SURVEY 8(f): metrics + input pipeline
 def confusion_hist(label_true: torch.Tensor, label_pred: torch.Tensor, n_class: int, hist: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Accumulate `runningScore._fast_hist` (metrics.py:18-23) into `hist` (int64 [n_class, n_class], created zeroed if None)."""

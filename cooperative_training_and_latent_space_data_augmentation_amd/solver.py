@@ -19,14 +19,14 @@ from typing import Dict, Optional
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import _ffi, ops
 from .autograd import LabelFields, cross_entropy_2D, net_apply, scaled_mse, segmentation_loss, softmax_t, split_halves
 from .losses import DIST_LOSS_NAMES, parse_loss_type
 from .metrics import runningScore
-from .model_util import (_disable_tracking_bn_stats, _draw_seed, mask_latent_code_channel_wise,
+from .model_util import (_disable_tracking_bn_stats, _draw_seed, get_scheduler, mask_latent_code_channel_wise,
                          mask_latent_code_spatial_wise, set_grad)
 from .nets import build_networks, check_config
-from .optim import FlatAdam
+from .optim import FlatAdam, ema_decay_at
 
 _DEFAULT_IMG_CFG = {"loss_name": "mse", "mask_type": "random", "max_threshold": 0.5, "random_threshold": True, "if_soft": True}
 _DEFAULT_SEG_CFG = {"loss_name": "ce", "mask_type": "random", "max_threshold": 0.5, "random_threshold": True, "if_soft": True}
@@ -76,13 +76,20 @@ SPLIT_WGRAD_TAIL = True     # a stacked backward runs its weight-gradient family
 class AdvancedTripletReconSegmentationModel(nn.Module):
     def __init__(self, network_type="FCN_16_standard", image_ch=1, learning_rate=1e-4, encoder_dropout=None,
                  decoder_dropout=None, num_classes=4, n_iter=1, checkpoint_dir=None, use_gpu=True, debug=False, *, compute_dtype=None,
-                 seg_loss_type="cross entropy", class_weights=None):
+                 seg_loss_type="cross entropy", class_weights=None, max_grad_norm=None, skip_nonfinite=False, use_ema=False,
+                 ema_decay=0.999, ema_use_num_updates=True, lr_policy=None, lr_decay_iters=5, epoch_count=None, niter=None,
+                 niter_decay=None):
         """`compute_dtype` (keyword-only, no upstream counterpart): "fp32" = the reference's arithmetic (default, BASELINE config 2);
         "bf16" = BASELINE config 3: network-internal activations / gradients stored as bf16, convolutions on bf16 MFMA with fp32
         accumulation, fp32 master weights / BatchNorm statistics / losses.
         `seg_loss_type` / `class_weights` (keyword-only, no upstream counterpart): the `loss_type` and `class_weights` of every
         `basic_loss_fn` call that compares logits with `label_l` in standard_training and hard_example_training -- a name or a
-        {name: weight} mapping.  The saliency loss of hard_example_generation (`loss_name` of the DA configs) is not affected."""
+        {name: weight} mapping.  The saliency loss of hard_example_generation (`loss_name` of the DA configs) is not affected.
+        The optimizer tail (keyword-only, all off by default; DESIGN.md "Optimizer tail"): `max_grad_norm` clips the global gradient
+        norm over the five networks as clip_grad_norm_(solver.parameters(), max_norm) would; `skip_nonfinite` leaves weights, moments and
+        shadows untouched in a step whose gradient norm is not finite; `use_ema` / `ema_decay` / `ema_use_num_updates` keep upstream's
+        ExponentialMovingAverage of the weights, which eval() predicts with; `lr_policy` (+ `lr_decay_iters`, `epoch_count`, `niter`,
+        `niter_decay`) is model_util.get_scheduler's policy, advanced by scheduler_step()."""
         super().__init__()
         self.compute_dtype = compute_dtype or "fp32"
         if network_type not in ("FCN_16_standard", "FCN_16_standard_w_o_filter", "FCN_16_standard_share_code"):
@@ -100,6 +107,21 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
         self.use_gpu, self.debug = use_gpu, debug
         self.device = torch.device("cuda", torch.cuda.current_device())
         self.model = self.get_network(checkpoint_dir=checkpoint_dir)
+        if max_grad_norm is not None and not (max_grad_norm > 0 and max_grad_norm < float("inf")):
+            raise ValueError("max_grad_norm must be a positive finite number (None: no clipping)")
+        if not 0.0 <= ema_decay <= 1.0:
+            raise ValueError("ema_decay must be between 0 and 1")
+        self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
+        self.use_ema, self.ema_decay, self.ema_use_num_updates = bool(use_ema), float(ema_decay), bool(ema_use_num_updates)
+        self.lr_policy = lr_policy
+        self._sched_kw = dict(lr_decay_iters=lr_decay_iters, epoch_count=epoch_count, niter=niter, niter_decay=niter_decay)
+        self._tail_on = max_grad_norm is not None or self.skip_nonfinite or self.use_ema or lr_policy is not None
+        self._ctrl = self._norm_work = None      # the device control record of the tail and the norm's workspace
+        self.ema_num_updates = 0                 # EMA updates issued (host count: a step the device skipped is counted too)
+        self._ema_in = False                     # eval() has swapped the shadows in; _ema_stash holds the live weights
+        self._ema_stash = None
+        self.schedulers = None
+        self._gstate = None
         self.optimizers = None
         self.reset_all_optimizers()
         self.latent_code = {"image": None, "segmentation": None, "shape": None}
@@ -180,10 +202,19 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
         epoch_path = join(save_dir, "interrupted", "checkpoints")
         os.makedirs(epoch_path, exist_ok=True)
         save_path = join(epoch_path, self.network_type + ".pkl")
+        swapped = self._ema_in                   # saved during eval: the file gets the live weights, like one saved while training
+        if swapped:
+            self.train(if_testing=False)
+            self.training = False
         state = {"network_type": self.network_type, "epoch": epoch,
                  "model_state": {k: {n: v.detach().cpu().clone() for n, v in m.state_dict().items()} for k, m in self.model.items()},
                  "optimizer_state": {k: o.state_dict() for k, o in self.optimizers.items()}}
+        if self._tail_on:                        # a new key; files without it load as before
+            state["optim_tail"] = {"ema_num_updates": self.ema_num_updates, "skipped": self.optim_report()["skipped_steps"],
+                                   "scheduler": {k: s.state_dict() for k, s in (self.schedulers or {}).items()}}
         torch.save(state, save_path)
+        if swapped:
+            self.eval()
         return save_path
 
     def load_snapshots(self, file_path):
@@ -196,11 +227,24 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
             net.load_state_dict(ckpt["model_state"][k])
         for k, opt in self.optimizers.items():
             opt.load_state_dict(ckpt["optimizer_state"][k])
+        tail = ckpt.get("optim_tail")
+        if self._tail_on:
+            self._ema_in = False                 # the file's weights are live weights
+            self.ema_num_updates = int(tail["ema_num_updates"]) if tail else 0
+            self._ctrl[_ffi.OPTIM_SKIPPED] = float(tail["skipped"]) if tail else 0.0
+            for k, sd in (tail["scheduler"] if tail else {}).items():
+                if self.schedulers is not None and k in self.schedulers:
+                    self.schedulers[k].load_state_dict(sd)
         return ckpt["epoch"]
 
     # ------------------------------------------------------------------ mode switches / optimizers (model.py:740-795)
     def train(self, if_testing=False):
         self.training = True          # upstream never clears this inside train(); eval() clears it first
+        if not if_testing and self._ema_in:      # back to the live weights (base_segmentation_model.train(): ema.restore)
+            for name, net in self.model.items():
+                net._flat_data.copy_(self._ema_stash[name])
+                net.weights_changed()
+            self._ema_in = False
         for net in self.model.values():
             if not if_testing:
                 net.train()
@@ -212,10 +256,88 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
     def eval(self):
         self.training = False
         self.train(if_testing=True)
+        if self.use_ema and not self._ema_in:    # predict with the shadows (base_segmentation_model.eval(): ema.store, ema.copy_to).
+            if self._ema_stash is None:          # a second eval() keeps the stash: upstream overwrites it with the EMA weights
+                self._ema_stash = {name: torch.empty_like(net._flat_data) for name, net in self.model.items()}
+            for name, net in self.model.items():
+                self._ema_stash[name].copy_(net._flat_data)
+                net._flat_data.copy_(self.optimizers[name].ema)
+                net.weights_changed()
+            self._ema_in = True
         return self
 
     def set_optimizers(self):
         self.optimizers = {name: FlatAdam(net, lr=self.learning_rate) for name, net in self.model.items()}
+        if self._tail_on:
+            self._enable_tail()
+
+    # ------------------------------------------------------------------ optimizer tail: schedules, clipping, guard, EMA
+    def _enable_tail(self):
+        """Route the five Adam launches through ctl_adam_tail: one control record, every optimizer given its lr slot."""
+        self._tail_on = True
+        if self._ctrl is None:
+            self._ctrl = ops.optim_ctrl(self.device)
+            # (allocated here, not at first use: the first use may be inside a graph capture, whose pool other captures reuse)
+            self._norm_work = torch.empty(ops.grad_norm_work([m._pcount for m in self.model.values()]), dtype=torch.float64,
+                                          device=self.device)
+        for j, o in enumerate(self.optimizers.values()):
+            o.configure(self._ctrl, j, use_ema=self.use_ema)
+        if self.lr_policy is not None and self.schedulers is None:
+            self.schedulers = {name: get_scheduler(o, self.lr_policy, **self._sched_kw) for name, o in self.optimizers.items()}
+
+    def reset_ema(self):
+        """Restart the shadows from the current weights (after weights were loaded into the networks by hand; checkpoint_dir and
+        load_snapshots need no such call)."""
+        self.ema_num_updates = 0
+        for name, o in self.optimizers.items():
+            if o.ema is not None:
+                o.ema.copy_(self._ema_stash[name] if self._ema_in else o.net._flat_data)
+                o.num_updates = 0
+
+    def _ema_omd(self) -> float:
+        """1 - decay of the NEXT EMA update (ExponentialMovingAverage.update's num_updates rule)."""
+        return 1.0 - ema_decay_at(self.ema_decay, self.ema_num_updates + 1 if self.ema_use_num_updates else None)
+
+    def write_optim_control(self):
+        """This step's learning rates and EMA decay into the control record: one launch, the values as launch arguments.  Issued by
+        optimize_all_params / optimize_params; a captured step cannot carry it (the arguments would be frozen), so
+        graph.CooperativeStepGraph calls it in front of every replay."""
+        ops.optim_control(self._ctrl, [o.param_groups[0]["lr"] for o in self.optimizers.values()], self.max_grad_norm or 0.0,
+                          self.skip_nonfinite, self._ema_omd() if self.use_ema else 0.0)
+
+    def _tail_norm(self, names):
+        if self.max_grad_norm is None and not self.skip_nonfinite:
+            return
+        if self._dp is not None:
+            for name in names:                   # the norm is over whole gradients: every range of the exchange has to be in
+                self._dp.wait(name)
+        grads = [self.model[n]._flat.grad for n in names]
+        ops.grad_norm(grads, self.grad_scale, self._ctrl, self._norm_work)
+
+    def set_lr(self, lr):
+        """One learning rate for every network, or {network name: lr}.  Switches the optimizer tail on (the rate then lives in the
+        device control record, so a captured step follows it too); takes effect with the next step."""
+        if not self._tail_on:
+            self._enable_tail()
+        for name, o in self.optimizers.items():
+            v = lr.get(name) if isinstance(lr, dict) else lr
+            if v is not None:
+                for g in o.param_groups:
+                    g["lr"] = float(v)
+
+    def scheduler_step(self, metric=None):
+        """Advance the learning-rate schedule by one epoch (the plateau policies need the epoch's loss as `metric`) -> the rates."""
+        if self.schedulers is not None:
+            for sch in self.schedulers.values():
+                sch.step(metric)
+        return {name: o.param_groups[0]["lr"] for name, o in self.optimizers.items()}
+
+    def optim_report(self):
+        """{'grad_norm', 'clip', 'skipped_steps'} of the last step from one small readback (synchronises: once per epoch, not per step)."""
+        if self._ctrl is None:
+            return {"grad_norm": None, "clip": 1.0, "skipped_steps": 0}
+        c = self._ctrl.tolist()
+        return {"grad_norm": c[_ffi.OPTIM_NORM], "clip": c[_ffi.OPTIM_CLIP], "skipped_steps": int(c[_ffi.OPTIM_SKIPPED])}
 
     def reset_all_optimizers(self):
         if self.optimizers is None:
@@ -230,12 +352,24 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
         return self.optimizers if model_name is None else self.optimizers[model_name]
 
     def optimize_all_params(self):
+        if self._tail_on:
+            if self._gstate is None:             # (captured step: the caller refreshes the record in front of every replay)
+                self.write_optim_control()
+            self._tail_norm(list(self.optimizers))
+            if self.use_ema:
+                self.ema_num_updates += 1
         for name, o in self.optimizers.items():
             if self._dp is not None:
                 self._dp.wait(name)              # this network's range of the gradient bucket (no-op if the exchange was already waited for)
             o.step(grad_scale=self.grad_scale, state=self._gstate)
 
     def optimize_params(self, model_name):
+        if self._tail_on:
+            if self._gstate is None:
+                self.write_optim_control()
+            self._tail_norm([model_name])        # clipping here is by the norm of this network alone
+            if self.use_ema:
+                self.ema_num_updates += 1
         if self._dp is not None:
             self._dp.wait(model_name)
         self.optimizers[model_name].step(grad_scale=self.grad_scale, state=self._gstate)

@@ -88,15 +88,43 @@ def train_step(segmentation_solver, clean_image_l, label_l, latent_DA, separate_
     return tuple(v.detach() for v in (seg_loss, image_recon_loss, gt_recon_loss, shape_recon_loss) + tuple(hard))
 
 
+TAIL_KEYS = ('lr_policy', 'lr_decay_iters', 'max_grad_norm', 'skip_nonfinite', 'use_ema', 'ema_decay')
+
+
+def configure_optim_tail(segmentation_solver, learning) -> bool:
+    """The optional optimizer-tail keys of experiment_opt['learning'] onto the solver -> is any feature on?  Keys that are absent leave
+    what the solver was built with."""
+    given = {k: learning[k] for k in TAIL_KEYS if k in learning}
+    s = segmentation_solver
+    if given:
+        s.max_grad_norm = given.get('max_grad_norm', s.max_grad_norm)
+        s.skip_nonfinite = bool(given.get('skip_nonfinite', s.skip_nonfinite))
+        s.use_ema = bool(given.get('use_ema', s.use_ema))
+        s.ema_decay = float(given.get('ema_decay', s.ema_decay))
+        if 'lr_policy' in given and given['lr_policy'] != s.lr_policy:
+            s.lr_policy, s.schedulers = given['lr_policy'], None
+        if 'lr_decay_iters' in given and given['lr_decay_iters'] != s._sched_kw['lr_decay_iters']:
+            s._sched_kw['lr_decay_iters'], s.schedulers = given['lr_decay_iters'], None      # (a new schedule starts from the current rates)
+        if s.max_grad_norm is not None or s.skip_nonfinite or s.use_ema or s.lr_policy is not None:
+            s._enable_tail()
+    return bool(getattr(s, '_tail_on', False))
+
+
 def train_network(segmentation_solver, train_loader, validate_loader, experiment_opt, model_dir, start_epoch=0, cooperative=False,
                   experiment_name='experiment', verbose=True):
     """:144-288.  experiment_opt: upstream's dict -- ['learning'] (n_epochs, max_iteration, latent_DA, separate_training), ['latent_DA']
     (mask_scope, 'image code', 'shape code'), ['output']['save_epoch_every_num_epochs'], ['segmentation_model']['network_type'].  The
     batch size and keep_orig_image_label_pair_for_training are the loaders' (DeviceBatchLoader(train_set, batch_size, keep_orig=True);
     validation: DeviceBatchLoader(val_set, batch_size, keep_orig=False, shuffle=False), each with a generator of its own).
-    -> {'score_list', 'best_score', 'losses': one {key: mean over the epoch's steps} per epoch, 'iterations'}."""
+    -> {'score_list', 'best_score', 'losses': one {key: mean over the epoch's steps} per epoch, 'iterations'}.
+    Optional keys of ['learning'] switch the solver's optimizer tail on (absent: nothing changes): lr_policy, lr_decay_iters,
+    max_grad_norm, skip_nonfinite, use_ema, ema_decay.  The schedule advances once per epoch after validation (the plateau policies get
+    the epoch's mean total loss); validation and the 'best' checkpoint then use the EMA weights; the result gains 'lr' and
+    'skipped_steps', one entry per epoch, read with the epoch's losses."""
     latent_DA, separate_training, image_cfg, seg_cfg = latent_da_configs(experiment_opt)
     prefix = experiment_opt['segmentation_model']['network_type']
+    tail_on = configure_optim_tail(segmentation_solver, experiment_opt['learning'])
+    lrs, skipped = [], []
     best_score = -10000
     stop_flag = False
     score_list, losses, iterations = [], [], 0
@@ -123,6 +151,9 @@ def train_network(segmentation_solver, train_loader, validate_loader, experiment
                     stop_flag = True
             means = (sums / max(g_count, 1)).tolist()                       # the epoch's one readback of losses
             losses.append(dict(zip(LOSS_KEYS + ['loss/total'], means)))
+            if tail_on:
+                skipped.append(segmentation_solver.optim_report()['skipped_steps'])      # (joins the epoch's readback)
+                lrs.append(next(iter(segmentation_solver.optimizers.values())).param_groups[0]['lr'])
             if verbose:
                 print('{} network: {} epoch {} training loss iter: {}, total  loss: {}'.format(experiment_name, prefix, i_epoch, g_count, means[-1]))
             curr_score, _ = eval_model(segmentation_solver, validate_loader)
@@ -132,10 +163,15 @@ def train_network(segmentation_solver, train_loader, validate_loader, experiment
                 segmentation_solver.save_model(model_dir, epoch_iter='best', model_prefix=prefix)
             if (i_epoch + 1) % experiment_opt['output']['save_epoch_every_num_epochs'] == 0 or i_epoch == 0:
                 segmentation_solver.save_model(model_dir, epoch_iter=i_epoch, model_prefix=prefix)
+            if tail_on:
+                segmentation_solver.scheduler_step(means[-1])
             if stop_flag:
                 break
     except Exception:
         if i_epoch > 0:
             segmentation_solver.save_snapshots(model_dir, epoch=i_epoch)
         raise
-    return {'score_list': score_list, 'best_score': best_score, 'losses': losses, 'iterations': iterations}
+    result = {'score_list': score_list, 'best_score': best_score, 'losses': losses, 'iterations': iterations}
+    if tail_on:
+        result.update(lr=lrs, skipped_steps=skipped)
+    return result

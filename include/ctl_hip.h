@@ -865,6 +865,55 @@ int ctl_accumulate(float* dst, const float* const* srcs, int32_t k, int64_t coun
 int ctl_adam_dev(float* p, const float* g, float* m, float* v, int64_t count, float lr, float beta1, float beta2,
                  float eps, const int64_t* state, float grad_scale, ctl_stream stream);
 
+/* ------------------------------------------------------------------------------------------------ optimizer tail
+ * Learning-rate schedules, global-norm clipping, a guard against a non-finite gradient and the EMA shadow of the weights, folded into
+ * the pass that already streams p, g, m, v once per step (upstream: ExponentialMovingAverage, medseg/models/model_util.py:21-101,
+ * get_scheduler 621-671; torch.nn.utils.clip_grad_norm_).  Opt-in: ctl_adam / ctl_adam_dev above are untouched.
+ *
+ * Control record: `double ctrl[CTL_OPTIM_CTRL_DOUBLES]` on the device, one per solver, for up to CTL_OPTIM_MAX_NETS networks.  fp32
+ * values are stored as the double of the fp32 value, so reading one back as float is exact.
+ *   host-written (ctl_optim_control)          device-written (ctl_grad_norm)
+ *   [CTL_OPTIM_LR + j]   lr of network j      [CTL_OPTIM_SUMSQ]    sum of g^2 over all buffers (fp64)
+ *   [CTL_OPTIM_MAX_NORM] 0 = no clipping      [CTL_OPTIM_NORM]     grad_scale * sqrt(sumsq)
+ *   [CTL_OPTIM_GUARD]    1 = skip a step      [CTL_OPTIM_CLIP]     factor on every gradient, 1 = none (also reset by ctl_optim_control)
+ *                        whose norm is not    [CTL_OPTIM_FINITE]   1 = the norm is finite (also reset to 1 by ctl_optim_control)
+ *                        finite               [CTL_OPTIM_SKIPPED]  running count of skipped steps; never reset by the library
+ *   [CTL_OPTIM_EMA_OMD]  1 - decay of this step
+ * Every other word is reserved and never written.  The caller zeroes the record once.
+ *
+ * ctl_optim_control: ONE launch; the values travel as launch arguments (`lr` is a HOST array of k floats), so the host may run any
+ *   number of steps ahead of the device.  Writes the host fields (lr of networks >= k: 0), clip = 1 and finite = 1; leaves the rest.
+ * ctl_grad_norm_work: doubles of workspace ctl_grad_norm needs for these counts (a HOST array): sum_j ceil(counts[j] / CTL_GRAD_NORM_CHUNK);
+ *   0 for a bad argument.
+ * ctl_grad_norm: two launches for all k flat gradient buffers (`grads`, `counts`: HOST arrays).  Pass 1: block b of buffer j sums g^2 in
+ *   fp64 over the fixed chunk [b CH, (b + 1) CH) into work[j][b]; CH = CTL_GRAD_NORM_CHUNK is a compile-time constant, so the grouping
+ *   of the sum depends on the counts alone, not on the grid or the alignment.  Pass 2: one wave adds the partials in a fixed order and
+ *   writes sumsq, norm = grad_scale * sqrt(sumsq), finite = isfinite(norm),
+ *   clip = (max_norm > 0 && finite) ? min(1, max_norm / (norm + 1e-6)) : 1 (fp64), skipped += (guard && !finite).
+ *   No atomics, no readback; the same bits on every call and in a graph replay.
+ * ctl_adam_tail: one launch per network.  Guard on and finite == 0: returns without writing.  Otherwise gi = (g * grad_scale) * clip
+ *   (clip == 1 changes no bit), then ctl_adam's arithmetic with lr = (float)ctrl[CTL_OPTIM_LR + net]; bias corrections from state[2]
+ *   as ctl_adam_dev when `state` is given, else from `step` as ctl_adam.  `ema` (nullable): s <- s - omd * (s - p_new) as three
+ *   separately rounded fp32 operations.  Reads p, g, m, v, s and writes p, m, v, s: 36 bytes per parameter. */
+#define CTL_OPTIM_CTRL_DOUBLES 32
+#define CTL_OPTIM_MAX_NETS 8
+#define CTL_OPTIM_LR 0
+#define CTL_OPTIM_MAX_NORM 8
+#define CTL_OPTIM_GUARD 9
+#define CTL_OPTIM_EMA_OMD 10
+#define CTL_OPTIM_SUMSQ 16
+#define CTL_OPTIM_NORM 17
+#define CTL_OPTIM_CLIP 18
+#define CTL_OPTIM_FINITE 19
+#define CTL_OPTIM_SKIPPED 20
+#define CTL_GRAD_NORM_CHUNK 16384
+int ctl_optim_control(double* ctrl, int32_t k, const float* lr, float max_norm, int32_t skip_nonfinite, float ema_omd, ctl_stream stream);
+size_t ctl_grad_norm_work(const int64_t* counts, int32_t k);
+int ctl_grad_norm(const float* const* grads, const int64_t* counts, int32_t k, float grad_scale, double* work, double* ctrl,
+                  ctl_stream stream);
+int ctl_adam_tail(float* p, const float* g, float* m, float* v, float* ema, int64_t count, float beta1, float beta2, float eps,
+                  const int64_t* state, int32_t step, float grad_scale, const double* ctrl, int32_t net, ctl_stream stream);
+
 /* ------------------------------------------------------------------------------------------------ plans
  * A plan is an array of ctl_op executed in order on one stream: one C call per network pass (the Python host builds
  * it once per (network, shape, mode)).  Tensor arguments are (slot, byte offset) pairs resolved against `bases`.

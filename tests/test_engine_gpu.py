@@ -238,8 +238,9 @@ def _network_eval_mode_vs_oracle(name, golden_sd, cfg=()):
         close(a, b, what=f"{name} eval output")
 
 
-def _solver(golden_sd):
-    s = AdvancedTripletReconSegmentationModel(use_gpu=True)
+def _solver(golden_sd, dtype=None):
+    """dtype: the solver's compute_dtype (None = fp32, today's tests; "bf16" = tests/test_bf16_forms_gpu.py)"""
+    s = AdvancedTripletReconSegmentationModel(use_gpu=True, compute_dtype=dtype)
     for k, m in s.model.items():
         m.load_state_dict(golden_sd[k])
     return s

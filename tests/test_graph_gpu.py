@@ -29,8 +29,9 @@ def dev(x):
     return x.contiguous(memory_format=torch.channels_last) if x.dim() == 4 else x.contiguous()
 
 
-def _solver(golden_sd):
-    s = AdvancedTripletReconSegmentationModel(use_gpu=True)
+def _solver(golden_sd, dtype=None):
+    """dtype: the solver's compute_dtype (None = fp32, today's tests; "bf16" = tests/test_bf16_forms_gpu.py)"""
+    s = AdvancedTripletReconSegmentationModel(use_gpu=True, compute_dtype=dtype)
     for k, m in s.model.items():
         m.load_state_dict(golden_sd[k])
     return s

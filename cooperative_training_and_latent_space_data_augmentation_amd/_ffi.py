@@ -32,6 +32,7 @@ DT_BF16, DT_X16, DT_Y16, DT_RES16, DT_X3 = 1, 2, 4, 8, 16
 PACK_X3 = 16                         # or-ed into the mode word of a pack record (CTL_PACK_X3)
 LOSS_WCE, LOSS_FOCAL, LOSS_DICE, LOSS_FG_DICE = 0, 1, 2, 3      # CTL_LOSS_* kinds of ctl_seg_loss_fwd / ctl_seg_loss_bwd
 DLOSS_BOUNDARY, DLOSS_HAUSDORFF_DT = 0, 1                       # CTL_DLOSS_* kinds of ctl_dist_loss_fwd / ctl_dist_loss_bwd
+CONS_KL, CONS_CE, CONS_WCE, CONS_MSE, CONS_DICE, CONS_CONTOUR = 1, 2, 4, 8, 16, 32    # CTL_CONS_* bits of ctl_consistency_fwd / _bwd (bit t = kind t)
 FIELD_D2, FIELD_SIGNED, FIELD_SQUARED = 0, 1, 2                 # CTL_FIELD_* forms of ctl_class_fields
 LABEL_U8, LABEL_I64 = 0, 1                                      # CTL_LABEL_* of ctl_class_fields
 TTA_LOGIT, TTA_PROB, TTA_MAX_VIEWS = 0, 1, 8                    # CTL_TTA_* of ctl_tta_merge
@@ -197,6 +198,11 @@ def _signatures() -> dict:
         "ctl_dist_loss_ws_doubles": (sz, [i32, i32, i64, i32]),
         "ctl_dist_loss_fwd": (int_, [i32, p, p, p, p, i32, i64, i32, p, p, p]),
         "ctl_dist_loss_bwd": (int_, [i32, p, p, p, p, p, i32, i64, i32, p, p]),
+        "ctl_consistency_ws_doubles": (sz, [i32] * 5),
+        "ctl_consistency_fwd": (int_, [i32] + [p] * 5 + [i32] * 5 + [p, p, p]),
+        "ctl_consistency_bwd": (int_, [i32] + [p] * 5 + [i32, p, p] + [i32] * 4 + [p, p]),
+        "ctl_avgpool_fwd": (int_, [p] + [i32] * 5 + [p, p]),
+        "ctl_avgpool_bwd": (int_, [p] + [i32] * 5 + [p, p]),
         "ctl_mse_fwd": (int_, [p, p, i64, f32, p, p, p]),
         "ctl_mse_bwd": (int_, [p, p, p, i64, f32, p, p]),
         "ctl_argmax_c": (int_, [p, p, i64, i32, p]),

@@ -234,6 +234,39 @@ class _DistSegLoss(torch.autograd.Function):
         return ops.dist_loss_bwd(logit, label, ctx.kind, g.float().contiguous(), field, pred), None, None, None
 
 
+class _ConsistencyLoss(torch.autograd.Function):
+    """The weighted sum of consistency losses between an output and a constant reference (consistency.py): one fused forward, whose
+    scratch carries 1/R and the Dice coefficient table to the backward."""
+
+    @staticmethod
+    def forward(ctx, output, reference, mask, kinds, class_weights, is_gt):
+        output, reference = _nhwc(output), _nhwc(reference)
+        loss, _, ws = ops.consistency_fwd(output, reference, kinds, class_weights, mask, is_gt)
+        ctx.save_for_backward(output, reference, ws, *(() if mask is None else (mask,)))
+        ctx.args = (dict(kinds), class_weights, is_gt)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        output, reference, ws = ctx.saved_tensors[:3]
+        mask = ctx.saved_tensors[3] if len(ctx.saved_tensors) > 3 else None
+        kinds, class_weights, is_gt = ctx.args
+        return ops.consistency_bwd(output, reference, kinds, g.float().contiguous(), ws, class_weights, mask, is_gt), None, None, None, None, None
+
+
+class _AvgPool(torch.autograd.Function):
+    """AvgPool2d(2^scale) of logits, window = stride, floor sizes."""
+
+    @staticmethod
+    def forward(ctx, x, scale):
+        ctx.scale, ctx.hw = scale, (x.shape[2], x.shape[3])
+        return ops.avgpool_fwd(_nhwc(x), scale)
+
+    @staticmethod
+    def backward(ctx, g):
+        return ops.avgpool_bwd(_nhwc(g), ctx.scale, ctx.hw), None
+
+
 class _ScaledMSE(torch.autograd.Function):
     """scale * mean((a-b)^2)"""
 
@@ -293,6 +326,33 @@ def segmentation_loss(logit, label, kind, class_weights=None, gamma=2.0, fields=
     if class_weights is not None:
         class_weights = tuple(float(v) for v in class_weights)
     return _PointwiseSegLoss.apply(logit, label, kind, class_weights, float(gamma))
+
+
+def consistency_loss(output, reference, kinds, class_weights=None, mask=None, is_gt=False):
+    """sum_name kinds[name] * L_name(output, reference) of the consistency losses of ops.CONSISTENCY_KINDS (consistency.py), differentiable
+    in `output`; the reference is a constant and must not require grad.  `kinds`: {name: weight}; `class_weights`: a host sequence of C
+    numbers ('weighted ce' only); `mask`: per pixel, [B,1,H,W] or [B,H,W], nonzero = 1."""
+    if not kinds:
+        raise ValueError("consistency_loss: `kinds` maps at least one name to its weight")
+    for name in kinds:
+        if name not in ops.CONSISTENCY_KINDS:
+            raise NotImplementedError(f"consistency loss {name!r} (one of {', '.join(ops.CONSISTENCY_KINDS)})")
+    if reference.requires_grad:
+        raise ValueError("the reference is a constant: detach it (no gradient reaches the reference)")
+    ops.require_gpu(output, reference, mask)
+    if class_weights is not None:
+        class_weights = tuple(float(v) for v in class_weights)
+    if mask is not None:
+        mask = (mask.detach() != 0).to(torch.uint8).contiguous()
+    return _ConsistencyLoss.apply(output, reference, mask, kinds, class_weights, bool(is_gt))
+
+
+def avg_pool(x, scale):
+    """AvgPool2d(2^scale) of [B,C,H,W] logits on the device, differentiable; scale 0 is the identity."""
+    if int(scale) == 0:
+        return x
+    ops.require_gpu(x)
+    return _AvgPool.apply(x, int(scale))
 
 
 def scaled_mse(a, b, scale=1.0):

@@ -362,6 +362,103 @@ def dist_loss_bwd(logit, label, kind, gout, field_a, field_b=None):
     return d
 
 
+# ---------------------------------------------------------------------------------------------- consistency losses
+# names of calc_segmentation_consistency (custom_loss.py:892-973) -> CTL_CONS_* bit; bit t is kind t, the order of `terms` and of the weights
+CONSISTENCY_KINDS = {"kl": _ffi.CONS_KL, "ce": _ffi.CONS_CE, "weighted ce": _ffi.CONS_WCE, "mse": _ffi.CONS_MSE, "Dice": _ffi.CONS_DICE,
+                     "contour": _ffi.CONS_CONTOUR}
+
+
+def _consistency_args(output, reference, kinds, class_weights, mask, who):
+    """(kind bits, weights, class weights, mask as uint8, n, h, w, c) of a {name: weight} mapping `kinds`; names and weights are checked
+    before the tensors are looked at."""
+    if not kinds:
+        raise ValueError(f"{who}: `kinds` maps at least one name to its weight")
+    for name in kinds:
+        if name not in CONSISTENCY_KINDS:
+            raise NotImplementedError(f"consistency loss {name!r} (one of {', '.join(CONSISTENCY_KINDS)})")
+    if "weighted ce" in kinds and class_weights is None:
+        raise ValueError("'weighted ce' must be given class weights")
+    require_gpu(output, reference, mask)
+    if output.dim() != 4 or output.dtype != torch.float32 or reference.dtype != torch.float32 or tuple(reference.shape) != tuple(output.shape):
+        raise ValueError(f"{who}: expected fp32 output and reference logits of one shape [B,C,H,W]")
+    if not (output.permute(0, 2, 3, 1).is_contiguous() and reference.permute(0, 2, 3, 1).is_contiguous()):
+        raise ValueError(f"{who}: output and reference must be NHWC in memory (channels_last)")
+    n, c, h, w = (int(v) for v in output.shape)
+    if "contour" in kinds and c < 2:
+        raise ValueError("'contour' needs at least 2 classes (it runs over the classes 1 .. C-1)")
+    bits, weights = 0, [0.0] * len(CONSISTENCY_KINDS)
+    for name, weight in kinds.items():
+        bits |= CONSISTENCY_KINDS[name]
+        weights[CONSISTENCY_KINDS[name].bit_length() - 1] = float(weight)
+    wts = None
+    if class_weights is not None and "weighted ce" in kinds:
+        vals = [float(v) for v in class_weights]
+        if len(vals) != c:
+            raise ValueError(f"each class must have a weight: expected {c} weights, got {len(vals)}")
+        wts = (C.c_double * c)(*vals)
+    if mask is not None:
+        if tuple(mask.shape) not in ((n, 1, h, w), (n, h, w)):
+            raise ValueError(f"{who}: the mask is per pixel, [{n},1,{h},{w}] or [{n},{h},{w}], got {tuple(mask.shape)}")
+        mask = mask if mask.dtype == torch.uint8 and mask.is_contiguous() else (mask != 0).to(torch.uint8).contiguous()
+    return bits, (C.c_double * len(weights))(*weights), wts, mask, n, h, w, c
+
+
+def consistency_fwd(output, reference, kinds, class_weights=None, mask=None, is_gt=False):
+    """(loss, terms, ws) of the {name: weight} mapping `kinds` (CONSISTENCY_KINDS): the 0-d weighted total, fp32 terms[6] in the order of
+    CONSISTENCY_KINDS (0 for a name that is not in `kinds`), and the scratch consistency_bwd reads.  `mask`: [B,1,H,W] or [B,H,W], any
+    dtype, nonzero = 1 (a contiguous uint8 mask is used as it is)."""
+    bits, weights, wts, mask, n, h, w, c = _consistency_args(output, reference, kinds, class_weights, mask, "consistency_fwd")
+    ws = torch.empty(max(1, lib.ctl_consistency_ws_doubles(bits, n, h, w, c)), dtype=torch.float64, device=output.device)
+    loss = torch.empty(1 + len(CONSISTENCY_KINDS), dtype=torch.float32, device=output.device)
+    call("ctl_consistency_fwd", bits, weights, wts, ptr(output), ptr(reference), ptr(mask), int(bool(is_gt)), n, h, w, c, ptr(ws), ptr(loss),
+         stream_ptr())
+    return loss[0], loss[1:], ws
+
+
+def consistency_bwd(output, reference, kinds, gout, ws, class_weights=None, mask=None, is_gt=False):
+    """gout (0-d fp32 device tensor) * d total / d output; `ws` is what consistency_fwd returned for the same arguments."""
+    bits, weights, wts, mask, n, h, w, c = _consistency_args(output, reference, kinds, class_weights, mask, "consistency_bwd")
+    require_gpu(gout, ws)
+    _arg(ws, torch.float64, (None,), "consistency_bwd", "ws", dense=True)
+    if ws.numel() < lib.ctl_consistency_ws_doubles(bits, n, h, w, c):
+        raise ValueError("consistency_bwd: `ws` is not the scratch of consistency_fwd for these arguments")
+    d = torch.empty_like(output)
+    call("ctl_consistency_bwd", bits, weights, wts, ptr(output), ptr(reference), ptr(mask), int(bool(is_gt)), ptr(gout), ptr(ws), n, h, w, c,
+         ptr(d), stream_ptr())
+    return d
+
+
+def _pool_args(x, scale, who):
+    require_gpu(x)
+    scale = int(scale)
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.permute(0, 2, 3, 1).is_contiguous():
+        raise ValueError(f"{who}: expected an fp32 [B,C,H,W] tensor that is NHWC in memory (channels_last)")
+    if not 1 <= scale <= 4:
+        raise ValueError(f"{who}: scale {scale} (1 .. 4)")
+    return scale, tuple(int(v) for v in x.shape)
+
+
+def avgpool_fwd(x: torch.Tensor, scale: int) -> torch.Tensor:
+    """AvgPool2d(2^scale) (window = stride, floor sizes) of fp32 NHWC logits: the fp64 window mean, rounded once."""
+    scale, (n, c, h, w) = _pool_args(x, scale, "avgpool_fwd")
+    if (h >> scale) < 1 or (w >> scale) < 1:
+        raise ValueError(f"avgpool_fwd: a {h}x{w} plane is smaller than the {1 << scale}x{1 << scale} window of scale {scale}")
+    y = empty_nhwc(n, c, h >> scale, w >> scale, x.device)
+    call("ctl_avgpool_fwd", ptr(x), n, h, w, c, scale, ptr(y), stream_ptr())
+    return y
+
+
+def avgpool_bwd(gy: torch.Tensor, scale: int, hw) -> torch.Tensor:
+    """The transpose of avgpool_fwd for an input plane hw = (H, W): gy * 4^-scale on every pixel of a window, zero where the floor drops."""
+    scale, (n, c, ho, wo) = _pool_args(gy, scale, "avgpool_bwd")
+    h, w = (int(v) for v in hw)
+    if (h >> scale, w >> scale) != (ho, wo):
+        raise ValueError(f"avgpool_bwd: a {h}x{w} plane pools to {h >> scale}x{w >> scale} at scale {scale}, the gradient is {ho}x{wo}")
+    gx = empty_nhwc(n, c, h, w, gy.device)
+    call("ctl_avgpool_bwd", ptr(gy), n, h, w, c, scale, ptr(gx), stream_ptr())
+    return gx
+
+
 def mse_fwd(a, b, scale):
     partial = torch.empty(_ffi.RED_BLOCKS, dtype=torch.float64, device=a.device)
     loss = torch.empty((), dtype=torch.float32, device=a.device)

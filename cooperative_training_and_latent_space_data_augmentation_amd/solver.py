@@ -550,6 +550,22 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
             y_0 = self._call(self.model["segmentation_decoder"], z_s, disable_track_bn_stats)
         return (z_i, z_s), y_0
 
+    def consistency_training(self, image, perturbed_image, target="stn", divergence_types=("kl",), divergence_weights=(1.0,), scales=(0,),
+                             class_weights=None, mask=None):
+        """Consistency loss for slices WITHOUT labels (no upstream counterpart; consistency.calc_segmentation_consistency): the fast
+        network's prediction on `perturbed_image` against a constant reference predicted from `image` -- its own prediction
+        (target="ftn") or the shape network's refinement of it (target="stn").  Eager; BatchNorm running statistics are left alone.
+        The caller runs backward() and optimize_params as after standard_training."""
+        from .consistency import calc_segmentation_consistency
+        if target not in ("stn", "ftn"):
+            raise ValueError(f"consistency_training: target {target!r} ('stn' or 'ftn')")
+        with torch.no_grad():
+            y_ref = self.fast_predict(image, disable_track_bn_stats=True)[1]
+            if target == "stn":
+                y_ref = self.recon_shape(y_ref, is_label_map=False, disable_track_bn_stats=True)
+        y = self.fast_predict(perturbed_image, disable_track_bn_stats=True)[1]
+        return calc_segmentation_consistency(y, y_ref.detach(), list(divergence_types), list(divergence_weights), class_weights, list(scales), mask)
+
     def decoder_inference(self, decoder, latent_code, eval=False, disable_track_bn_stats=False):
         """model.py:396-412."""
         state = decoder.training

@@ -356,6 +356,49 @@ int ctl_dist_loss_fwd(int32_t kind, const float* logit, const int64_t* label, co
                       int64_t hw, int32_t c, double* ws, float* loss, ctl_stream stream);
 int ctl_dist_loss_bwd(int32_t kind, const float* logit, const int64_t* label, const float* field_a, const float* field_b, const float* gout,
                       int32_t b, int64_t hw, int32_t c, float* dlogit, ctl_stream stream);
+/* Consistency losses (ctl_consist.hip): losses between two PREDICTIONS, medseg/models/custom_loss.py calc_segmentation_consistency :892-973 with
+ * kl_divergence :863-889, soft-target cross_entropy_2D :741-766, the softmax 'mse' :942-952, SoftDiceLoss with a 4-D target :356-396 and the
+ * Sobel contour_loss :784-860.  x = output logits, r = reference, both float NHWC [b][h][w][c], c in 1..16; mask uint8 [b][h][w] (nonzero = 1)
+ * or NULL.  q = softmax(x); p = softmax(r), or p = r when is_gt.  M = b h w, R = sum m (M without a mask), s = 0.01.  r is a constant.
+ *   CTL_CONS_KL       (1/M) sum_pix m sum_k p_k (log p_k - log q_k).  is_gt: upstream's rule, p_k = 1 where r_k != 0 else float(1e-8), with
+ *                     p_k log p_k = 0 resp. the float product 1e-8f * logf(1e-8f).  dlogit_j = (m/M)(S q_j - p_j), S = sum_k p_k.
+ *   CTL_CONS_CE       -(1/R) sum_pix m sum_k p_k log q_k;  R = 0: loss 0, gradient 0.
+ *   CTL_CONS_WCE      -(1/R) sum_pix m sum_k w'_k p_k log q_k, w' = w / sum(w) * c.  Both: dlogit_j = (m/R)(q_j sum_k w'_k p_k - w'_j p_j).
+ *   CTL_CONS_MSE      (1/M) sum_pix m sum_k (q_k - p_k)^2;  g_k = 2 m (q_k - p_k) / M.
+ *   CTL_CONS_DICE     1 - (sum_{b,k} 2I/U) / (b c), per (b,k): I = sum m q p + s, U = sum m q + sum m p + s;  g_k = -(m/(b c))(2 p_k/U - 2I/U^2).
+ *   CTL_CONS_CONTOUR  (1/(c-1)) sum_{k=1..c-1} 1/2 (1/M) sum_pix m (E_x^2 + E_y^2), c >= 2: with d = q - p, E_x / E_y are the 3x3 zero-padded
+ *                     cross-correlations of d_k with [[1,0,-1],[2,0,-2],[1,0,-1]] / [[1,2,1],[0,0,0],[-1,-2,-1]] (:823-841);
+ *                     g_k = (1/((c-1) M)) (S_x^T(m E_x) + S_y^T(m E_y))_k, g_0 = 0.
+ *   The kinds with a g: dlogit_j = q_j (g_j - sum_k q_k g_k).
+ * kinds: a non-empty set of CTL_CONS_* bits; bit t is kind t.  weights: HOST array of 6 doubles, entry t the weight of kind t (read for
+ * the selected kinds only).  class_weights: HOST array of c doubles, CTL_CONS_WCE only, else NULL allowed.
+ * ctl_consistency_fwd writes loss[7]: loss[0] = sum_t weights[t] term_t, loss[1 + t] = term_t (0 for a kind that is not selected); a term has
+ *   the same bits whichever other kinds are selected beside it.  Launches: one streaming pass over x, r and the mask for ANY set of the
+ *   first five kinds (fp64 block sums, the masked count among them), one tiled pass for CTL_CONS_CONTOUR (d of the classes 1..c-1 in LDS at
+ *   halo 1; tiles of 32x32 pixels up to 4 classes, 16x16 above), then one finalize block.
+ * ws: ctl_consistency_ws_doubles(kinds, b, h, w, c) doubles: the Dice coefficient table [b][c][2] (g_k = m (coef0 p_k + coef1); zeros
+ *   without CTL_CONS_DICE), a record of 8 doubles ([0] = 1/R or 0, [1] = R, the rest 0), then -- with one of the first five kinds -- the block
+ *   sums [b][ctl_seg_loss_blocks(b, h w)][5 + 3c] and -- with CTL_CONS_CONTOUR -- min(tiles, 2048) block sums.  Every double is written by the
+ *   forward; hand the forward's ws to the backward with the same kinds.
+ * ctl_consistency_bwd writes every element of dlogit = gout[0] * sum_t weights[t] dterm_t/dx (gout read on the device), q and p recomputed:
+ *   one streaming launch for the first five kinds together; the contour gradient is a SECOND, tiled launch (d at halo 2 and the masked
+ *   responses at halo 1 in LDS, the transposed stencil at the centre) that adds into dlogit -- it writes dlogit when it is the only kind.
+ * ctl_avgpool_fwd: AvgPool2d(2^scale) of float NHWC [b][h][w][c] -> [b][h >> scale][w >> scale][c], scale in 1..4: each window summed in a
+ *   fixed order in fp64, rounded once.  ctl_avgpool_bwd: gx = gy * 4^-scale on every pixel of a window, zero on the rows / columns the floor drops.
+ * No float atomics, no readback: the same bits on every call and in a graph replay.  Null pointers, an empty or unknown kind set, non-positive
+ * sizes, c outside 1..16 (contour: 2..16), more than 65535 samples, a tensor at or past 2 GiB, a weight that is not finite, class weights
+ * whose sum is not finite and positive, a scale outside 1..4 and a plane smaller than the window are refused with CTL_EINVAL before any
+ * launch; ctl_consistency_ws_doubles returns 0 for them. */
+enum { CTL_CONS_KL = 1, CTL_CONS_CE = 2, CTL_CONS_WCE = 4, CTL_CONS_MSE = 8, CTL_CONS_DICE = 16, CTL_CONS_CONTOUR = 32 };
+size_t ctl_consistency_ws_doubles(int32_t kinds, int32_t b, int32_t h, int32_t w, int32_t c);
+int ctl_consistency_fwd(int32_t kinds, const double* weights, const double* class_weights, const float* x, const float* r,
+                        const uint8_t* mask, int32_t is_gt, int32_t b, int32_t h, int32_t w, int32_t c, double* ws, float* loss,
+                        ctl_stream stream);
+int ctl_consistency_bwd(int32_t kinds, const double* weights, const double* class_weights, const float* x, const float* r,
+                        const uint8_t* mask, int32_t is_gt, const float* gout, const double* ws, int32_t b, int32_t h, int32_t w,
+                        int32_t c, float* dlogit, ctl_stream stream);
+int ctl_avgpool_fwd(const float* x, int32_t b, int32_t h, int32_t w, int32_t c, int32_t scale, float* y, ctl_stream stream);
+int ctl_avgpool_bwd(const float* gy, int32_t b, int32_t h, int32_t w, int32_t c, int32_t scale, float* gx, ctl_stream stream);
 /* loss = scale * mean((a-b)^2) (model.py:445-447: scale 0.5; util.py:216: scale 1); bwd: da = gout*2*scale*(a-b)/count */
 int ctl_mse_fwd(const float* a, const float* b, int64_t count, float scale, double* partial, float* loss,
                 ctl_stream stream);

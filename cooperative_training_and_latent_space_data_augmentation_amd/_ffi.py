@@ -33,6 +33,7 @@ PACK_X3 = 16                         # or-ed into the mode word of a pack record
 LOSS_WCE, LOSS_FOCAL, LOSS_DICE, LOSS_FG_DICE = 0, 1, 2, 3      # CTL_LOSS_* kinds of ctl_seg_loss_fwd / ctl_seg_loss_bwd
 DLOSS_BOUNDARY, DLOSS_HAUSDORFF_DT = 0, 1                       # CTL_DLOSS_* kinds of ctl_dist_loss_fwd / ctl_dist_loss_bwd
 CONS_KL, CONS_CE, CONS_WCE, CONS_MSE, CONS_DICE, CONS_CONTOUR = 1, 2, 4, 8, 16, 32    # CTL_CONS_* bits of ctl_consistency_fwd / _bwd (bit t = kind t)
+RECON_MSE, RECON_L1, RECON_SMOOTH_L1, RECON_NCC, RECON_LNCC = 1, 2, 4, 8, 16                 # CTL_RECON_* bits of ctl_recon_loss_fwd / _bwd (bit k = kind k)
 FIELD_D2, FIELD_SIGNED, FIELD_SQUARED = 0, 1, 2                 # CTL_FIELD_* forms of ctl_class_fields
 LABEL_U8, LABEL_I64 = 0, 1                                      # CTL_LABEL_* of ctl_class_fields
 TTA_LOGIT, TTA_PROB, TTA_MAX_VIEWS = 0, 1, 8                    # CTL_TTA_* of ctl_tta_merge
@@ -203,6 +204,9 @@ def _signatures() -> dict:
         "ctl_consistency_bwd": (int_, [i32] + [p] * 5 + [i32, p, p] + [i32] * 4 + [p, p]),
         "ctl_avgpool_fwd": (int_, [p] + [i32] * 5 + [p, p]),
         "ctl_avgpool_bwd": (int_, [p] + [i32] * 5 + [p, p]),
+        "ctl_recon_ws_doubles": (sz, [i32] * 6),
+        "ctl_recon_loss_fwd": (int_, [i32] + [p] * 4 + [i32] * 5 + [f64] + [i32] * 3 + [p, p, p]),
+        "ctl_recon_loss_bwd": (int_, [i32] + [p] * 4 + [i32, p, p] + [i32] * 4 + [f64] + [i32] * 3 + [p, p]),
         "ctl_mse_fwd": (int_, [p, p, i64, f32, p, p, p]),
         "ctl_mse_bwd": (int_, [p, p, p, i64, f32, p, p]),
         "ctl_argmax_c": (int_, [p, p, i64, i32, p]),

@@ -267,6 +267,26 @@ class _AvgPool(torch.autograd.Function):
         return ops.avgpool_bwd(_nhwc(g), ctx.scale, ctx.hw), None
 
 
+class _ImageSimilarityLoss(torch.autograd.Function):
+    """The weighted sum of image-similarity losses between a prediction and a constant target (recon.py): one fused forward, whose
+    scratch carries the 'ncc' table and the 'lncc' coefficient maps to the one backward launch."""
+
+    @staticmethod
+    def forward(ctx, x, t, mask, kinds, params):
+        x, t = _nhwc(x), _nhwc(t)
+        loss, _, ws = ops.recon_loss_fwd(x, t, kinds, mask, **params)
+        ctx.save_for_backward(x, t, ws, *(() if mask is None else (mask,)))
+        ctx.args = (dict(kinds), dict(params))
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        x, t, ws = ctx.saved_tensors[:3]
+        mask = ctx.saved_tensors[3] if len(ctx.saved_tensors) > 3 else None
+        kinds, params = ctx.args
+        return ops.recon_loss_bwd(x, t, kinds, g.float().contiguous(), ws, mask, **params), None, None, None, None
+
+
 class _ScaledMSE(torch.autograd.Function):
     """scale * mean((a-b)^2)"""
 
@@ -353,6 +373,23 @@ def avg_pool(x, scale):
         return x
     ops.require_gpu(x)
     return _AvgPool.apply(x, int(scale))
+
+
+def image_similarity_loss(x, t, kinds, weights=None, mask=None, *, beta=1.0 / 9, win=9, zero_mean=True, reduction="mean"):
+    """sum_name weight_name * L_name(x, t) of the image-similarity losses of ops.RECON_KINDS (recon.py), differentiable in the prediction
+    `x`; the target `t` ([B,C,H,W] or [1,C,H,W]) is a constant and must not require grad.  `kinds`: a name, names with `weights`, or
+    {name: weight}; `mask`: per pixel, [B,1,H,W] or [B,H,W], nonzero = 1, multiplies x and t."""
+    from .recon import parse_kinds
+    kinds = parse_kinds(kinds, weights)
+    if t.requires_grad:
+        raise ValueError("the target is a constant: detach it (no gradient reaches the target)")
+    if reduction == "none":
+        raise NotImplementedError("reduction='none' is not offered on the device ('mean' or 'sum')")
+    ops.require_gpu(x, t, mask)
+    if mask is not None:
+        mask = (mask.detach() != 0).to(torch.uint8).contiguous()
+    params = dict(beta=float(beta), win=win, zero_mean=bool(zero_mean), reduction=reduction)
+    return _ImageSimilarityLoss.apply(x, t, mask, kinds, params)
 
 
 def scaled_mse(a, b, scale=1.0):

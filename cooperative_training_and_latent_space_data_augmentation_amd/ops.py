@@ -459,6 +459,74 @@ def avgpool_bwd(gy: torch.Tensor, scale: int, hw) -> torch.Tensor:
     return gx
 
 
+# ---------------------------------------------------------------------------------------------- image-similarity (reconstruction) losses
+# names of recon.py (custom_loss.py:310-318, :514-571, :574-661) -> CTL_RECON_* bit; bit k is kind k, the order of `terms` and of the weights
+RECON_KINDS = {"mse": _ffi.RECON_MSE, "l1": _ffi.RECON_L1, "smooth l1": _ffi.RECON_SMOOTH_L1, "ncc": _ffi.RECON_NCC, "lncc": _ffi.RECON_LNCC}
+
+
+def _recon_args(x, t, kinds, mask, beta, win, reduction, who):
+    """(kind bits, weights, mask as uint8, t's batch, n, h, w, c, reduce_sum) of a {name: weight} mapping `kinds`; names, weights and
+    parameters are checked before the tensors are looked at."""
+    if not kinds:
+        raise ValueError(f"{who}: `kinds` maps at least one name to its weight")
+    for name in kinds:
+        if name not in RECON_KINDS:
+            raise NotImplementedError(f"image-similarity loss {name!r} (one of {', '.join(RECON_KINDS)})")
+    if reduction == "none":
+        raise NotImplementedError(f"{who}: reduction='none' is not offered on the device ('mean' or 'sum')")
+    if reduction not in ("mean", "sum"):
+        raise ValueError(f"{who}: reduction {reduction!r} ('mean' or 'sum')")
+    if "smooth l1" in kinds and not float(beta) > 0.0:
+        raise ValueError(f"{who}: beta = {beta} (smooth l1 needs beta > 0)")
+    if "lncc" in kinds and (int(win) != win or win % 2 == 0 or not 3 <= win <= 15):
+        raise ValueError(f"{who}: win = {win} (odd, 3 .. 15)")
+    require_gpu(x, t, mask)
+    if x.dim() != 4 or t.dim() != 4 or x.dtype != torch.float32 or t.dtype != torch.float32 or tuple(t.shape[1:]) != tuple(x.shape[1:]) \
+            or t.shape[0] not in (1, x.shape[0]):
+        raise ValueError(f"{who}: expected an fp32 prediction [B,C,H,W] and an fp32 target of that shape or [1,C,H,W]")
+    if not (x.permute(0, 2, 3, 1).is_contiguous() and t.permute(0, 2, 3, 1).is_contiguous()):
+        raise ValueError(f"{who}: prediction and target must be NHWC in memory (channels_last)")
+    n, c, h, w = (int(v) for v in x.shape)
+    if c > 16:
+        raise ValueError(f"{who}: {c} channels (1 .. 16)")
+    if "lncc" in kinds and (win > h or win > w):
+        raise ValueError(f"{who}: win = {win} is larger than the {h}x{w} plane")
+    bits, weights = 0, [0.0] * len(RECON_KINDS)
+    for name, weight in kinds.items():
+        bits |= RECON_KINDS[name]
+        weights[RECON_KINDS[name].bit_length() - 1] = float(weight)
+    if mask is not None:
+        if tuple(mask.shape) not in ((n, 1, h, w), (n, h, w)):
+            raise ValueError(f"{who}: the mask is per pixel, [{n},1,{h},{w}] or [{n},{h},{w}], got {tuple(mask.shape)}")
+        mask = mask if mask.dtype == torch.uint8 and mask.is_contiguous() else (mask != 0).to(torch.uint8).contiguous()
+    return bits, (C.c_double * len(weights))(*weights), mask, int(t.shape[0]), n, h, w, c, int(reduction == "sum")
+
+
+def recon_loss_fwd(x, t, kinds, mask=None, beta=1.0 / 9, win=9, zero_mean=True, reduction="mean"):
+    """(loss, terms, ws) of the {name: weight} mapping `kinds` (RECON_KINDS) between the prediction x and the constant target t ([B,C,H,W]
+    or [1,C,H,W]): the 0-d weighted total, fp32 terms[5] in the order of RECON_KINDS (0 for a name that is not in `kinds`), and the
+    scratch recon_loss_bwd reads.  `mask`: [B,1,H,W] or [B,H,W], any dtype, nonzero = 1 (a contiguous uint8 mask is used as it is)."""
+    bits, weights, mask, tb, n, h, w, c, rsum = _recon_args(x, t, kinds, mask, beta, win, reduction, "recon_loss_fwd")
+    ws = torch.empty(max(1, lib.ctl_recon_ws_doubles(bits, n, h, w, c, int(win))), dtype=torch.float64, device=x.device)
+    loss = torch.empty(1 + len(RECON_KINDS), dtype=torch.float32, device=x.device)
+    call("ctl_recon_loss_fwd", bits, weights, ptr(x), ptr(t), ptr(mask), tb, n, h, w, c, float(beta), int(win), int(bool(zero_mean)), rsum,
+         ptr(ws), ptr(loss), stream_ptr())
+    return loss[0], loss[1:], ws
+
+
+def recon_loss_bwd(x, t, kinds, gout, ws, mask=None, beta=1.0 / 9, win=9, zero_mean=True, reduction="mean"):
+    """gout (0-d fp32 device tensor) * d total / d x; `ws` is what recon_loss_fwd returned for the same arguments."""
+    bits, weights, mask, tb, n, h, w, c, rsum = _recon_args(x, t, kinds, mask, beta, win, reduction, "recon_loss_bwd")
+    require_gpu(gout, ws)
+    _arg(ws, torch.float64, (None,), "recon_loss_bwd", "ws", dense=True)
+    if ws.numel() < lib.ctl_recon_ws_doubles(bits, n, h, w, c, int(win)):
+        raise ValueError("recon_loss_bwd: `ws` is not the scratch of recon_loss_fwd for these arguments")
+    d = torch.empty_like(x)
+    call("ctl_recon_loss_bwd", bits, weights, ptr(x), ptr(t), ptr(mask), tb, ptr(gout), ptr(ws), n, h, w, c, float(beta), int(win),
+         int(bool(zero_mean)), rsum, ptr(d), stream_ptr())
+    return d
+
+
 def mse_fwd(a, b, scale):
     partial = torch.empty(_ffi.RED_BLOCKS, dtype=torch.float64, device=a.device)
     loss = torch.empty((), dtype=torch.float32, device=a.device)

@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import _ffi, ops
-from .autograd import LabelFields, cross_entropy_2D, net_apply, scaled_mse, segmentation_loss, softmax_t, split_halves
+from .autograd import LabelFields, cross_entropy_2D, image_similarity_loss, net_apply, scaled_mse, segmentation_loss, softmax_t, split_halves
 from .losses import DIST_LOSS_NAMES, parse_loss_type
 from .metrics import runningScore
 from .model_util import (_disable_tracking_bn_stats, _draw_seed, get_scheduler, mask_latent_code_channel_wise,
@@ -78,13 +78,17 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
                  decoder_dropout=None, num_classes=4, n_iter=1, checkpoint_dir=None, use_gpu=True, debug=False, *, compute_dtype=None,
                  seg_loss_type="cross entropy", class_weights=None, max_grad_norm=None, skip_nonfinite=False, use_ema=False,
                  ema_decay=0.999, ema_use_num_updates=True, lr_policy=None, lr_decay_iters=5, epoch_count=None, niter=None,
-                 niter_decay=None):
+                 niter_decay=None, recon_loss_type="mse", recon_loss_params=None):
         """`compute_dtype` (keyword-only, no upstream counterpart): "fp32" = the reference's arithmetic (default, BASELINE config 2);
         "bf16" = BASELINE config 3: network-internal activations / gradients stored as bf16, convolutions on bf16 MFMA with fp32
         accumulation, fp32 master weights / BatchNorm statistics / losses.
         `seg_loss_type` / `class_weights` (keyword-only, no upstream counterpart): the `loss_type` and `class_weights` of every
         `basic_loss_fn` call that compares logits with `label_l` in standard_training and hard_example_training -- a name or a
         {name: weight} mapping.  The saliency loss of hard_example_generation (`loss_name` of the DA configs) is not affected.
+        `recon_loss_type` / `recon_loss_params` (keyword-only, no upstream counterpart): the image reconstruction term of standard_training
+        and of the hard-example pass -- a name of recon.RECON_NAMES or a {name: weight} mapping, with `recon_loss_params` (beta, win,
+        zero_mean, reduction) as recon.image_similarity takes them.  The whole term keeps upstream's factor 0.5 (model.py:445), whatever
+        the kinds.  The default "mse" without parameters is today's scaled_mse call, launch for launch.
         The optimizer tail (keyword-only, all off by default; DESIGN.md "Optimizer tail"): `max_grad_norm` clips the global gradient
         norm over the five networks as clip_grad_norm_(solver.parameters(), max_norm) would; `skip_nonfinite` leaves weights, moments and
         shadows untouched in a step whose gradient norm is not finite; `use_ema` / `ema_decay` / `ema_use_num_updates` keep upstream's
@@ -100,6 +104,7 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
         _, class_weights = parse_loss_type(seg_loss_type, class_weights, num_classes)      # (NotImplementedError / ValueError likewise)
         self.seg_loss_type = dict(seg_loss_type) if isinstance(seg_loss_type, dict) else seg_loss_type
         self.class_weights = class_weights
+        self.recon_loss_type, self.recon_loss_params, self._recon_kinds = self._parse_recon(recon_loss_type, recon_loss_params, image_ch)
         self._fields_cache = None        # [(label tensor, its version, LabelFields)] of the running cooperative_step
         self.network_type, self.image_ch, self.checkpoint_dir = network_type, image_ch, checkpoint_dir
         self.num_classes, self.learning_rate, self.n_iter = num_classes, learning_rate, n_iter
@@ -459,6 +464,27 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
             torch.cuda.current_stream().wait_stream(self._side)
             self._side_pending = False
 
+    @staticmethod
+    def _parse_recon(recon_loss_type, recon_loss_params, image_ch):
+        """(type, params, {name: 0.5 * weight} or None for the default scaled_mse call); NotImplementedError / ValueError as recon.py raises."""
+        from .recon import check_params, parse_kinds
+        params = dict(recon_loss_params or {})
+        unknown = sorted(set(params) - {"beta", "win", "zero_mean", "reduction"})
+        if unknown:
+            raise ValueError(f"recon_loss_params: unknown parameter(s) {unknown} (beta, win, zero_mean, reduction)")
+        kinds = parse_kinds(recon_loss_type)
+        check_params(kinds, (1, image_ch, 15, 15), params.get("beta", 1.0 / 9), params.get("win", 9), params.get("reduction", "mean"))
+        rtype = dict(recon_loss_type) if isinstance(recon_loss_type, dict) else recon_loss_type
+        if recon_loss_type == "mse" and not params:
+            return rtype, params, None
+        return rtype, params, {name: 0.5 * weight for name, weight in kinds.items()}
+
+    def _recon_term(self, image_recon, clean_image_l):
+        """0.5 * the configured image-similarity loss (model.py:445-447); the default is the scaled_mse launch pair."""
+        if self._recon_kinds is None:
+            return scaled_mse(image_recon, clean_image_l, 0.5)
+        return image_similarity_loss(image_recon, clean_image_l.detach(), self._recon_kinds, **self.recon_loss_params)
+
     def _image_recon_loss(self, z_i, clean_image_l, disable_track_bn_stats=False):
         def work():
             ev = getattr(self, "_img_std_done", None)
@@ -467,7 +493,7 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
                 # chains (standard pass on the main chain, this pass on the side chain; upstream's decode_image always tracks,
                 # model.py:444).  The standard pass comes first in the reference: make that an event, not a matter of timing.
                 torch.cuda.current_stream().wait_event(ev)
-            return scaled_mse(self.decode_image(z_i, disable_track_bn_stats), clean_image_l, 0.5)
+            return self._recon_term(self.decode_image(z_i, disable_track_bn_stats), clean_image_l)
         return self._fork_side(work, z_i, clean_image_l)
 
     def encode_shape(self, segmentation, is_label_map=False, disable_track_bn_stats=False, temperature=2):
@@ -627,7 +653,7 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
         standard_supervised_loss = self._seg_loss(y_0, label_l.detach(), fields)
         if image_recon_loss is None and _pre is None:
             image_recon = self.decode_image(z_i)                       # always BN mode A, as upstream (model.py:444)
-            image_recon_loss = scaled_mse(image_recon, clean_image_l, 0.5)
+            image_recon_loss = self._recon_term(image_recon, clean_image_l)
         y_0_new = y_0.detach() if separate_training else y_0
         if compute_gt_recon and self.group_stn_passes and not disable_track_bn_stats and self.training:
             # the two STN passes are independent and share the BatchNorm mode: one grouped pass (same order: gt, then p)
@@ -852,7 +878,7 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
         early_seg = _mu.REUSE_SALIENCY_FORWARD and scheme_of(seg_cfg, seg_override) not in (None, "dropout")
         image_recon_loss = y_0 = None
         if early_img:
-            image_recon_loss = scaled_mse(self.decode_image(z_i), clean_image_l, 0.5)
+            image_recon_loss = self._recon_term(self.decode_image(z_i), clean_image_l)
             self._img_std_done = torch.cuda.Event()
             self._img_std_done.record(cur)
             side.wait_event(self._img_std_done)         # the image saliency pass reads these activations, and replays this pass' running update
@@ -889,7 +915,7 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
         if image_recon_loss is None:
             if img_saliency_done is not None:
                 cur.wait_event(img_saliency_done)
-            image_recon_loss = scaled_mse(self.decode_image(z_i), clean_image_l, 0.5)
+            image_recon_loss = self._recon_term(self.decode_image(z_i), clean_image_l)
             self._img_std_done = torch.cuda.Event()
             self._img_std_done.record(cur)           # the hard phase's image-decoder pass (side chain) waits for this one
         # CPU issue order (one Python thread feeds both streams): the side chain's long part is issued BEFORE the main chain's

@@ -399,6 +399,49 @@ int ctl_consistency_bwd(int32_t kinds, const double* weights, const double* clas
                         int32_t c, float* dlogit, ctl_stream stream);
 int ctl_avgpool_fwd(const float* x, int32_t b, int32_t h, int32_t w, int32_t c, int32_t scale, float* y, ctl_stream stream);
 int ctl_avgpool_bwd(const float* gy, int32_t b, int32_t h, int32_t w, int32_t c, int32_t scale, float* gx, ctl_stream stream);
+/* Image-similarity (reconstruction) losses (ctl_recon.hip) between a prediction x and a constant target t, medseg/models/custom_loss.py:
+ * smooth_l1_loss :310-318, CustomNormalizedCrossCorrelationLoss :514-571, CustomLocalNormalizedCrossCorrelationLoss :574-661, next to
+ * 'mse' and 'l1'.  x float NHWC [b][h][w][c], c in 1..16; t the same, or one sample [1][h][w][c] broadcast over the batch (t_batch = 1:
+ * upstream's single template, :536); mask uint8 [b][h][w] (nonzero = 1) or NULL multiplies both first: J = m x, I = m t.  N = b c h w;
+ * reduce_sum = 0: the means below, 1: the sums (every 1/N, 1/b below becomes 1; CTL_RECON_LNCC: 1 - c * sum of the scores).
+ *   CTL_RECON_MSE        (1/N) sum (J - I)^2;  dJ = 2 (J - I) / N.
+ *   CTL_RECON_L1         (1/N) sum |J - I|;  dJ = sign(J - I) / N, 0 where they are equal.
+ *   CTL_RECON_SMOOTH_L1  (1/N) sum (n < beta ? 0.5 n^2 / beta : n - 0.5 beta), n = |J - I| (:313-315);  dJ = (n < beta ? (J - I) / beta : sign) / N.
+ *   CTL_RECON_NCC        1 - (1/b) sum_b s_b, s_b = <a, u> / (max(|a|, 1e-6) max(|u|, 1e-6)) over the c h w elements of a sample, with
+ *                        a = J - mean_hw J, u = I - mean_hw I per sample and channel when zero_mean (:545-549), else a = J, u = I (the
+ *                        clamped norms of torch's CosineSimilarity(dim=1, eps=1e-6), :556);  dJ = -(1/b)(u / (Na Nu) - [|a| > eps] <a,u> a / (Na^3 Nu)).
+ *   CTL_RECON_LNCC       1 - (1/(b h w)) sum_p score_p (:608-661): the five sums I, J, I^2, J^2, I J over the win x win window (zero padding
+ *                        win / 2) AND all c channels, A = win^2, uI = I_sum / A, uJ = J_sum / A, cross = IJ_sum - uJ I_sum - uI J_sum +
+ *                        uI uJ A, I_var = I2_sum - 2 uI I_sum + uI^2 A (J_var alike), score = cross / (sqrt(I_var) sqrt(J_var) + 1e-6).
+ *                        A variance <= 2^-40 (its sum of squares) counts as exactly 0 (and its b_p as 0).  dJ_q = -(1/(b h w)) (I_q Sa -
+ *                        J_q Sb + Sc) with Sa, Sb, Sc the window sums of a_p = 1 / D_p, b_p = cross_p sqrt(I_var_p) / (D_p^2 sqrt(J_var_p))
+ *                        and b_p uJ_p - a_p uI_p.  win odd, 3..15, win <= h, win <= w.
+ * kinds: a non-empty set of CTL_RECON_* bits; bit k is kind k.  weights: HOST array of 5 doubles, entry k the weight of kind k (read for the
+ * selected kinds only).  beta is read with CTL_RECON_SMOOTH_L1, win with CTL_RECON_LNCC, zero_mean with CTL_RECON_NCC.
+ * ctl_recon_loss_fwd writes loss[6]: loss[0] = sum_k weights[k] term_k, loss[1 + k] = term_k (0 for a kind that is not selected); a term has
+ *   the same bits whichever other kinds are selected beside it.  Launches: one streaming pass over x, t and the mask for ANY set of the
+ *   first four kinds (ordered fp64 block sums: the three point-wise sums and, per channel, sum x, t, x^2, t^2, x t), one tiled pass for
+ *   CTL_RECON_LNCC (16x16 pixel tiles, the channel-summed I, J, I^2, J^2, I J of the tile plus a halo of win / 2 in LDS as fp64, separable
+ *   row-then-column window sums; it leaves the maps a_p, b_p, b_p uJ_p - a_p uI_p in ws), then one finalize block.
+ * ws: ctl_recon_ws_doubles(kinds, b, h, w, c, win) doubles, every one written by the forward: per sample (1 / (Na Nu), [|a| > eps] <a,u> /
+ *   (Na^3 Nu)) [b][2], the subtracted means [b][c][2], the channel sums [b][c][5] (zeros without CTL_RECON_NCC), then -- with one of the first
+ *   four kinds -- the block sums [b][ctl_seg_loss_blocks(b, h w)][3 + 5c] and -- with CTL_RECON_LNCC -- min(tiles, 2048) block sums and the
+ *   three maps [b][h][w][3].  Hand the forward's ws to the backward with the same arguments.
+ * ctl_recon_loss_bwd writes every element of dx = gout[0] * sum_k weights[k] dterm_k/dx (gout read on the device) in ONE launch, formed in
+ *   fp64 and rounded once: a streaming launch for the first four kinds; with CTL_RECON_LNCC a tiled launch that stages the three maps
+ *   with a halo of win / 2, takes their window sums and adds the point-wise kinds' gradient in the same thread.  dx is exactly 0 where the mask is 0.
+ * No float atomics, no readback: the same bits on every call and in a graph replay.  Null pointers, an empty or unknown kind set,
+ * non-positive sizes, c outside 1..16, more than 65535 samples, t_batch other than 1 or b, tensors of 2^31 elements or more, a weight that
+ * is not finite, beta <= 0, win even or outside 3..15, win > h or win > w are refused with CTL_EINVAL before any launch;
+ * ctl_recon_ws_doubles returns 0 for them. */
+enum { CTL_RECON_MSE = 1, CTL_RECON_L1 = 2, CTL_RECON_SMOOTH_L1 = 4, CTL_RECON_NCC = 8, CTL_RECON_LNCC = 16 };
+size_t ctl_recon_ws_doubles(int32_t kinds, int32_t b, int32_t h, int32_t w, int32_t c, int32_t win);
+int ctl_recon_loss_fwd(int32_t kinds, const double* weights, const float* x, const float* t, const uint8_t* mask, int32_t t_batch, int32_t b,
+                       int32_t h, int32_t w, int32_t c, double beta, int32_t win, int32_t zero_mean, int32_t reduce_sum, double* ws,
+                       float* loss, ctl_stream stream);
+int ctl_recon_loss_bwd(int32_t kinds, const double* weights, const float* x, const float* t, const uint8_t* mask, int32_t t_batch,
+                       const float* gout, const double* ws, int32_t b, int32_t h, int32_t w, int32_t c, double beta, int32_t win,
+                       int32_t zero_mean, int32_t reduce_sum, float* dx, ctl_stream stream);
 /* loss = scale * mean((a-b)^2) (model.py:445-447: scale 0.5; util.py:216: scale 1); bwd: da = gout*2*scale*(a-b)/count */
 int ctl_mse_fwd(const float* a, const float* b, int64_t count, float scale, double* partial, float* loss,
                 ctl_stream stream);

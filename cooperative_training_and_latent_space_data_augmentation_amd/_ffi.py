@@ -34,6 +34,7 @@ LOSS_WCE, LOSS_FOCAL, LOSS_DICE, LOSS_FG_DICE = 0, 1, 2, 3      # CTL_LOSS_* kin
 DLOSS_BOUNDARY, DLOSS_HAUSDORFF_DT = 0, 1                       # CTL_DLOSS_* kinds of ctl_dist_loss_fwd / ctl_dist_loss_bwd
 CONS_KL, CONS_CE, CONS_WCE, CONS_MSE, CONS_DICE, CONS_CONTOUR = 1, 2, 4, 8, 16, 32    # CTL_CONS_* bits of ctl_consistency_fwd / _bwd (bit t = kind t)
 RECON_MSE, RECON_L1, RECON_SMOOTH_L1, RECON_NCC, RECON_LNCC = 1, 2, 4, 8, 16                 # CTL_RECON_* bits of ctl_recon_loss_fwd / _bwd (bit k = kind k)
+ADV_L2, ADV_RMS, ADV_LINF = 0, 1, 2                             # CTL_ADV_* norms of ctl_adv_unit_scale
 FIELD_D2, FIELD_SIGNED, FIELD_SQUARED = 0, 1, 2                 # CTL_FIELD_* forms of ctl_class_fields
 LABEL_U8, LABEL_I64 = 0, 1                                      # CTL_LABEL_* of ctl_class_fields
 TTA_LOGIT, TTA_PROB, TTA_MAX_VIEWS = 0, 1, 8                    # CTL_TTA_* of ctl_tta_merge
@@ -207,6 +208,11 @@ def _signatures() -> dict:
         "ctl_recon_ws_doubles": (sz, [i32] * 6),
         "ctl_recon_loss_fwd": (int_, [i32] + [p] * 4 + [i32] * 5 + [f64] + [i32] * 3 + [p, p, p]),
         "ctl_recon_loss_bwd": (int_, [i32] + [p] * 4 + [i32, p, p] + [i32] * 4 + [f64] + [i32] * 3 + [p, p]),
+        "ctl_adv_bias_ws_bytes": (sz, [i32] * 4),
+        "ctl_adv_bias_fwd": (int_, [p, p] + [i32] * 7 + [p, p, p]),
+        "ctl_adv_bias_bwd": (int_, [p, p, p] + [i32] * 7 + [p, sz, p, p, p]),
+        "ctl_adv_unit_scale_ws_bytes": (sz, [i32, i64]),
+        "ctl_adv_unit_scale": (int_, [p, i32, i64, i32, f64, p, sz, p, p]),
         "ctl_mse_fwd": (int_, [p, p, i64, f32, p, p, p]),
         "ctl_mse_bwd": (int_, [p, p, p, i64, f32, p, p]),
         "ctl_argmax_c": (int_, [p, p, i64, i32, p]),

@@ -287,6 +287,23 @@ class _ImageSimilarityLoss(torch.autograd.Function):
         return ops.recon_loss_bwd(x, t, kinds, g.float().contiguous(), ws, mask, **params), None, None, None, None
 
 
+class _AdvBiasField(torch.autograd.Function):
+    """x * exp(S(theta)) (adversarial.py): one forward launch; the backward recomputes the field and gives dtheta and dx in two."""
+
+    @staticmethod
+    def forward(ctx, x, theta, spacing):
+        x, theta = _nhwc(x), theta.float().contiguous()
+        ctx.save_for_backward(x, theta)
+        ctx.spacing = spacing
+        return ops.adv_bias_fwd(x, theta, spacing)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, theta = ctx.saved_tensors
+        dtheta, dx = ops.adv_bias_bwd(_nhwc(g), x, theta, ctx.spacing, need_dx=ctx.needs_input_grad[0])
+        return dx, (dtheta if ctx.needs_input_grad[1] else None), None
+
+
 class _ScaledMSE(torch.autograd.Function):
     """scale * mean((a-b)^2)"""
 
@@ -390,6 +407,21 @@ def image_similarity_loss(x, t, kinds, weights=None, mask=None, *, beta=1.0 / 9,
         mask = (mask.detach() != 0).to(torch.uint8).contiguous()
     params = dict(beta=float(beta), win=win, zero_mean=bool(zero_mean), reduction=reduction)
     return _ImageSimilarityLoss.apply(x, t, mask, kinds, params)
+
+
+def adv_bias_field(x, theta, spacing):
+    """The image x [N,C,H,W] times the multiplicative bias field of the log-space control grid theta [N,gh,gw] (ops.adv_bias_grid),
+    differentiable in both."""
+    ops.require_gpu(x, theta)
+    return _AdvBiasField.apply(x, theta, int(spacing))
+
+
+def adv_unit_scale(g, scale, norm="l2"):
+    """ops.adv_unit_scale of a detached g: the bounded step of a gradient.  It has no backward (it is used under no_grad)."""
+    g = g.detach().float()
+    if not (g.is_contiguous() or (g.dim() == 4 and g.is_contiguous(memory_format=torch.channels_last))):
+        g = g.contiguous()
+    return ops.adv_unit_scale(g, scale, norm)
 
 
 def scaled_mse(a, b, scale=1.0):

@@ -527,6 +527,68 @@ def recon_loss_bwd(x, t, kinds, gout, ws, mask=None, beta=1.0 / 9, win=9, zero_m
     return d
 
 
+# ---------------------------------------------------------------------------------------------- adversarial input augmentation
+ADV_NORMS = {"l2": _ffi.ADV_L2, "rms": _ffi.ADV_RMS, "linf": _ffi.ADV_LINF}      # names of adversarial.unit_scale_host -> CTL_ADV_*
+
+
+def adv_bias_grid(h: int, w: int, spacing: int):
+    """(gh, gw) of the control grid of an h x w plane at integer spacing >= 2: (h - 1) // s + 4, (w - 1) // s + 4."""
+    from .adversarial import bias_grid
+    return bias_grid(h, w, spacing)
+
+
+def _adv_bias_args(x, theta, spacing, who):
+    """(n, h, w, c, s, gh, gw) of an fp32 image [N,C,H,W] (NHWC in memory) and its fp32 control grid [N,gh,gw]"""
+    adv_bias_grid(1, 1, spacing)                     # the spacing is checked before the tensors are looked at
+    require_gpu(x, theta)
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.permute(0, 2, 3, 1).is_contiguous():
+        raise ValueError(f"{who}: expected an fp32 image [N,C,H,W] that is NHWC in memory (channels_last)")
+    n, c, h, w = (int(v) for v in x.shape)
+    gh, gw = adv_bias_grid(h, w, spacing)
+    _arg(theta, torch.float32, (n, gh, gw), who, "theta", dense=True)
+    return n, h, w, c, int(spacing), gh, gw
+
+
+def adv_bias_fwd(x, theta, spacing, with_field=False):
+    """x * exp(S(theta)) with S the cubic B-spline field of the control grid `theta` [N,gh,gw] (log space, adv_bias_grid); one launch.
+    with_field: (x', f) with the field f [N,H,W] as well."""
+    n, h, w, c, s, gh, gw = _adv_bias_args(x, theta, spacing, "adv_bias_fwd")
+    y = torch.empty_like(x)
+    f = torch.empty((n, h, w), dtype=torch.float32, device=x.device) if with_field else None
+    call("ctl_adv_bias_fwd", ptr(x), ptr(theta), n, h, w, c, s, gh, gw, ptr(y), ptr(f), stream_ptr())
+    return (y, f) if with_field else y
+
+
+def adv_bias_bwd(g, x, theta, spacing, need_dx=True):
+    """(dtheta [N,gh,gw], dx or None) of adv_bias_fwd for the gradient g at its output; two launches."""
+    n, h, w, c, s, gh, gw = _adv_bias_args(x, theta, spacing, "adv_bias_bwd")
+    require_gpu(g)
+    if g.dtype != torch.float32 or tuple(g.shape) != tuple(x.shape) or not g.permute(0, 2, 3, 1).is_contiguous():
+        raise ValueError("adv_bias_bwd: the gradient must be an fp32 tensor of the image's shape, NHWC in memory")
+    ws, _ = _workspace("ctl_adv_bias_ws_bytes", n, h, w, s, device=x.device)
+    dtheta = torch.empty_like(theta)
+    dx = torch.empty_like(x) if need_dx else None
+    call("ctl_adv_bias_bwd", ptr(g), ptr(x), ptr(theta), n, h, w, c, s, gh, gw, ptr(ws), ws.numel(), ptr(dtheta), ptr(dx), stream_ptr())
+    return dtheta, dx
+
+
+def adv_unit_scale(g, scale, norm="l2"):
+    """Per sample (the first axis) scale * g / norm(g), norm one of ADV_NORMS; a sample whose norm is 0 or not finite gives zeros.  Two
+    launches; the result keeps g's shape and memory format."""
+    if norm not in ADV_NORMS:
+        raise ValueError(f"adv_unit_scale: norm {norm!r} (one of {', '.join(ADV_NORMS)})")
+    require_gpu(g)
+    dense = g.is_contiguous() or (g.dim() == 4 and g.is_contiguous(memory_format=torch.channels_last))
+    if g.dtype != torch.float32 or g.dim() < 1 or g.numel() == 0 or not dense:
+        raise ValueError(f"adv_unit_scale: expected a dense, non-empty fp32 tensor with the samples on the first axis, got {g.dtype} {tuple(g.shape)}")
+    n = int(g.shape[0])
+    m = g.numel() // n
+    ws, _ = _workspace("ctl_adv_unit_scale_ws_bytes", n, m, device=g.device)
+    out = torch.empty_like(g)
+    call("ctl_adv_unit_scale", ptr(g), n, m, ADV_NORMS[norm], float(scale), ptr(ws), ws.numel(), ptr(out), stream_ptr())
+    return out
+
+
 def mse_fwd(a, b, scale):
     partial = torch.empty(_ffi.RED_BLOCKS, dtype=torch.float64, device=a.device)
     loss = torch.empty((), dtype=torch.float32, device=a.device)

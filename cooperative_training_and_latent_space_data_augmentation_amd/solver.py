@@ -592,6 +592,31 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
         y = self.fast_predict(perturbed_image, disable_track_bn_stats=True)[1]
         return calc_segmentation_consistency(y, y_ref.detach(), list(divergence_types), list(divergence_weights), class_weights, list(scales), mask)
 
+    def adversarial_example_generation(self, image, label=None, kind="bias", seed=0, **params):
+        """(x_adv, {name: parameters}) of the input-space adversarial baselines (no upstream counterpart; adversarial.generate): `kind`
+        'bias' (a multiplicative bias field), 'noise' (additive noise) or ("bias", "noise") (the bias first); `params`: the
+        constructor arguments of adversarial.AdvBias / AdvNoise -- for a chain one mapping per name, bias={...}, noise={...}.  The
+        objective is the 'kl' consistency with the clean prediction or, with `label`, the solver's segmentation loss.  Eager, train()
+        mode only; requires_grad flags, gradients and BatchNorm running buffers are left as they were."""
+        from .adversarial import generate, make_chain
+        chain = make_chain(kind, **params)
+        x_adv, ps = generate(self, image, label, chain, seed)
+        return x_adv, {t.kind: p for t, p in zip(chain, ps)}
+
+    def adversarial_training(self, image, label=None, kind="bias", target="stn", divergence_types=("kl",), divergence_weights=(1.0,),
+                             scales=(0,), class_weights=None, mask=None, seed=0, **params):
+        """adversarial_example_generation followed by consistency_training(image, x_adv, ...): the consistency loss and, with `label`,
+        (consistency loss, segmentation loss of the fast network on x_adv).  The caller runs backward() and optimize_params as after
+        consistency_training."""
+        if target not in ("stn", "ftn"):
+            raise ValueError(f"adversarial_training: target {target!r} ('stn' or 'ftn')")
+        x_adv, _ = self.adversarial_example_generation(image, label, kind, seed, **params)
+        loss = self.consistency_training(image, x_adv, target, divergence_types, divergence_weights, scales, class_weights, mask)
+        if label is None:
+            return loss
+        y = self.fast_predict(x_adv, disable_track_bn_stats=True)[1]
+        return loss, self._seg_loss(y, label, self._label_fields(label))
+
     def decoder_inference(self, decoder, latent_code, eval=False, disable_track_bn_stats=False):
         """model.py:396-412."""
         state = decoder.training

@@ -442,6 +442,37 @@ int ctl_recon_loss_fwd(int32_t kinds, const double* weights, const float* x, con
 int ctl_recon_loss_bwd(int32_t kinds, const double* weights, const float* x, const float* t, const uint8_t* mask, int32_t t_batch,
                        const float* gout, const double* ws, int32_t b, int32_t h, int32_t w, int32_t c, double beta, int32_t win,
                        int32_t zero_mean, int32_t reduce_sum, float* dx, ctl_stream stream);
+/* Adversarial input augmentation (ctl_adv.hip; adversarial.py holds the float64 statement; a project addition, no upstream counterpart).
+ * Bias field: x float NHWC [n][h][w][c], c in 1..16, planes up to 2048 x 2048, n in 1..65535; integer control-point spacing s >= 2; theta
+ * float [n][gh][gw] in log space with gh = (h - 1) / s + 4, gw = (w - 1) / s + 4 (integer division).  For pixel row y: i = y / s,
+ * t = (y - i s) / s, columns alike; S(y, x) = sum_{a,b = 0..3} B_a(t_y) B_b(t_x) theta[i_y + a][i_x + b] with the uniform cubic B-spline
+ * basis B0 = (1 - t)^3 / 6, B1 = (3 t^3 - 6 t^2 + 4) / 6, B2 = (-3 t^3 + 3 t^2 + 3 t + 1) / 6, B3 = t^3 / 6 (the approximating spline, no
+ * prefilter: the weights are non-negative and sum to 1, |S| <= max |theta|); f = exp(S); x' = x f, the same field for every channel.
+ * ctl_adv_bias_fwd writes every element of y = x' and, unless f is NULL, of f [n][h][w] in ONE launch: the 16-term sum and exp in fp64, f
+ *   rounded to fp32 once, x' the fp64 product rounded once.  y (and f) must not overlap x: in place is refused.
+ * ctl_adv_bias_bwd, given g = dL/dx': dtheta [n][gh][gw] = My^T (f sum_c g_c x_c) Mx with M the [h][gh] / [w][gw] weight matrices above,
+ *   and, unless dx is NULL, dx = g f (rounded once from fp64).  TWO launches, separable: one block per image row recomputes f, keeps
+ *   q = f sum_c g_c x_c of the row in LDS as fp64 and leaves sum_x Mx[x][b] q[x] for every control column b in ws ([n][gw][h] doubles,
+ *   ctl_adv_bias_ws_bytes; 8-byte aligned); one wave per control point then sums My[y][a] times those over the rows of its support.
+ *   Every dtheta element is an ordered fp64 sum (lanes stride the support, then the xor butterfly) rounded once; a control point with an
+ *   empty support gets exactly 0.
+ * Unit step: g float [n][m], m in 1 .. 16 * 2048 * 2048; per sample out = scale g / norm(g) with norm CTL_ADV_L2 sqrt(sum g^2), CTL_ADV_RMS
+ *   sqrt(sum g^2 / m), CTL_ADV_LINF max |g|; a sample whose norm is 0 or not finite gives zeros.  TWO launches: ordered fp64 partials over
+ *   fixed chunks of 16384 elements (the result does not depend on the grid) in ws (ctl_adv_unit_scale_ws_bytes), then every block combines
+ *   its sample's chunks in order and writes its elements, each formed in fp64 and rounded once.  out must not overlap g.
+ * No float atomics, no readback: the same bits on every call, at every alignment and in a graph replay.  s < 2, a grid that disagrees
+ * with h, w and s, n outside 1..65535, a plane edge above 2048, c outside 1..16, n h w c of 2^31 or more, an unknown norm, a scale that is
+ * not finite, null required pointers, an undersized or misaligned workspace and overlapping outputs are refused with CTL_EINVAL before any
+ * launch; the size queries return 0 for sizes the entries refuse. */
+enum { CTL_ADV_L2 = 0, CTL_ADV_RMS = 1, CTL_ADV_LINF = 2 };
+size_t ctl_adv_bias_ws_bytes(int32_t n, int32_t h, int32_t w, int32_t s);
+int ctl_adv_bias_fwd(const float* x, const float* theta, int32_t n, int32_t h, int32_t w, int32_t c, int32_t s, int32_t gh, int32_t gw,
+                     float* y, float* f, ctl_stream stream);
+int ctl_adv_bias_bwd(const float* g, const float* x, const float* theta, int32_t n, int32_t h, int32_t w, int32_t c, int32_t s, int32_t gh,
+                     int32_t gw, void* ws, size_t ws_bytes, float* dtheta, float* dx, ctl_stream stream);
+size_t ctl_adv_unit_scale_ws_bytes(int32_t n, int64_t m);
+int ctl_adv_unit_scale(const float* g, int32_t n, int64_t m, int32_t norm, double scale, void* ws, size_t ws_bytes, float* out,
+                       ctl_stream stream);
 /* loss = scale * mean((a-b)^2) (model.py:445-447: scale 0.5; util.py:216: scale 1); bwd: da = gout*2*scale*(a-b)/count */
 int ctl_mse_fwd(const float* a, const float* b, int64_t count, float scale, double* partial, float* loss,
                 ctl_stream stream);

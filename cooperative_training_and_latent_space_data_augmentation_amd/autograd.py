@@ -365,6 +365,11 @@ def segmentation_loss(logit, label, kind, class_weights=None, gamma=2.0, fields=
     return _PointwiseSegLoss.apply(logit, label, kind, class_weights, float(gamma))
 
 
+def _mask_u8(mask):
+    """A mask of any dtype as a contiguous uint8 constant, nonzero = 1 (None stays None): what the loss Functions save and the kernels read."""
+    return None if mask is None else (mask.detach() != 0).to(torch.uint8).contiguous()
+
+
 def consistency_loss(output, reference, kinds, class_weights=None, mask=None, is_gt=False):
     """sum_name kinds[name] * L_name(output, reference) of the consistency losses of ops.CONSISTENCY_KINDS (consistency.py), differentiable
     in `output`; the reference is a constant and must not require grad.  `kinds`: {name: weight}; `class_weights`: a host sequence of C
@@ -379,8 +384,7 @@ def consistency_loss(output, reference, kinds, class_weights=None, mask=None, is
     ops.require_gpu(output, reference, mask)
     if class_weights is not None:
         class_weights = tuple(float(v) for v in class_weights)
-    if mask is not None:
-        mask = (mask.detach() != 0).to(torch.uint8).contiguous()
+    mask = _mask_u8(mask)
     return _ConsistencyLoss.apply(output, reference, mask, kinds, class_weights, bool(is_gt))
 
 
@@ -403,8 +407,7 @@ def image_similarity_loss(x, t, kinds, weights=None, mask=None, *, beta=1.0 / 9,
     if reduction == "none":
         raise NotImplementedError("reduction='none' is not offered on the device ('mean' or 'sum')")
     ops.require_gpu(x, t, mask)
-    if mask is not None:
-        mask = (mask.detach() != 0).to(torch.uint8).contiguous()
+    mask = _mask_u8(mask)
     params = dict(beta=float(beta), win=win, zero_mean=bool(zero_mean), reduction=reduction)
     return _ImageSimilarityLoss.apply(x, t, mask, kinds, params)
 

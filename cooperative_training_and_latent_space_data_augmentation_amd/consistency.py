@@ -31,7 +31,7 @@ from __future__ import annotations
 import torch
 import torch.nn.functional as F
 
-from .losses import SMOOTH, normalised_weights
+from .losses import SMOOTH, check_mask, mask01, normalised_weights
 
 CONSISTENCY_NAMES = ("kl", "ce", "weighted ce", "mse", "Dice", "contour")
 MAX_SCALE = 4
@@ -68,21 +68,12 @@ def check_pair(output, reference, mask=None):
         raise ValueError(f"expected output and reference logits of one shape [B,C,H,W], got {tuple(output.shape)} and {tuple(reference.shape)}")
     if reference.requires_grad:
         raise ValueError("the reference is a constant: detach it (no gradient reaches the reference)")
-    b, _, h, w = output.shape
-    if mask is not None and tuple(mask.shape) not in ((b, 1, h, w), (b, h, w)):
-        raise ValueError(f"the mask is per pixel: [{b},1,{h},{w}] or [{b},{h},{w}], got {tuple(mask.shape)}")
+    check_mask(mask, output.shape)
 
 
 def check_plane(h, w, scale):
     if (h >> scale) < 1 or (w >> scale) < 1:
         raise ValueError(f"a {h}x{w} plane is smaller than the {1 << scale}x{1 << scale} window of scale {scale}")
-
-
-def _mask01(mask, shape, dtype, device):
-    b, _, h, w = shape
-    if mask is None:
-        return torch.ones((b, 1, h, w), dtype=dtype, device=device)
-    return (mask.detach().reshape(b, 1, h, w) != 0).to(device=device, dtype=dtype)
 
 
 def _pad_shifts(d):
@@ -173,7 +164,7 @@ def consistency_and_grad(output, reference, divergence_types=("kl", "contour"), 
     check_pair(output, reference, mask)
     x, r = output.detach().double().cpu(), reference.detach().double().cpu()
     terms, wn, scales = parse_consistency(divergence_types, divergence_weights, class_weights, scales, mask, x.shape[1])
-    m = _mask01(None if mask is None else mask.cpu(), x.shape, torch.float64, "cpu")
+    m = mask01(None if mask is None else mask.cpu(), x.shape, torch.float64, "cpu")
     loss, grad = torch.zeros((), dtype=torch.float64), torch.zeros_like(x)
     for s in scales:
         xs, rs = pool(x, s), pool(r, s)
@@ -222,7 +213,7 @@ def _one_torch(x, r, name, wn, m, is_gt):
 def _consistency_torch(output, reference, terms, wn, scales, mask, is_gt):
     x = output if output.is_floating_point() else output.float()
     r = reference.detach().to(x.dtype)
-    m = _mask01(mask, x.shape, x.dtype, x.device)
+    m = mask01(mask, x.shape, x.dtype, x.device)
     total = 0.0
     for s in scales:
         xs, rs = pool(x, s), pool(r, s)

@@ -9,11 +9,9 @@
 // dL_t/dx of the point-wise / Dice kinds with both softmaxes recomputed in registers; the contour gradient is a second, tiled launch that
 // ADDS into dlogit (it writes dlogit when 'contour' is the only kind).  Sums are two-stage and ordered: no float atomics, nothing is read
 // back, the same bits on every call and in a graph replay.
-#include <cmath>
-#include "ctl_device.h"
+#include "ctl_rows.h"
 
-#define EB 256               // threads per block
-#define MAXC 16
+#define EB CTL_ROW_THREADS   // threads per block
 #define CONS_NK 6            // kinds
 #define CONS_PW (CTL_CONS_KL | CTL_CONS_CE | CTL_CONS_WCE | CTL_CONS_MSE | CTL_CONS_DICE)
 #define CONS_ALL (CONS_PW | CTL_CONS_CONTOUR)
@@ -22,38 +20,15 @@
 #define CONS_SCAL 8          // doubles of the scalar record: [0] = 1/R (0 where R = 0), [1] = R
 #define CONS_PW_SCALARS 5    // per-block sums in front of the per-class ones: count, kl, ce, weighted ce, mse
 
-struct cons_wc { double v[MAXC]; };       // normalised class weights of 'weighted ce' (ones otherwise), a launch argument
+struct cons_wc { double v[CTL_ROW_MAXC]; };    // normalised class weights of 'weighted ce' (ones otherwise), a launch argument
 struct cons_wk { double v[CONS_NK]; };    // weight of each kind (0 where the kind is not selected)
 
-// Channel rows, as ctl_loss.hip has them.  CT = 4: one 16-byte load / store per pixel; CT = 0: runtime channel count, loops unrolled over
-// MAXC with the tail switched off.  The arithmetic and its order are the same in both; contraction is off throughout.
-template <int CT> __device__ __forceinline__ void crow_load(const float* __restrict__ base, int64_t i, int c, float* v) {
-    if (CT == 4) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(base + i * 4);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < MAXC; ++k) if (k < c) v[k] = base[i * c + k];
-    }
-}
-template <int CT> __device__ __forceinline__ void crow_store(float* __restrict__ base, int64_t i, int c, const float* v) {
-    if (CT == 4) {
-        *reinterpret_cast<f32x4*>(base + i * 4) = f32x4{v[0], v[1], v[2], v[3]};
-    } else {
-#pragma unroll
-        for (int k = 0; k < MAXC; ++k) if (k < c) base[i * c + k] = v[k];
-    }
-}
-// v <- softmax(v) = exp(v - max) * (1 / sum), fp32; returns log of the partition sum, max + log(sum) in fp64 (log softmax_k = x_k - it)
+// v <- softmax(v) = exp(v - max) * (1 / sum), fp32 (a reciprocal and a product, as ctl_loss.hip forms it; ctl_uncert.hip divides); returns log of the partition sum, max + log(sum) in fp64 (log softmax_k = x_k - it)
 template <int CT> __device__ __forceinline__ double crow_softmax(float* v, int c) {
 #pragma clang fp contract(off)
-    constexpr int NC = CT ? CT : MAXC;
-    float m = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < NC; ++k) if (k < c) m = fmaxf(m, v[k]);
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < NC; ++k) if (k < c) { v[k] = expf(v[k] - m); s += v[k]; }
+    constexpr int NC = CT ? CT : CTL_ROW_MAXC;
+    float s;
+    const float m = ctl_row_exp<CT>(v, c, s);
     const float r = 1.f / s;
 #pragma unroll
     for (int k = 0; k < NC; ++k) if (k < c) v[k] = v[k] * r;
@@ -68,8 +43,8 @@ __global__ __launch_bounds__(EB) void cons_pw_partial_kernel(const float* __rest
                                                               const uint8_t* __restrict__ mask, int64_t hw, int c_rt, int kinds, int is_gt,
                                                               cons_wc wc, double p8, double p8logp8, double* __restrict__ partial) {
 #pragma clang fp contract(off)
-    constexpr int NC = CT ? CT : MAXC;
-    constexpr int NV = CONS_PW_SCALARS + 3 * MAXC;
+    constexpr int NC = CT ? CT : CTL_ROW_MAXC;
+    constexpr int NV = CONS_PW_SCALARS + 3 * CTL_ROW_MAXC;
     __shared__ double sm[EB / 64][NV];
     const int c = CT ? CT : c_rt;
     const int64_t b = blockIdx.y;
@@ -86,8 +61,8 @@ __global__ __launch_bounds__(EB) void cons_pw_partial_kernel(const float* __rest
     for (int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x; i < hw; i += stride) {
         if (mk && mk[i] == 0) continue;
         float q[NC], p[NC], xv[NC], rv[NC];
-        crow_load<CT>(x, i, c, q);
-        crow_load<CT>(r, i, c, p);
+        ctl_row_load<CT>(x, i, c, q);
+        ctl_row_load<CT>(r, i, c, p);
 #pragma unroll
         for (int k = 0; k < NC; ++k) if (k < c) { xv[k] = q[k]; rv[k] = p[k]; }
         const double lzx = crow_softmax<CT>(q, c);
@@ -115,13 +90,8 @@ __global__ __launch_bounds__(EB) void cons_pw_partial_kernel(const float* __rest
         const double a = wave_sum_double(si[k]), u = wave_sum_double(sq[k]), t = wave_sum_double(sp[k]);
         if (first) { sm[wv][CONS_PW_SCALARS + 3 * k] = a; sm[wv][CONS_PW_SCALARS + 3 * k + 1] = u; sm[wv][CONS_PW_SCALARS + 3 * k + 2] = t; }
     }
-    __syncthreads();
     const int nv = CONS_PW_SCALARS + 3 * c;
-    if ((int)threadIdx.x < nv) {
-        double a = 0.0;
-        for (int i = 0; i < EB / 64; ++i) a += sm[i][threadIdx.x];
-        partial[(b * gridDim.x + blockIdx.x) * nv + threadIdx.x] = a;
-    }
+    CTL_BLOCK_ROWS_STORE(sm, EB / 64, nv, partial + (b * gridDim.x + blockIdx.x) * nv);
 }
 
 // ------------------------------------------------------------------------------------------------ contour, forward
@@ -134,10 +104,10 @@ template <int CT>
 __device__ __forceinline__ void cons_store_d(const float* __restrict__ xo, const float* __restrict__ xr, int64_t pix, int c, int is_gt,
                                              float* __restrict__ dst, int plane, int at) {
 #pragma clang fp contract(off)
-    constexpr int NC = CT ? CT : MAXC;
+    constexpr int NC = CT ? CT : CTL_ROW_MAXC;
     float q[NC], p[NC];
-    crow_load<CT>(xo, pix, c, q);
-    crow_load<CT>(xr, pix, c, p);
+    ctl_row_load<CT>(xo, pix, c, q);
+    ctl_row_load<CT>(xr, pix, c, p);
     crow_softmax<CT>(q, c);
     if (!is_gt) crow_softmax<CT>(p, c);
 #pragma unroll
@@ -217,7 +187,7 @@ __global__ __launch_bounds__(EB) void cons_finalize_kernel(const double* __restr
                 si += e[0]; sq += e[1]; sp += e[2];
             }
         }
-        for (int o = 8; o > 0; o >>= 1) { si += __shfl_xor(si, o); sq += __shfl_xor(sq, o); sp += __shfl_xor(sp, o); }
+        CTL_GROUP16_SUM3(si, sq, sp);
         if (ok && lane == 0) {
             const double I = si + smooth, U = sq + sp + smooth;
             coef[(int64_t)it * 2] = dice ? -(2.0 / U) / div : 0.0;
@@ -266,7 +236,7 @@ __global__ __launch_bounds__(EB) void cons_pw_bwd_kernel(const float* __restrict
                                                           int kinds, int is_gt, cons_wc wc, cons_wk wk, double p8, double pixels,
                                                           float* __restrict__ dlogit) {
 #pragma clang fp contract(off)
-    constexpr int NC = CT ? CT : MAXC;
+    constexpr int NC = CT ? CT : CTL_ROW_MAXC;
     const int c = CT ? CT : c_rt;
     const int64_t b = blockIdx.y;
     const float* __restrict__ x = xo + b * hw * c;
@@ -291,12 +261,12 @@ __global__ __launch_bounds__(EB) void cons_pw_bwd_kernel(const float* __restrict
         if (mk && mk[i] == 0) {
 #pragma unroll
             for (int k = 0; k < NC; ++k) q[k] = 0.f;
-            crow_store<CT>(dx, i, c, q);
+            ctl_row_store<CT>(dx, i, c, q);
             continue;
         }
         float rv[NC];
-        crow_load<CT>(x, i, c, q);
-        crow_load<CT>(r, i, c, p);
+        ctl_row_load<CT>(x, i, c, q);
+        ctl_row_load<CT>(r, i, c, p);
 #pragma unroll
         for (int k = 0; k < NC; ++k) if (k < c) rv[k] = p[k];
         crow_softmax<CT>(q, c);
@@ -319,7 +289,7 @@ __global__ __launch_bounds__(EB) void cons_pw_bwd_kernel(const float* __restrict
             const double v = qd * (g[k] * S - dot) + a_kl * (skl * qd - pk) + a_ce * (qd * sp - pd) + a_wce * (qd * swp - wc.v[k] * pd);
             q[k] = (float)(go * v);
         }
-        crow_store<CT>(dx, i, c, q);
+        ctl_row_store<CT>(dx, i, c, q);
     }
 }
 
@@ -333,7 +303,7 @@ __global__ __launch_bounds__(EB) void cons_contour_bwd_kernel(const float* __res
                                                                int w, int c_rt, int is_gt, int tiles_y, int tiles_x, double coef, int accumulate,
                                                                float* __restrict__ dlogit) {
 #pragma clang fp contract(off)
-    constexpr int NC = CT ? CT : MAXC;
+    constexpr int NC = CT ? CT : CTL_ROW_MAXC;
     constexpr int HD = T + 4, HE = T + 2;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int c = CT ? CT : c_rt;
@@ -371,7 +341,7 @@ __global__ __launch_bounds__(EB) void cons_contour_bwd_kernel(const float* __res
             if (gy >= h || gx >= w) continue;
             const int64_t pix = (s * h + gy) * w + gx;
             float q[NC];
-            crow_load<CT>(xo, pix, c, q);
+            ctl_row_load<CT>(xo, pix, c, q);
             crow_softmax<CT>(q, c);
             double g[NC], S = (double)q[0], dot = 0.0;
             g[0] = 0.0;
@@ -390,13 +360,13 @@ __global__ __launch_bounds__(EB) void cons_contour_bwd_kernel(const float* __res
                 dot += (double)q[k] * g[k];
             }
             float o[NC];
-            if (accumulate) crow_load<CT>(dlogit, pix, c, o);
+            if (accumulate) ctl_row_load<CT>(dlogit, pix, c, o);
 #pragma unroll
             for (int k = 0; k < NC; ++k) if (k < c) {
                 const float v = (float)(go * ((double)q[k] * (g[k] * S - dot)));
                 o[k] = accumulate ? o[k] + v : v;
             }
-            crow_store<CT>(dlogit, pix, c, o);
+            ctl_row_store<CT>(dlogit, pix, c, o);
         }
         __syncthreads();
     }
@@ -438,41 +408,21 @@ __global__ __launch_bounds__(EB) void cons_avgpool_bwd_kernel(const float* __res
 }
 
 // ------------------------------------------------------------------------------------------------ launchers
-static inline int cons_sample_blocks(int64_t b, int64_t hw, int cap) {
-    int64_t nb = ctl_cdiv64(hw, EB), lim = cap / b;
-    if (lim < 1) lim = 1;
-    return (int)(nb < lim ? nb : lim);
-}
 static inline int cons_tile(int c) { return c <= 4 ? 32 : 16; }
-static inline int cons_tile_blocks(int64_t b, int h, int w, int c) {
-    const int t = cons_tile(c);
-    const int64_t n = b * ctl_cdiv(h, t) * ctl_cdiv(w, t);
-    return (int)(n < CONS_MAX_TILE_BLOCKS ? n : CONS_MAX_TILE_BLOCKS);
-}
 static int cons_check(const char* who, int kinds, int64_t b, int64_t h, int64_t w, int c) {
     CTL_REQUIRE(kinds > 0 && (kinds & ~CONS_ALL) == 0, "%s: kinds 0x%x (a non-empty set of the bits 0x01 .. 0x20)", who, kinds);
     CTL_REQUIRE(b > 0 && h > 0 && w > 0, "%s: sizes must be positive (batch %lld, plane %lld x %lld)", who, (long long)b, (long long)h, (long long)w);
-    CTL_REQUIRE(c >= 1 && c <= MAXC, "%s: %d classes (1 .. %d)", who, c, MAXC);
+    if (int rc = ctl_check_channels(who, c, "classes")) return rc;
     CTL_REQUIRE(!(kinds & CTL_CONS_CONTOUR) || c >= 2, "%s: contour needs at least 2 classes (got %d): it runs over the classes 1 .. c-1", who, c);
-    CTL_REQUIRE(b <= 65535, "%s: batch %lld (at most 65535 samples)", who, (long long)b);
-    CTL_REQUIRE(h * w < ((int64_t)1 << 31) && b * h * w < ((int64_t)1 << 31) / (c * 4),
-                "%s: %lld x %lld x %lld pixels of %d classes reach the 2 GiB tensor limit", who, (long long)b, (long long)h, (long long)w, c);
-    return CTL_OK;
+    if (int rc = ctl_check_batch(who, b)) return rc;
+    return ctl_check_2gib(who, b, h, w, c, "classes");
 }
 static int cons_weights(const char* who, int kinds, int c, const double* weights, const double* class_weights, cons_wk* wk, cons_wc* wc) {
-    CTL_REQUIRE(weights, "%s: null pointer (weights: one double per kind)", who);
-    for (int t = 0; t < CONS_NK; ++t) {
-        const bool on = (kinds >> t) & 1;
-        CTL_REQUIRE(!on || std::isfinite(weights[t]), "%s: the weight of kind %d is %g (finite)", who, t, weights[t]);
-        wk->v[t] = on ? weights[t] : 0.0;
-    }
-    for (int k = 0; k < MAXC; ++k) wc->v[k] = k < c ? 1.0 : 0.0;
+    if (int rc = ctl_kind_weights(who, kinds, CONS_NK, weights, wk->v)) return rc;
+    for (int k = 0; k < CTL_ROW_MAXC; ++k) wc->v[k] = k < c ? 1.0 : 0.0;
     if (kinds & CTL_CONS_WCE) {
         CTL_REQUIRE(class_weights, "%s: null pointer (weighted ce needs the class weights)", who);
-        double sum = 0.0;
-        for (int k = 0; k < c; ++k) sum += class_weights[k];
-        CTL_REQUIRE(std::isfinite(sum) && sum > 0.0, "%s: the class weights sum to %g (a finite, positive sum is needed)", who, sum);
-        for (int k = 0; k < c; ++k) wc->v[k] = class_weights[k] / sum * (double)c;
+        if (int rc = ctl_class_weights_norm(who, c, class_weights, wc->v)) return rc;
     }
     return CTL_OK;
 }
@@ -483,8 +433,8 @@ static inline double cons_p8logp8() { return (double)(1e-8f * logf(1e-8f)); }
 struct cons_layout { size_t coef, scal, pw, ct, total; int nb, ncb; };
 static cons_layout cons_ws(int kinds, int64_t b, int h, int w, int c) {
     cons_layout l;
-    l.nb = cons_sample_blocks(b, (int64_t)h * w, CTL_RED_BLOCKS);
-    l.ncb = cons_tile_blocks(b, h, w, c);
+    l.nb = ctl_sample_blocks(b, (int64_t)h * w, EB, CTL_RED_BLOCKS);
+    l.ncb = ctl_tile_blocks(b, h, w, cons_tile(c), CONS_MAX_TILE_BLOCKS);
     l.coef = 0;
     l.scal = (size_t)b * c * 2;
     l.pw = l.scal + CONS_SCAL;
@@ -515,8 +465,7 @@ extern "C" int ctl_consistency_fwd(int32_t kinds, const double* weights, const d
     int extra = 0;
     if (kinds & CONS_PW) {
         const dim3 grid(l.nb, b);
-        if (v4) cons_pw_partial_kernel<4><<<grid, dim3(EB), 0, S_>>>(x, r, mask, hw, c, kinds, is_gt != 0, wc, cons_p8(), cons_p8logp8(), ws + l.pw);
-        else cons_pw_partial_kernel<0><<<grid, dim3(EB), 0, S_>>>(x, r, mask, hw, c, kinds, is_gt != 0, wc, cons_p8(), cons_p8logp8(), ws + l.pw);
+        CTL_ROW_DISPATCH(cons_pw_partial_kernel, v4, grid, x, r, mask, hw, c, kinds, is_gt != 0, wc, cons_p8(), cons_p8logp8(), ws + l.pw);
         ++extra;
     }
     if (kinds & CTL_CONS_CONTOUR) {
@@ -548,9 +497,8 @@ extern "C" int ctl_consistency_bwd(int32_t kinds, const double* weights, const d
     const bool v4 = ctl_vec4(c, x, r, dlogit);
     int extra = -1;
     if (kinds & CONS_PW) {
-        const dim3 grid(cons_sample_blocks(b, hw, CONS_MAX_STREAM_BLOCKS), b);
-        if (v4) cons_pw_bwd_kernel<4><<<grid, dim3(EB), 0, S_>>>(x, r, mask, gout, ws + l.coef, ws + l.scal, hw, c, kinds, is_gt != 0, wc, wk, cons_p8(), pixels, dlogit);
-        else cons_pw_bwd_kernel<0><<<grid, dim3(EB), 0, S_>>>(x, r, mask, gout, ws + l.coef, ws + l.scal, hw, c, kinds, is_gt != 0, wc, wk, cons_p8(), pixels, dlogit);
+        const dim3 grid(ctl_sample_blocks(b, hw, EB, CONS_MAX_STREAM_BLOCKS), b);
+        CTL_ROW_DISPATCH(cons_pw_bwd_kernel, v4, grid, x, r, mask, gout, ws + l.coef, ws + l.scal, hw, c, kinds, is_gt != 0, wc, wk, cons_p8(), pixels, dlogit);
         ++extra;
     }
     if (kinds & CTL_CONS_CONTOUR) {
@@ -570,12 +518,10 @@ extern "C" int ctl_consistency_bwd(int32_t kinds, const double* weights, const d
 
 static int cons_pool_check(const char* who, int64_t b, int64_t h, int64_t w, int c, int s) {
     CTL_REQUIRE(b > 0 && h > 0 && w > 0, "%s: sizes must be positive (batch %lld, plane %lld x %lld)", who, (long long)b, (long long)h, (long long)w);
-    CTL_REQUIRE(c >= 1 && c <= MAXC, "%s: %d channels (1 .. %d)", who, c, MAXC);
+    if (int rc = ctl_check_channels(who, c, "channels")) return rc;
     CTL_REQUIRE(s >= 1 && s <= 4, "%s: scale %d (1 .. 4: windows of 2 .. 16 pixels)", who, s);
     CTL_REQUIRE((h >> s) >= 1 && (w >> s) >= 1, "%s: a %lld x %lld plane is smaller than the window of scale %d", who, (long long)h, (long long)w, s);
-    CTL_REQUIRE(h * w < ((int64_t)1 << 31) && b * h * w < ((int64_t)1 << 31) / (c * 4),
-                "%s: %lld x %lld x %lld pixels of %d channels reach the 2 GiB tensor limit", who, (long long)b, (long long)h, (long long)w, c);
-    return CTL_OK;
+    return ctl_check_2gib(who, b, h, w, c, "channels");
 }
 extern "C" int ctl_avgpool_fwd(const float* x, int32_t b, int32_t h, int32_t w, int32_t c, int32_t scale, float* y, ctl_stream stream) {
     CTL_REQUIRE(x && y, "avgpool_fwd: null pointer");

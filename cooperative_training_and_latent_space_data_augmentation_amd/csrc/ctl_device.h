@@ -1,5 +1,6 @@
-// Helpers shared by the feature kernels (ctl_elem, ctl_io, ctl_mask, ctl_aug, ctl_surface, ctl_cc, ctl_prep, ctl_restore, ctl_corrupt,
-// ctl_batch, ctl_loss, ctl_dist); the conv / weight-gradient families and the plan compiler need none of this and include ctl_common.h alone.
+// Helpers shared by the feature kernels (every .hip file but the conv / weight-gradient families, which like the plan compiler need none
+// of this and include ctl_common.h alone).  The kernels over channel rows of NHWC logits (ctl_loss, ctl_consist, ctl_recon, ctl_uncert,
+// ctl_elem) include it through ctl_rows.h, which adds the row accessors, the block-row reduction steps and the launch sizing they share.
 //   host    S_                       the launchers' stream argument as a hipStream_t
 //           ctl_align256             workspace sections start on 256 bytes
 //           ctl_blocks               1-D launch sizing: clamp(cdiv(items, threads), 1, cap)

@@ -2,9 +2,9 @@
 // backward, STN input builders, fused losses, argmax and the flat multi-tensor Adam.  All fp32 NHWC; 16 bytes per lane
 // wherever the channel count allows, wavefront(64)-shuffle + LDS block reductions, two-stage deterministic sums
 // (per-block partials in fp32, finalisation in fp64) instead of float atomics.
-#include "ctl_device.h"
+#include "ctl_rows.h"
 
-#define EB 256               // threads per block for the streaming kernels
+#define EB CTL_ROW_THREADS   // threads per block for the streaming kernels
 #ifndef CTL_FIN_THREADS
 #define CTL_FIN_THREADS EB      // threads per block of the BatchNorm finalize kernels (one block per channel)
 #endif
@@ -453,9 +453,10 @@ __global__ __launch_bounds__(EB) void sigmoid_bwd_kernel(const float* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------ STN input builders
-#define MAXC 16
 // Per-pixel channel rows of the label-space tensors.  CT = 4 (the 4-class maps of the path): one 16-byte load / store per pixel
 // and fully unrolled loops; CT = 0: runtime channel count.  The arithmetic and its order are the same in both.
+// (ctl_row_load / ctl_row_store of ctl_rows.h with a plain runtime loop for CT = 0; kept apart because the shared form, unrolled over
+// CTL_ROW_MAXC with the tail switched off, compiles the <0> kernels below to other code)
 template <int CT> __device__ __forceinline__ void row_load(const float* __restrict__ base, int64_t i, int c, float* v) {
     if (CT == 4) {
         const f32x4 t = *reinterpret_cast<const f32x4*>(base + i * 4);
@@ -471,18 +472,13 @@ template <int CT> __device__ __forceinline__ void row_store(float* __restrict__ 
         for (int k = 0; k < c; ++k) base[i * c + k] = v[k];
     }
 }
-#define CTL_ROW_DISPATCH(kernel, vec4, grid, ...)                                \
-    do {                                                                         \
-        if (vec4) kernel<4><<<grid, dim3(EB), 0, S_>>>(__VA_ARGS__);             \
-        else kernel<0><<<grid, dim3(EB), 0, S_>>>(__VA_ARGS__);                  \
-    } while (0)
 template <int CT>
 __global__ __launch_bounds__(EB) void softmax_t_fwd_kernel(const float* __restrict__ x, float inv_t, float* __restrict__ p,
                                                             int64_t pixels, int c_rt) {
     const int c = CT ? CT : c_rt;
     const int64_t stride = (int64_t)gridDim.x * EB;
     for (int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x; i < pixels; i += stride) {
-        float v[CT ? CT : MAXC];
+        float v[CT ? CT : CTL_ROW_MAXC];
         row_load<CT>(x, i, c, v);
         float m = -INFINITY;
 #pragma unroll
@@ -502,7 +498,7 @@ __global__ __launch_bounds__(EB) void softmax_t_bwd_kernel(const float* __restri
     const int c = CT ? CT : c_rt;
     const int64_t stride = (int64_t)gridDim.x * EB;
     for (int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x; i < pixels; i += stride) {
-        float pv[CT ? CT : MAXC], dv[CT ? CT : MAXC];
+        float pv[CT ? CT : CTL_ROW_MAXC], dv[CT ? CT : CTL_ROW_MAXC];
         row_load<CT>(p, i, c, pv);
         row_load<CT>(dp, i, c, dv);
         float dot = 0.f;
@@ -537,7 +533,7 @@ __global__ __launch_bounds__(EB) void ce2d_partial_kernel(const float* __restric
     const int64_t stride = (int64_t)gridDim.x * EB;
     double acc = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x; i < pixels; i += stride) {
-        float v[CT ? CT : MAXC];
+        float v[CT ? CT : CTL_ROW_MAXC];
         row_load<CT>(logit, i, c, v);
         float m = -INFINITY;
 #pragma unroll
@@ -570,7 +566,7 @@ __global__ __launch_bounds__(EB) void ce2d_bwd_kernel(const float* __restrict__ 
     const float gs = gout[0] / (float)pixels;
     const int64_t stride = (int64_t)gridDim.x * EB;
     for (int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x; i < pixels; i += stride) {
-        float v[CT ? CT : MAXC];
+        float v[CT ? CT : CTL_ROW_MAXC];
         row_load<CT>(logit, i, c, v);
         float m = -INFINITY;
 #pragma unroll
@@ -873,14 +869,14 @@ extern "C" int ctl_sigmoid_bwd(const float* dy, const float* y, float* dx, int64
     return CTL_OK;
 }
 extern "C" int ctl_softmax_t_fwd(const float* x, float inv_t, float* p, int64_t pixels, int32_t c, ctl_stream stream) {
-    CTL_REQUIRE(x && p && pixels > 0 && c > 0 && c <= MAXC, "softmax_t_fwd: bad arguments");
+    CTL_REQUIRE(x && p && pixels > 0 && c > 0 && c <= CTL_ROW_MAXC, "softmax_t_fwd: bad arguments");
     CTL_ROW_DISPATCH(softmax_t_fwd_kernel, ctl_vec4(c, x, p), dim3(ctl_blocks(pixels, EB, MAX_STREAM_BLOCKS)), x, inv_t, p, pixels, c);
     CTL_LAUNCH_CHECK("softmax_t_fwd");
     return CTL_OK;
 }
 extern "C" int ctl_softmax_t_bwd(const float* p, const float* dp, float inv_t, float* dx, int64_t pixels, int32_t c,
                                  ctl_stream stream) {
-    CTL_REQUIRE(p && dp && dx && pixels > 0 && c > 0 && c <= MAXC, "softmax_t_bwd: bad arguments");
+    CTL_REQUIRE(p && dp && dx && pixels > 0 && c > 0 && c <= CTL_ROW_MAXC, "softmax_t_bwd: bad arguments");
     CTL_ROW_DISPATCH(softmax_t_bwd_kernel, ctl_vec4(c, p, dp, dx), dim3(ctl_blocks(pixels, EB, MAX_STREAM_BLOCKS)), p, dp, inv_t, dx, pixels, c);
     CTL_LAUNCH_CHECK("softmax_t_bwd");
     return CTL_OK;
@@ -893,7 +889,7 @@ extern "C" int ctl_onehot(const int64_t* label, float* y, int64_t pixels, int32_
 }
 extern "C" int ctl_ce2d_fwd(const float* logit, const int64_t* label, int64_t pixels, int32_t c, double* partial,
                             float* loss, ctl_stream stream) {
-    CTL_REQUIRE(logit && label && partial && loss && pixels > 0 && c > 0 && c <= MAXC, "ce2d_fwd: bad arguments");
+    CTL_REQUIRE(logit && label && partial && loss && pixels > 0 && c > 0 && c <= CTL_ROW_MAXC, "ce2d_fwd: bad arguments");
     CTL_ROW_DISPATCH(ce2d_partial_kernel, ctl_vec4(c, logit), dim3(CTL_RED_BLOCKS), logit, label, pixels, c, partial);
     scalar_finalize_kernel<<<dim3(1), dim3(EB), 0, S_>>>(partial, CTL_RED_BLOCKS, 1.0 / (double)pixels, loss);
     ctl_count_launches(1);      // partial + finalize
@@ -902,7 +898,7 @@ extern "C" int ctl_ce2d_fwd(const float* logit, const int64_t* label, int64_t pi
 }
 extern "C" int ctl_ce2d_bwd(const float* logit, const int64_t* label, const float* gout, int64_t pixels, int32_t c,
                             float* dlogit, ctl_stream stream) {
-    CTL_REQUIRE(logit && label && gout && dlogit && pixels > 0 && c > 0 && c <= MAXC, "ce2d_bwd: bad arguments");
+    CTL_REQUIRE(logit && label && gout && dlogit && pixels > 0 && c > 0 && c <= CTL_ROW_MAXC, "ce2d_bwd: bad arguments");
     CTL_ROW_DISPATCH(ce2d_bwd_kernel, ctl_vec4(c, logit, dlogit), dim3(ctl_blocks(pixels, EB, MAX_STREAM_BLOCKS)), logit, label, gout, pixels, c, dlogit);
     CTL_LAUNCH_CHECK("ce2d_bwd");
     return CTL_OK;

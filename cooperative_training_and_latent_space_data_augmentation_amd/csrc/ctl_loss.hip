@@ -8,47 +8,12 @@
 //
 // The distance-map losses ('boundary', 'hausdorff dt'; no upstream counterpart) stream the same way with one or two fp32 NHWC field tensors
 // beside the logits (ctl_dist.hip writes them); ctl_confident_label is the thresholding of a prediction whose fields 'hausdorff dt' needs.
-#include <cmath>
-#include "ctl_device.h"
+#include "ctl_rows.h"
 
-#define EB 256               // threads per block
-#define MAXC 16
+#define EB CTL_ROW_THREADS   // threads per block
 #define LOSS_MAX_STREAM_BLOCKS 2048
 
-struct ctl_w16 { float v[MAXC]; };      // normalised class weights, a launch argument (constant from step to step)
-
-// Channel rows.  CT = 4: one 16-byte load / store per pixel; CT = 0: runtime channel count, the loops still unrolled over MAXC with the
-// tail switched off (everything stays in registers).  The arithmetic and its order are the same in both; contraction is off in every
-// function below so that neither form turns a product and a sum into an fma the other one keeps apart.
-template <int CT> __device__ __forceinline__ void lrow_load(const float* __restrict__ base, int64_t i, int c, float* v) {
-    if (CT == 4) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(base + i * 4);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < MAXC; ++k) if (k < c) v[k] = base[i * c + k];
-    }
-}
-template <int CT> __device__ __forceinline__ void lrow_store(float* __restrict__ base, int64_t i, int c, const float* v) {
-    if (CT == 4) {
-        *reinterpret_cast<f32x4*>(base + i * 4) = f32x4{v[0], v[1], v[2], v[3]};
-    } else {
-#pragma unroll
-        for (int k = 0; k < MAXC; ++k) if (k < c) base[i * c + k] = v[k];
-    }
-}
-// v <- exp(v - max v); returns the row maximum, `s` = the sum of the exponentials
-template <int CT> __device__ __forceinline__ float lrow_exp(float* v, int c, float& s) {
-#pragma clang fp contract(off)
-    constexpr int NC = CT ? CT : MAXC;
-    float m = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < NC; ++k) if (k < c) m = fmaxf(m, v[k]);
-    s = 0.f;
-#pragma unroll
-    for (int k = 0; k < NC; ++k) if (k < c) { v[k] = expf(v[k] - m); s += v[k]; }
-    return m;
-}
+struct ctl_w16 { float v[CTL_ROW_MAXC]; };      // normalised class weights, a launch argument (constant from step to step)
 
 // ------------------------------------------------------------------------------------------------ point-wise kinds
 // pixel term of the loss and the factor f of its gradient f * (p_k - t_k):
@@ -58,7 +23,7 @@ template <int CT> __device__ __forceinline__ float lrow_exp(float* v, int c, flo
 template <int CT>
 __device__ __forceinline__ float pw_factor(int kind, const float* e, float s, int c, int64_t l, const ctl_w16& w, float gamma) {
 #pragma clang fp contract(off)
-    constexpr int NC = CT ? CT : MAXC;
+    constexpr int NC = CT ? CT : CTL_ROW_MAXC;
     if (kind == CTL_LOSS_WCE) {
         float wl = 0.f;
 #pragma unroll
@@ -76,18 +41,18 @@ __global__ __launch_bounds__(EB) void seg_pw_partial_kernel(const float* __restr
                                                              int64_t pixels, int c_rt, int kind, ctl_w16 w, float gamma,
                                                              double* __restrict__ partial) {
 #pragma clang fp contract(off)
-    constexpr int NC = CT ? CT : MAXC;
+    constexpr int NC = CT ? CT : CTL_ROW_MAXC;
     __shared__ double sm[EB / 64];
     const int c = CT ? CT : c_rt;
     const int64_t stride = (int64_t)gridDim.x * EB;
     double acc = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x; i < pixels; i += stride) {
         float v[NC], x[NC];
-        lrow_load<CT>(logit, i, c, v);
+        ctl_row_load<CT>(logit, i, c, v);
 #pragma unroll
         for (int k = 0; k < NC; ++k) if (k < c) x[k] = v[k];
         float s;
-        const float m = lrow_exp<CT>(v, c, s);
+        const float m = ctl_row_exp<CT>(v, c, s);
         const int64_t l = label[i];
         float xl = m;      // (no class: log p = -log s, times the factor 0)
 #pragma unroll
@@ -113,8 +78,8 @@ template <int CT>
 __global__ __launch_bounds__(EB) void dice_partial_kernel(const float* __restrict__ logit, const int64_t* __restrict__ label, int64_t hw,
                                                            int c_rt, double* __restrict__ partial) {
 #pragma clang fp contract(off)
-    constexpr int NC = CT ? CT : MAXC;
-    __shared__ double sm[EB / 64][3 * MAXC];
+    constexpr int NC = CT ? CT : CTL_ROW_MAXC;
+    __shared__ double sm[EB / 64][3 * CTL_ROW_MAXC];
     const int c = CT ? CT : c_rt;
     const int64_t b = blockIdx.y;
     const float* __restrict__ x = logit + b * hw * c;
@@ -126,9 +91,9 @@ __global__ __launch_bounds__(EB) void dice_partial_kernel(const float* __restric
     const int64_t stride = (int64_t)gridDim.x * EB;
     for (int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x; i < hw; i += stride) {
         float v[NC];
-        lrow_load<CT>(x, i, c, v);
+        ctl_row_load<CT>(x, i, c, v);
         float s;
-        lrow_exp<CT>(v, c, s);
+        ctl_row_exp<CT>(v, c, s);
         const float r = 1.f / s;
         const int64_t l = y[i];
 #pragma unroll
@@ -146,12 +111,7 @@ __global__ __launch_bounds__(EB) void dice_partial_kernel(const float* __restric
         const double a = wave_sum_double(sp[k]), t = wave_sum_double(spt[k]), n = wave_sum_double((double)cnt[k]);
         if ((threadIdx.x & 63) == 0) { sm[wv][3 * k] = a; sm[wv][3 * k + 1] = t; sm[wv][3 * k + 2] = n; }
     }
-    __syncthreads();
-    if ((int)threadIdx.x < 3 * c) {
-        double r = 0.0;
-        for (int i = 0; i < EB / 64; ++i) r += sm[i][threadIdx.x];
-        partial[((b * gridDim.x + blockIdx.x) * c) * 3 + threadIdx.x] = r;
-    }
+    CTL_BLOCK_ROWS_STORE(sm, EB / 64, 3 * c, partial + ((b * gridDim.x + blockIdx.x) * c) * 3);
 }
 // pass 2, one block: a group of 16 lanes sums the `nb` block rows of one (sample, class) in a fixed order, the group's first lane forms
 // the Dice term and the two coefficients of the backward:  g_k = dL/dp_k = coef[b][k][0] * t_k + coef[b][k][1]
@@ -176,7 +136,7 @@ __global__ __launch_bounds__(EB) void dice_finalize_kernel(const double* __restr
                 sp += q[0]; spt += q[1]; n += q[2];
             }
         }
-        for (int o = 8; o > 0; o >>= 1) { sp += __shfl_xor(sp, o); spt += __shfl_xor(spt, o); n += __shfl_xor(n, o); }
+        CTL_GROUP16_SUM3(sp, spt, n);
         if (ok && lane == 0) {
             const bool sel = !fg || k >= 1;
             const double U = sp + n + smooth;
@@ -199,7 +159,7 @@ __global__ __launch_bounds__(EB) void seg_loss_bwd_kernel(const float* __restric
                                                            int c_rt, int kind, ctl_w16 w, float gamma, float pixels_f,
                                                            float* __restrict__ dlogit) {
 #pragma clang fp contract(off)
-    constexpr int NC = CT ? CT : MAXC;
+    constexpr int NC = CT ? CT : CTL_ROW_MAXC;
     const int c = CT ? CT : c_rt;
     const int64_t b = blockIdx.y;
     const float* __restrict__ x = logit + b * hw * c;
@@ -218,9 +178,9 @@ __global__ __launch_bounds__(EB) void seg_loss_bwd_kernel(const float* __restric
     const int64_t stride = (int64_t)gridDim.x * EB;
     for (int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x; i < hw; i += stride) {
         float v[NC];
-        lrow_load<CT>(x, i, c, v);
+        ctl_row_load<CT>(x, i, c, v);
         float s;
-        lrow_exp<CT>(v, c, s);
+        ctl_row_exp<CT>(v, c, s);
         const float r = 1.f / s;
         const int64_t l = y[i];
         if (dice) {
@@ -244,50 +204,47 @@ __global__ __launch_bounds__(EB) void seg_loss_bwd_kernel(const float* __restric
 #pragma unroll
             for (int k = 0; k < NC; ++k) if (k < c) v[k] = gf * ((l == (int64_t)k) ? -(so * r) : v[k] * r);
         }
-        lrow_store<CT>(dx, i, c, v);
+        ctl_row_store<CT>(dx, i, c, v);
     }
 }
 
 // ------------------------------------------------------------------------------------------------ launchers
 static inline bool kind_is_dice(int kind) { return kind == CTL_LOSS_DICE || kind == CTL_LOSS_FG_DICE; }
-// blocks per sample of the two-dimensional grids: at most `cap` blocks over all samples (one per sample where b exceeds the cap)
-static inline int sample_blocks(int64_t b, int64_t hw, int cap) {
-    int64_t nb = ctl_cdiv64(hw, EB), lim = cap / b;
-    if (lim < 1) lim = 1;
-    return (int)(nb < lim ? nb : lim);
+// the tensor limit of both loss families: logits of c floats per pixel beside labels of 8 bytes per pixel
+static int loss_check_2gib(const char* who, int64_t b, int64_t hw, int c) {
+    const int64_t row_bytes = c * 4 > 8 ? c * 4 : 8;
+    CTL_REQUIRE(hw < ((int64_t)1 << 31) && b * hw < ((int64_t)1 << 31) / row_bytes,
+                "%s: %lld x %lld pixels of %d classes reach the 2 GiB tensor limit", who, (long long)b, (long long)hw, c);
+    return CTL_OK;
 }
 // the checks every entry shares; the message names the entry
 static int seg_loss_check(const char* who, int kind, int64_t b, int64_t hw, int c) {
     CTL_REQUIRE(kind >= CTL_LOSS_WCE && kind <= CTL_LOSS_FG_DICE, "%s: unknown loss kind %d", who, kind);
     CTL_REQUIRE(b > 0 && hw > 0, "%s: sizes must be positive (batch %lld, pixels per sample %lld)", who, (long long)b, (long long)hw);
-    CTL_REQUIRE(c >= 1 && c <= MAXC, "%s: %d classes (1 .. %d)", who, c, MAXC);
+    if (int rc = ctl_check_channels(who, c, "classes")) return rc;
     CTL_REQUIRE(kind != CTL_LOSS_FG_DICE || c >= 2, "%s: foreground dice needs at least 2 classes (got %d)", who, c);
-    CTL_REQUIRE(b <= 65535, "%s: batch %lld (at most 65535 samples)", who, (long long)b);
-    const int64_t row_bytes = c * 4 > 8 ? c * 4 : 8;      // logits: c floats per pixel, labels: 8 bytes per pixel
-    CTL_REQUIRE(hw < ((int64_t)1 << 31) && b * hw < ((int64_t)1 << 31) / row_bytes,
-                "%s: %lld x %lld pixels of %d classes reach the 2 GiB tensor limit", who, (long long)b, (long long)hw, c);
-    return CTL_OK;
+    if (int rc = ctl_check_batch(who, b)) return rc;
+    return loss_check_2gib(who, b, hw, c);
 }
 // w' = w / sum(w) * c in fp64, handed to the kernels as fp32 (custom_loss.py:733-734); NULL = upstream's uniform 1/c, i.e. all ones
 static int seg_loss_weights(const char* who, int kind, int c, const double* class_weights, float gamma, ctl_w16* w) {
-    for (int k = 0; k < MAXC; ++k) w->v[k] = k < c ? 1.f : 0.f;
+    for (int k = 0; k < CTL_ROW_MAXC; ++k) w->v[k] = k < c ? 1.f : 0.f;
     if (kind == CTL_LOSS_WCE && class_weights) {
-        double sum = 0.0;
-        for (int k = 0; k < c; ++k) sum += class_weights[k];
-        CTL_REQUIRE(std::isfinite(sum) && sum > 0.0, "%s: the class weights sum to %g (a finite, positive sum is needed)", who, sum);
-        for (int k = 0; k < c; ++k) w->v[k] = (float)(class_weights[k] / sum * (double)c);
+        double wn[CTL_ROW_MAXC];
+        if (int rc = ctl_class_weights_norm(who, c, class_weights, wn)) return rc;
+        for (int k = 0; k < c; ++k) w->v[k] = (float)wn[k];
     }
     CTL_REQUIRE(kind != CTL_LOSS_FOCAL || (std::isfinite(gamma) && gamma >= 0.f), "%s: focal gamma %g (finite, >= 0)", who, (double)gamma);
     return CTL_OK;
 }
 
 extern "C" int32_t ctl_seg_loss_blocks(int32_t b, int64_t hw) {
-    return (b > 0 && hw > 0) ? sample_blocks(b, hw, CTL_RED_BLOCKS) : 0;
+    return (b > 0 && hw > 0) ? ctl_sample_blocks(b, hw, EB, CTL_RED_BLOCKS) : 0;
 }
 extern "C" size_t ctl_seg_loss_ws_doubles(int32_t kind, int32_t b, int64_t hw, int32_t c) {
     if (seg_loss_check("seg_loss_ws_doubles", kind, b, hw, c) != CTL_OK) return 0;
     if (!kind_is_dice(kind)) return CTL_RED_BLOCKS;
-    return (size_t)b * sample_blocks(b, hw, CTL_RED_BLOCKS) * c * 3 + (size_t)b * c * 2;
+    return (size_t)b * ctl_sample_blocks(b, hw, EB, CTL_RED_BLOCKS) * c * 3 + (size_t)b * c * 2;
 }
 extern "C" int ctl_seg_loss_fwd(int32_t kind, const float* logit, const int64_t* label, const double* class_weights, float gamma,
                                 int32_t b, int64_t hw, int32_t c, double* ws, float* loss, ctl_stream stream) {
@@ -297,16 +254,14 @@ extern "C" int ctl_seg_loss_fwd(int32_t kind, const float* logit, const int64_t*
     if (int rc = seg_loss_weights("seg_loss_fwd", kind, c, class_weights, gamma, &w)) return rc;
     const bool v4 = ctl_vec4(c, logit);
     if (kind_is_dice(kind)) {
-        const int nb = sample_blocks(b, hw, CTL_RED_BLOCKS);
+        const int nb = ctl_sample_blocks(b, hw, EB, CTL_RED_BLOCKS);
         double* coef = ws + (size_t)b * nb * c * 3;
         const int fg = kind == CTL_LOSS_FG_DICE;
-        if (v4) dice_partial_kernel<4><<<dim3(nb, b), dim3(EB), 0, S_>>>(logit, label, hw, c, ws);
-        else dice_partial_kernel<0><<<dim3(nb, b), dim3(EB), 0, S_>>>(logit, label, hw, c, ws);
+        CTL_ROW_DISPATCH(dice_partial_kernel, v4, dim3(nb, b), logit, label, hw, c, ws);
         dice_finalize_kernel<<<dim3(1), dim3(EB), 0, S_>>>(ws, b * c, nb, c, fg, (double)b * (double)(fg ? c - 1 : c), coef, loss);
     } else {
         const int64_t pixels = (int64_t)b * hw;
-        if (v4) seg_pw_partial_kernel<4><<<dim3(CTL_RED_BLOCKS), dim3(EB), 0, S_>>>(logit, label, pixels, c, kind, w, gamma, ws);
-        else seg_pw_partial_kernel<0><<<dim3(CTL_RED_BLOCKS), dim3(EB), 0, S_>>>(logit, label, pixels, c, kind, w, gamma, ws);
+        CTL_ROW_DISPATCH(seg_pw_partial_kernel, v4, dim3(CTL_RED_BLOCKS), logit, label, pixels, c, kind, w, gamma, ws);
         seg_pw_finalize_kernel<<<dim3(1), dim3(EB), 0, S_>>>(ws, CTL_RED_BLOCKS, 1.0 / (double)pixels, loss);
     }
     ctl_count_launches(1);      // partial + finalize
@@ -320,11 +275,10 @@ extern "C" int ctl_seg_loss_bwd(int32_t kind, const float* logit, const int64_t*
     CTL_REQUIRE(!kind_is_dice(kind) || ws, "seg_loss_bwd: null pointer (the Dice kinds read the coefficient table of the forward from ws)");
     ctl_w16 w;
     if (int rc = seg_loss_weights("seg_loss_bwd", kind, c, class_weights, gamma, &w)) return rc;
-    const double* coef = kind_is_dice(kind) ? ws + (size_t)b * sample_blocks(b, hw, CTL_RED_BLOCKS) * c * 3 : nullptr;
-    const dim3 grid(sample_blocks(b, hw, LOSS_MAX_STREAM_BLOCKS), b);
+    const double* coef = kind_is_dice(kind) ? ws + (size_t)b * ctl_sample_blocks(b, hw, EB, CTL_RED_BLOCKS) * c * 3 : nullptr;
+    const dim3 grid(ctl_sample_blocks(b, hw, EB, LOSS_MAX_STREAM_BLOCKS), b);
     const float pixels_f = (float)((int64_t)b * hw);
-    if (ctl_vec4(c, logit, dlogit)) seg_loss_bwd_kernel<4><<<grid, dim3(EB), 0, S_>>>(logit, label, gout, coef, hw, c, kind, w, gamma, pixels_f, dlogit);
-    else seg_loss_bwd_kernel<0><<<grid, dim3(EB), 0, S_>>>(logit, label, gout, coef, hw, c, kind, w, gamma, pixels_f, dlogit);
+    CTL_ROW_DISPATCH(seg_loss_bwd_kernel, ctl_vec4(c, logit, dlogit), grid, logit, label, gout, coef, hw, c, kind, w, gamma, pixels_f, dlogit);
     CTL_LAUNCH_CHECK("seg_loss_bwd");
     return CTL_OK;
 }
@@ -336,10 +290,10 @@ extern "C" int ctl_seg_loss_bwd(int32_t kind, const float* logit, const int64_t*
 // and dL/dx_j = p_j (g_j S - sum_k p_k g_k) with S the sum of the rounded p_k, as the Dice backward has it.
 template <int CT>
 __device__ __forceinline__ void dl_fields(int kind, const float* __restrict__ fa, const float* __restrict__ fb, int64_t i, int c, double* d) {
-    constexpr int NC = CT ? CT : MAXC;
+    constexpr int NC = CT ? CT : CTL_ROW_MAXC;
     float a[NC], b[NC];
-    lrow_load<CT>(fa, i, c, a);
-    if (kind == CTL_DLOSS_HAUSDORFF_DT) lrow_load<CT>(fb, i, c, b);
+    ctl_row_load<CT>(fa, i, c, a);
+    if (kind == CTL_DLOSS_HAUSDORFF_DT) ctl_row_load<CT>(fb, i, c, b);
 #pragma unroll
     for (int k = 0; k < NC; ++k) if (k < c) d[k] = k == 0 ? 0.0 : (kind == CTL_DLOSS_HAUSDORFF_DT ? (double)a[k] + (double)b[k] : (double)a[k]);
 }
@@ -348,7 +302,7 @@ __global__ __launch_bounds__(EB) void dist_loss_partial_kernel(const float* __re
                                                                 const float* __restrict__ fa, const float* __restrict__ fb, int64_t pixels,
                                                                 int c_rt, int kind, double* __restrict__ partial) {
 #pragma clang fp contract(off)
-    constexpr int NC = CT ? CT : MAXC;
+    constexpr int NC = CT ? CT : CTL_ROW_MAXC;
     __shared__ double sm[EB / 64];
     const int c = CT ? CT : c_rt;
     const int64_t stride = (int64_t)gridDim.x * EB;
@@ -356,9 +310,9 @@ __global__ __launch_bounds__(EB) void dist_loss_partial_kernel(const float* __re
     for (int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x; i < pixels; i += stride) {
         float v[NC];
         double d[NC];
-        lrow_load<CT>(logit, i, c, v);
+        ctl_row_load<CT>(logit, i, c, v);
         float s;
-        lrow_exp<CT>(v, c, s);
+        ctl_row_exp<CT>(v, c, s);
         const float r = 1.f / s;
         dl_fields<CT>(kind, fa, fb, i, c, d);
         const int64_t l = kind == CTL_DLOSS_HAUSDORFF_DT ? label[i] : -1;
@@ -382,16 +336,16 @@ __global__ __launch_bounds__(EB) void dist_loss_bwd_kernel(const float* __restri
                                                             const float* __restrict__ gout, int64_t pixels, int c_rt, int kind, double inv_div,
                                                             float* __restrict__ dlogit) {
 #pragma clang fp contract(off)
-    constexpr int NC = CT ? CT : MAXC;
+    constexpr int NC = CT ? CT : CTL_ROW_MAXC;
     const int c = CT ? CT : c_rt;
     const double go = (double)gout[0];
     const int64_t stride = (int64_t)gridDim.x * EB;
     for (int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x; i < pixels; i += stride) {
         float v[NC];
         double d[NC], g[NC];
-        lrow_load<CT>(logit, i, c, v);
+        ctl_row_load<CT>(logit, i, c, v);
         float s;
-        lrow_exp<CT>(v, c, s);
+        ctl_row_exp<CT>(v, c, s);
         const float r = 1.f / s;
         dl_fields<CT>(kind, fa, fb, i, c, d);
         const int64_t l = kind == CTL_DLOSS_HAUSDORFF_DT ? label[i] : -1;
@@ -406,21 +360,21 @@ __global__ __launch_bounds__(EB) void dist_loss_bwd_kernel(const float* __restri
         }
 #pragma unroll
         for (int k = 0; k < NC; ++k) if (k < c) v[k] = (float)(go * ((double)v[k] * (g[k] * S - dot)));
-        lrow_store<CT>(dlogit, i, c, v);
+        ctl_row_store<CT>(dlogit, i, c, v);
     }
 }
 // first class whose softmax probability exceeds 1/2 (at most one can), else 255
 template <int CT>
 __global__ __launch_bounds__(EB) void confident_label_kernel(const float* __restrict__ logit, int64_t pixels, int c_rt, uint8_t* __restrict__ out) {
 #pragma clang fp contract(off)
-    constexpr int NC = CT ? CT : MAXC;
+    constexpr int NC = CT ? CT : CTL_ROW_MAXC;
     const int c = CT ? CT : c_rt;
     const int64_t stride = (int64_t)gridDim.x * EB;
     for (int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x; i < pixels; i += stride) {
         float v[NC];
-        lrow_load<CT>(logit, i, c, v);
+        ctl_row_load<CT>(logit, i, c, v);
         float s;
-        lrow_exp<CT>(v, c, s);
+        ctl_row_exp<CT>(v, c, s);
         const float r = 1.f / s;
         int q = 255;
 #pragma unroll
@@ -432,11 +386,8 @@ __global__ __launch_bounds__(EB) void confident_label_kernel(const float* __rest
 static int dist_loss_check(const char* who, int kind, int64_t b, int64_t hw, int c) {
     CTL_REQUIRE(kind == CTL_DLOSS_BOUNDARY || kind == CTL_DLOSS_HAUSDORFF_DT, "%s: unknown loss kind %d (0: boundary, 1: hausdorff dt)", who, kind);
     CTL_REQUIRE(b > 0 && hw > 0, "%s: sizes must be positive (batch %lld, pixels per sample %lld)", who, (long long)b, (long long)hw);
-    CTL_REQUIRE(c >= 2 && c <= MAXC, "%s: %d classes (2 .. %d: the loss runs over the classes 1 .. c-1)", who, c, MAXC);
-    const int64_t row_bytes = c * 4 > 8 ? c * 4 : 8;
-    CTL_REQUIRE(hw < ((int64_t)1 << 31) && b * hw < ((int64_t)1 << 31) / row_bytes,
-                "%s: %lld x %lld pixels of %d classes reach the 2 GiB tensor limit", who, (long long)b, (long long)hw, c);
-    return CTL_OK;
+    CTL_REQUIRE(c >= 2 && c <= CTL_ROW_MAXC, "%s: %d classes (2 .. %d: the loss runs over the classes 1 .. c-1)", who, c, CTL_ROW_MAXC);
+    return loss_check_2gib(who, b, hw, c);
 }
 extern "C" size_t ctl_dist_loss_ws_doubles(int32_t kind, int32_t b, int64_t hw, int32_t c) {
     return dist_loss_check("dist_loss_ws_doubles", kind, b, hw, c) == CTL_OK ? CTL_RED_BLOCKS : 0;
@@ -447,9 +398,7 @@ extern "C" int ctl_dist_loss_fwd(int32_t kind, const float* logit, const int64_t
     if (int rc = dist_loss_check("dist_loss_fwd", kind, b, hw, c)) return rc;
     CTL_REQUIRE(kind != CTL_DLOSS_HAUSDORFF_DT || (label && field_b), "dist_loss_fwd: null pointer (hausdorff dt reads the label map and two fields)");
     const int64_t pixels = (int64_t)b * hw;
-    if (ctl_vec4(c, logit, field_a, field_b))
-        dist_loss_partial_kernel<4><<<dim3(CTL_RED_BLOCKS), dim3(EB), 0, S_>>>(logit, label, field_a, field_b, pixels, c, kind, ws);
-    else dist_loss_partial_kernel<0><<<dim3(CTL_RED_BLOCKS), dim3(EB), 0, S_>>>(logit, label, field_a, field_b, pixels, c, kind, ws);
+    CTL_ROW_DISPATCH(dist_loss_partial_kernel, ctl_vec4(c, logit, field_a, field_b), dim3(CTL_RED_BLOCKS), logit, label, field_a, field_b, pixels, c, kind, ws);
     seg_pw_finalize_kernel<<<dim3(1), dim3(EB), 0, S_>>>(ws, CTL_RED_BLOCKS, 1.0 / ((double)pixels * (double)(c - 1)), loss);
     ctl_count_launches(1);      // partial + finalize
     CTL_LAUNCH_CHECK("dist_loss_fwd");
@@ -463,9 +412,8 @@ extern "C" int ctl_dist_loss_bwd(int32_t kind, const float* logit, const int64_t
     const int64_t pixels = (int64_t)b * hw;
     const double inv_div = 1.0 / ((double)pixels * (double)(c - 1));
     const dim3 grid(ctl_blocks(pixels, EB, LOSS_MAX_STREAM_BLOCKS));
-    if (ctl_vec4(c, logit, field_a, field_b) && ((uintptr_t)dlogit & 15) == 0)
-        dist_loss_bwd_kernel<4><<<grid, dim3(EB), 0, S_>>>(logit, label, field_a, field_b, gout, pixels, c, kind, inv_div, dlogit);
-    else dist_loss_bwd_kernel<0><<<grid, dim3(EB), 0, S_>>>(logit, label, field_a, field_b, gout, pixels, c, kind, inv_div, dlogit);
+    const bool v4 = ctl_vec4(c, logit, field_a, field_b) && ((uintptr_t)dlogit & 15) == 0;
+    CTL_ROW_DISPATCH(dist_loss_bwd_kernel, v4, grid, logit, label, field_a, field_b, gout, pixels, c, kind, inv_div, dlogit);
     CTL_LAUNCH_CHECK("dist_loss_bwd");
     return CTL_OK;
 }
@@ -473,10 +421,9 @@ extern "C" int ctl_confident_label(const float* logit, uint8_t* out, int64_t pix
     CTL_REQUIRE(logit && out, "confident_label: null pointer");
     CTL_REQUIRE(pixels > 0 && pixels < ((int64_t)1 << 31) / (c > 0 ? c * 4 : 4), "confident_label: %lld pixels (positive, below the 2 GiB tensor limit)",
                 (long long)pixels);
-    CTL_REQUIRE(c >= 1 && c <= MAXC, "confident_label: %d classes (1 .. %d)", c, MAXC);
+    if (int rc = ctl_check_channels("confident_label", c, "classes")) return rc;
     const dim3 grid(ctl_blocks(pixels, EB, LOSS_MAX_STREAM_BLOCKS));
-    if (ctl_vec4(c, logit)) confident_label_kernel<4><<<grid, dim3(EB), 0, S_>>>(logit, pixels, c, out);
-    else confident_label_kernel<0><<<grid, dim3(EB), 0, S_>>>(logit, pixels, c, out);
+    CTL_ROW_DISPATCH(confident_label_kernel, ctl_vec4(c, logit), grid, logit, pixels, c, out);
     CTL_LAUNCH_CHECK("confident_label");
     return CTL_OK;
 }

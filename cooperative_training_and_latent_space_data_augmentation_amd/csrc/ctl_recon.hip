@@ -10,11 +10,9 @@
 // gout * sum_k weight_k dL_k/dx rounded once -- a streaming launch, or with 'lncc' a tiled launch that stages the three maps with the same
 // halo, takes their window sums and adds the point-wise kinds in the same thread.  Sums are two-stage and ordered: no float atomics,
 // nothing is read back, the same bits on every call and in a graph replay.
-#include <cmath>
-#include "ctl_device.h"
+#include "ctl_rows.h"
 
-#define EB 256               // threads per block
-#define MAXC 16
+#define EB CTL_ROW_THREADS   // threads per block
 #define RECON_NK 5           // kinds
 #define RECON_STREAM (CTL_RECON_MSE | CTL_RECON_L1 | CTL_RECON_SMOOTH_L1 | CTL_RECON_NCC)
 #define RECON_ALL (RECON_STREAM | CTL_RECON_LNCC)
@@ -30,30 +28,6 @@ struct recon_wk { double v[RECON_NK]; };      // weight of each kind (0 where th
 // the backward's constants: 2 w_mse / N, w_l1 / N, w_sl1 / N, w_ncc / b, w_lncc / (b h w) (the sum forms: without the divisors, lncc times c)
 struct recon_bw { double cm, cl, cs, cn, cw, beta; int kinds; };
 
-// Channel rows.  CT = 1: one float per pixel (the flagship image); CT = 4: one 16-byte load / store per pixel; CT = 0: runtime channel
-// count, loops unrolled over MAXC with the tail switched off.  The arithmetic and its order are the same in all three; contraction is off.
-template <int CT> __device__ __forceinline__ void rrow_load(const float* __restrict__ base, int64_t i, int c, float* v) {
-    if (CT == 4) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(base + i * 4);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else if (CT == 1) {
-        v[0] = base[i];
-    } else {
-#pragma unroll
-        for (int k = 0; k < MAXC; ++k) if (k < c) v[k] = base[i * c + k];
-    }
-}
-template <int CT> __device__ __forceinline__ void rrow_store(float* __restrict__ base, int64_t i, int c, const float* v) {
-    if (CT == 4) {
-        *reinterpret_cast<f32x4*>(base + i * 4) = f32x4{v[0], v[1], v[2], v[3]};
-    } else if (CT == 1) {
-        base[i] = v[0];
-    } else {
-#pragma unroll
-        for (int k = 0; k < MAXC; ++k) if (k < c) base[i * c + k] = v[k];
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ streaming kinds, forward
 // grid (blocks of a sample, sample); partial[b][block][3 + 5c]: sum d^2, sum |d|, sum smooth-l1(d), then per channel sum x, t, x^2, t^2, x t
 // of the masked-in pixels (a masked-out pixel has J = I = 0 and adds nothing).  Every entry is written (0 for a kind that is not selected).
@@ -62,8 +36,8 @@ __global__ __launch_bounds__(EB) void recon_stream_partial_kernel(const float* _
                                                                    const uint8_t* __restrict__ mask, int64_t hw, int c_rt, int64_t t_stride,
                                                                    int kinds, double beta, double* __restrict__ partial) {
 #pragma clang fp contract(off)
-    constexpr int NC = CT ? CT : MAXC;
-    constexpr int NV = RECON_PW_SCALARS + 5 * MAXC;
+    constexpr int NC = CT ? CT : CTL_ROW_MAXC;
+    constexpr int NV = RECON_PW_SCALARS + 5 * CTL_ROW_MAXC;
     __shared__ double sm[EB / 64][NV];
     const int c = CT ? CT : c_rt;
     const int64_t b = blockIdx.y;
@@ -80,8 +54,8 @@ __global__ __launch_bounds__(EB) void recon_stream_partial_kernel(const float* _
     for (int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x; i < hw; i += stride) {
         if (mk && mk[i] == 0) continue;
         float xv[NC], tv[NC];
-        rrow_load<CT>(x, i, c, xv);
-        rrow_load<CT>(t, i, c, tv);
+        ctl_row_load<CT>(x, i, c, xv);
+        ctl_row_load<CT>(t, i, c, tv);
 #pragma unroll
         for (int k = 0; k < NC; ++k) if (k < c) {
             const double xd = (double)xv[k], td = (double)tv[k], d = xd - td, n = fabs(d);
@@ -100,13 +74,8 @@ __global__ __launch_bounds__(EB) void recon_stream_partial_kernel(const float* _
 #pragma unroll
         for (int q = 0; q < 5; ++q) { const double a = wave_sum_double(ch[q][k]); if (first) sm[wv][RECON_PW_SCALARS + 5 * k + q] = a; }
     }
-    __syncthreads();
     const int nv = RECON_PW_SCALARS + 5 * c;
-    if ((int)threadIdx.x < nv) {
-        double a = 0.0;
-        for (int i = 0; i < EB / 64; ++i) a += sm[i][threadIdx.x];
-        partial[(b * gridDim.x + blockIdx.x) * nv + threadIdx.x] = a;
-    }
+    CTL_BLOCK_ROWS_STORE(sm, EB / 64, nv, partial + (b * gridDim.x + blockIdx.x) * nv);
 }
 
 // ------------------------------------------------------------------------------------------------ 'lncc': the separable window sums
@@ -146,7 +115,7 @@ __global__ __launch_bounds__(EB) void recon_lncc_fwd_kernel(const float* __restr
                                                              int win, int tiles_y, int tiles_x, double* __restrict__ maps,
                                                              double* __restrict__ partial) {
 #pragma clang fp contract(off)
-    constexpr int NC = CT ? CT : MAXC;
+    constexpr int NC = CT ? CT : CTL_ROW_MAXC;
     constexpr int T = RECON_T;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     __shared__ double sm[EB / 64];
@@ -171,8 +140,8 @@ __global__ __launch_bounds__(EB) void recon_lncc_fwd_kernel(const float* __restr
             if (on) {
                 float xv[NC], tv[NC];
                 const int64_t pix = (int64_t)gy * w + gx;
-                rrow_load<CT>(x, pix, c, xv);
-                rrow_load<CT>(t, pix, c, tv);
+                ctl_row_load<CT>(x, pix, c, xv);
+                ctl_row_load<CT>(t, pix, c, tv);
 #pragma unroll
                 for (int k = 0; k < NC; ++k) if (k < c) {
                     const double jd = (double)xv[k], id = (double)tv[k];
@@ -242,7 +211,7 @@ __global__ __launch_bounds__(EB) void recon_finalize_kernel(const double* __rest
             }
         }
 #pragma unroll
-        for (int q = 0; q < 5; ++q) for (int o = 8; o > 0; o >>= 1) v[q] += __shfl_xor(v[q], o);
+        for (int q = 0; q < 5; ++q) CTL_GROUP16_SUM(v[q]);
         if (ok && lane == 0) {
 #pragma unroll
             for (int q = 0; q < 5; ++q) chs[(int64_t)it * 5 + q] = v[q];
@@ -314,7 +283,7 @@ __global__ __launch_bounds__(EB) void recon_stream_bwd_kernel(const float* __res
                                                                const double* __restrict__ coefb, const double* __restrict__ bars, int64_t hw,
                                                                int c_rt, int64_t t_stride, recon_bw kb, float* __restrict__ dxs) {
 #pragma clang fp contract(off)
-    constexpr int NC = CT ? CT : MAXC;
+    constexpr int NC = CT ? CT : CTL_ROW_MAXC;
     const int c = CT ? CT : c_rt;
     const int64_t b = blockIdx.y;
     const float* __restrict__ x = xs + b * hw * c;
@@ -334,15 +303,15 @@ __global__ __launch_bounds__(EB) void recon_stream_bwd_kernel(const float* __res
         if (mk && mk[i] == 0) {
 #pragma unroll
             for (int k = 0; k < NC; ++k) xv[k] = 0.f;
-            rrow_store<CT>(dx, i, c, xv);
+            ctl_row_store<CT>(dx, i, c, xv);
             continue;
         }
-        rrow_load<CT>(x, i, c, xv);
-        rrow_load<CT>(t, i, c, tv);
+        ctl_row_load<CT>(x, i, c, xv);
+        ctl_row_load<CT>(t, i, c, tv);
 #pragma unroll
         for (int k = 0; k < NC; ++k) if (k < c)
             xv[k] = (float)(go * recon_pw_grad((double)xv[k], (double)tv[k], kb, alpha, bet, xbar[k], tbar[k]));
-        rrow_store<CT>(dx, i, c, xv);
+        ctl_row_store<CT>(dx, i, c, xv);
     }
 }
 
@@ -355,7 +324,7 @@ __global__ __launch_bounds__(EB) void recon_lncc_bwd_kernel(const float* __restr
                                                              const double* __restrict__ maps, int b, int h, int w, int c_rt, int64_t t_stride,
                                                              int win, int tiles_y, int tiles_x, recon_bw kb, float* __restrict__ dxs) {
 #pragma clang fp contract(off)
-    constexpr int NC = CT ? CT : MAXC;
+    constexpr int NC = CT ? CT : CTL_ROW_MAXC;
     constexpr int T = RECON_T;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int c = CT ? CT : c_rt;
@@ -387,8 +356,8 @@ __global__ __launch_bounds__(EB) void recon_lncc_bwd_kernel(const float* __restr
 #pragma unroll
                 for (int k = 0; k < NC; ++k) xv[k] = 0.f;
             } else {
-                rrow_load<CT>(xs + s * (int64_t)h * w * c, pix, c, xv);
-                rrow_load<CT>(ts + s * t_stride, pix, c, tv);
+                ctl_row_load<CT>(xs + s * (int64_t)h * w * c, pix, c, xv);
+                ctl_row_load<CT>(ts + s * t_stride, pix, c, tv);
                 const double alpha = coefb[s * 2], bet = coefb[s * 2 + 1];
 #pragma unroll
                 for (int k = 0; k < NC; ++k) if (k < c) {
@@ -399,27 +368,18 @@ __global__ __launch_bounds__(EB) void recon_lncc_bwd_kernel(const float* __restr
                     xv[k] = (float)(go * g);
                 }
             }
-            rrow_store<CT>(dx, pix, c, xv);
+            ctl_row_store<CT>(dx, pix, c, xv);
         }
         __syncthreads();
     }
 }
 
 // ------------------------------------------------------------------------------------------------ launchers
-static inline int recon_sample_blocks(int64_t b, int64_t hw, int cap) {
-    int64_t nb = ctl_cdiv64(hw, EB), lim = cap / b;
-    if (lim < 1) lim = 1;
-    return (int)(nb < lim ? nb : lim);
-}
-static inline int recon_tile_blocks(int64_t b, int h, int w) {
-    const int64_t n = b * ctl_cdiv(h, RECON_T) * ctl_cdiv(w, RECON_T);
-    return (int)(n < RECON_MAX_TILE_BLOCKS ? n : RECON_MAX_TILE_BLOCKS);
-}
 static int recon_check(const char* who, int kinds, int64_t b, int64_t h, int64_t w, int c, int win, double beta) {
     CTL_REQUIRE(kinds > 0 && (kinds & ~RECON_ALL) == 0, "%s: kinds 0x%x (a non-empty set of the bits 0x01 .. 0x10)", who, kinds);
     CTL_REQUIRE(b > 0 && h > 0 && w > 0, "%s: sizes must be positive (batch %lld, plane %lld x %lld)", who, (long long)b, (long long)h, (long long)w);
-    CTL_REQUIRE(c >= 1 && c <= MAXC, "%s: c = %d channels (1 .. %d)", who, c, MAXC);
-    CTL_REQUIRE(b <= 65535, "%s: batch %lld (at most 65535 samples)", who, (long long)b);
+    CTL_REQUIRE(c >= 1 && c <= CTL_ROW_MAXC, "%s: c = %d channels (1 .. %d)", who, c, CTL_ROW_MAXC);
+    if (int rc = ctl_check_batch(who, b)) return rc;
     CTL_REQUIRE(h < ((int64_t)1 << 31) / w && b * h * w < ((int64_t)1 << 31) / c,
                 "%s: %lld x %lld x %lld pixels of %d channels reach the limit of 2^31 elements", who, (long long)b, (long long)h, (long long)w, c);
     if (kinds & CTL_RECON_SMOOTH_L1) CTL_REQUIRE(std::isfinite(beta) && beta > 0.0, "%s: beta = %g (smooth l1 needs a finite beta > 0)", who, beta);
@@ -430,21 +390,12 @@ static int recon_check(const char* who, int kinds, int64_t b, int64_t h, int64_t
     }
     return CTL_OK;
 }
-static int recon_weights(const char* who, int kinds, const double* weights, recon_wk* wk) {
-    CTL_REQUIRE(weights, "%s: null pointer (weights: one double per kind)", who);
-    for (int k = 0; k < RECON_NK; ++k) {
-        const bool on = (kinds >> k) & 1;
-        CTL_REQUIRE(!on || std::isfinite(weights[k]), "%s: the weight of kind %d is %g (finite)", who, k, weights[k]);
-        wk->v[k] = on ? weights[k] : 0.0;
-    }
-    return CTL_OK;
-}
 
 struct recon_layout { size_t coefb, bars, chs, pw, lp, maps, total; int nb, ncb; };
 static recon_layout recon_ws(int kinds, int64_t b, int h, int w, int c) {
     recon_layout l;
-    l.nb = recon_sample_blocks(b, (int64_t)h * w, CTL_RED_BLOCKS);
-    l.ncb = recon_tile_blocks(b, h, w);
+    l.nb = ctl_sample_blocks(b, (int64_t)h * w, EB, CTL_RED_BLOCKS);
+    l.ncb = ctl_tile_blocks(b, h, w, RECON_T, RECON_MAX_TILE_BLOCKS);
     l.coefb = 0;
     l.bars = l.coefb + (size_t)b * 2;
     l.chs = l.bars + (size_t)b * c * 2;
@@ -471,24 +422,20 @@ extern "C" int ctl_recon_loss_fwd(int32_t kinds, const double* weights, const fl
     if (int rc = recon_check("recon_loss_fwd", kinds, b, h, w, c, win, beta)) return rc;
     CTL_REQUIRE(t_batch == 1 || t_batch == b, "recon_loss_fwd: t_batch = %d (1, or the batch %d)", t_batch, b);
     recon_wk wk;
-    if (int rc = recon_weights("recon_loss_fwd", kinds, weights, &wk)) return rc;
+    if (int rc = ctl_kind_weights("recon_loss_fwd", kinds, RECON_NK, weights, wk.v)) return rc;
     const recon_layout l = recon_ws(kinds, b, h, w, c);
     const int64_t hw = (int64_t)h * w, t_stride = t_batch == 1 ? 0 : hw * c;
     const bool v4 = ctl_vec4(c, x, t);
     int extra = 0;
     if (kinds & RECON_STREAM) {
         const dim3 grid(l.nb, b);
-        if (c == 1) recon_stream_partial_kernel<1><<<grid, dim3(EB), 0, S_>>>(x, t, mask, hw, c, t_stride, kinds, beta, ws + l.pw);
-        else if (v4) recon_stream_partial_kernel<4><<<grid, dim3(EB), 0, S_>>>(x, t, mask, hw, c, t_stride, kinds, beta, ws + l.pw);
-        else recon_stream_partial_kernel<0><<<grid, dim3(EB), 0, S_>>>(x, t, mask, hw, c, t_stride, kinds, beta, ws + l.pw);
+        CTL_ROW_DISPATCH_C1(recon_stream_partial_kernel, c, v4, grid, 0, x, t, mask, hw, c, t_stride, kinds, beta, ws + l.pw);
         ++extra;
     }
     if (kinds & CTL_RECON_LNCC) {
         const int ty = ctl_cdiv(h, RECON_T), tx = ctl_cdiv(w, RECON_T);
         const size_t lds = recon_lds(win, 5);
-        if (c == 1) recon_lncc_fwd_kernel<1><<<dim3(l.ncb), dim3(EB), lds, S_>>>(x, t, mask, b, h, w, c, t_stride, win, ty, tx, ws + l.maps, ws + l.lp);
-        else if (v4) recon_lncc_fwd_kernel<4><<<dim3(l.ncb), dim3(EB), lds, S_>>>(x, t, mask, b, h, w, c, t_stride, win, ty, tx, ws + l.maps, ws + l.lp);
-        else recon_lncc_fwd_kernel<0><<<dim3(l.ncb), dim3(EB), lds, S_>>>(x, t, mask, b, h, w, c, t_stride, win, ty, tx, ws + l.maps, ws + l.lp);
+        CTL_ROW_DISPATCH_C1(recon_lncc_fwd_kernel, c, v4, dim3(l.ncb), lds, x, t, mask, b, h, w, c, t_stride, win, ty, tx, ws + l.maps, ws + l.lp);
         ++extra;
     }
     recon_finalize_kernel<<<dim3(1), dim3(EB), 0, S_>>>((kinds & RECON_STREAM) ? ws + l.pw : nullptr, b, l.nb, c, (double)hw,
@@ -506,7 +453,7 @@ extern "C" int ctl_recon_loss_bwd(int32_t kinds, const double* weights, const fl
     if (int rc = recon_check("recon_loss_bwd", kinds, b, h, w, c, win, beta)) return rc;
     CTL_REQUIRE(t_batch == 1 || t_batch == b, "recon_loss_bwd: t_batch = %d (1, or the batch %d)", t_batch, b);
     recon_wk wk;
-    if (int rc = recon_weights("recon_loss_bwd", kinds, weights, &wk)) return rc;
+    if (int rc = ctl_kind_weights("recon_loss_bwd", kinds, RECON_NK, weights, wk.v)) return rc;
     const recon_layout l = recon_ws(kinds, b, h, w, c);
     const int64_t hw = (int64_t)h * w, t_stride = t_batch == 1 ? 0 : hw * c;
     const double nel = reduce_sum ? 1.0 : (double)b * (double)c * (double)hw;
@@ -522,14 +469,10 @@ extern "C" int ctl_recon_loss_bwd(int32_t kinds, const double* weights, const fl
     if (kinds & CTL_RECON_LNCC) {
         const int ty = ctl_cdiv(h, RECON_T), tx = ctl_cdiv(w, RECON_T);
         const size_t lds = recon_lds(win, 3);
-        if (c == 1) recon_lncc_bwd_kernel<1><<<dim3(l.ncb), dim3(EB), lds, S_>>>(x, t, mask, gout, ws + l.coefb, ws + l.bars, ws + l.maps, b, h, w, c, t_stride, win, ty, tx, kb, dx);
-        else if (v4) recon_lncc_bwd_kernel<4><<<dim3(l.ncb), dim3(EB), lds, S_>>>(x, t, mask, gout, ws + l.coefb, ws + l.bars, ws + l.maps, b, h, w, c, t_stride, win, ty, tx, kb, dx);
-        else recon_lncc_bwd_kernel<0><<<dim3(l.ncb), dim3(EB), lds, S_>>>(x, t, mask, gout, ws + l.coefb, ws + l.bars, ws + l.maps, b, h, w, c, t_stride, win, ty, tx, kb, dx);
+        CTL_ROW_DISPATCH_C1(recon_lncc_bwd_kernel, c, v4, dim3(l.ncb), lds, x, t, mask, gout, ws + l.coefb, ws + l.bars, ws + l.maps, b, h, w, c, t_stride, win, ty, tx, kb, dx);
     } else {
-        const dim3 grid(recon_sample_blocks(b, hw, RECON_MAX_STREAM_BLOCKS), b);
-        if (c == 1) recon_stream_bwd_kernel<1><<<grid, dim3(EB), 0, S_>>>(x, t, mask, gout, ws + l.coefb, ws + l.bars, hw, c, t_stride, kb, dx);
-        else if (v4) recon_stream_bwd_kernel<4><<<grid, dim3(EB), 0, S_>>>(x, t, mask, gout, ws + l.coefb, ws + l.bars, hw, c, t_stride, kb, dx);
-        else recon_stream_bwd_kernel<0><<<grid, dim3(EB), 0, S_>>>(x, t, mask, gout, ws + l.coefb, ws + l.bars, hw, c, t_stride, kb, dx);
+        const dim3 grid(ctl_sample_blocks(b, hw, EB, RECON_MAX_STREAM_BLOCKS), b);
+        CTL_ROW_DISPATCH_C1(recon_stream_bwd_kernel, c, v4, grid, 0, x, t, mask, gout, ws + l.coefb, ws + l.bars, hw, c, t_stride, kb, dx);
     }
     CTL_LAUNCH_CHECK("recon_loss_bwd");
     return CTL_OK;

@@ -86,6 +86,8 @@ __device__ __forceinline__ void tta_fetch(const float* __restrict__ src, int tr,
     __syncthreads();      // the next member may overwrite the tile
 }
 
+// (rows here are unrolled over the tile form's NC, 4 or 16, not over CTL_ROW_MAXC, and the softmax below likewise: ctl_row_load /
+// ctl_row_store / ctl_row_exp of ctl_rows.h have no such form, so this file keeps its own)
 template <int NC, bool VEC> __device__ __forceinline__ void tta_store(float* __restrict__ dst, int64_t at, int c, const float* v) {
     if (VEC) {
         *reinterpret_cast<f32x4*>(dst + at * 4) = f32x4{v[0], v[1], v[2], v[3]};

@@ -7,44 +7,18 @@
 //
 // A label outside 0..c-1 is no class: the pixel gets its maps and enters none of the labelled sums.  Labels are only ever compared with
 // a class index.
-#include <cmath>
-#include "ctl_device.h"
+#include "ctl_rows.h"
 
-#define UB 256                    // threads per block
-#define MAXC 16
+#define UB CTL_ROW_THREADS          // threads per block
 #define UNCERT_MAX_BLOCKS 2048    // blocks over all slices of the streaming pass: the number of partial rows, part of the result's bits
 
-// Channel rows, the two forms of ctl_loss.hip (which keeps its own copies private).  CT = 4: one 16-byte load / store per pixel; CT = 0:
-// runtime channel count, loops unrolled over MAXC with the tail switched off.  The arithmetic and its order are the same in both;
-// contraction is off in every function below so that neither form turns a product and a sum into an fma the other one keeps apart.
-template <int CT> __device__ __forceinline__ void urow_load(const float* __restrict__ base, int64_t i, int c, float* v) {
-    if (CT == 4) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(base + i * 4);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < MAXC; ++k) if (k < c) v[k] = base[i * c + k];
-    }
-}
-template <int CT> __device__ __forceinline__ void urow_store(float* __restrict__ base, int64_t i, int c, const float* v) {
-    if (CT == 4) {
-        *reinterpret_cast<f32x4*>(base + i * 4) = f32x4{v[0], v[1], v[2], v[3]};
-    } else {
-#pragma unroll
-        for (int k = 0; k < MAXC; ++k) if (k < c) base[i * c + k] = v[k];
-    }
-}
 // v <- softmax(v) with a true division (uniform logits give exactly float(1) / float(c)); returns log of the sum of exp(v - max),
 // `m` = the row maximum: log p_k = v_k - m - (the return value) without going through p_k, which underflows for a far-off class
 template <int CT> __device__ __forceinline__ float urow_softmax(float* v, int c, float& m) {
 #pragma clang fp contract(off)
-    constexpr int NC = CT ? CT : MAXC;
-    m = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < NC; ++k) if (k < c) m = fmaxf(m, v[k]);
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < NC; ++k) if (k < c) { v[k] = expf(v[k] - m); s += v[k]; }
+    constexpr int NC = CT ? CT : CTL_ROW_MAXC;
+    float s;
+    m = ctl_row_exp<CT>(v, c, s);
 #pragma unroll
     for (int k = 0; k < NC; ++k) if (k < c) v[k] = v[k] / s;
     return logf(s);
@@ -52,7 +26,7 @@ template <int CT> __device__ __forceinline__ float urow_softmax(float* v, int c,
 // -sum_k p_k log2(p_k + eps) in bits; a term whose p_k + eps is 0 contributes 0
 template <int CT> __device__ __forceinline__ float urow_entropy(const float* p, int c, float eps) {
 #pragma clang fp contract(off)
-    constexpr int NC = CT ? CT : MAXC;
+    constexpr int NC = CT ? CT : CTL_ROW_MAXC;
     float h = 0.f;
 #pragma unroll
     for (int k = 0; k < NC; ++k) if (k < c) {
@@ -71,7 +45,7 @@ __global__ __launch_bounds__(UB) void uncert_partial_kernel(const float* __restr
                                                              int64_t hw, int c_rt, int B, float eps, int is_prob, uncert_maps o,
                                                              double* __restrict__ pstats, unsigned long long* __restrict__ pbins) {
 #pragma clang fp contract(off)
-    constexpr int NC = CT ? CT : MAXC;
+    constexpr int NC = CT ? CT : CTL_ROW_MAXC;
     __shared__ float edge[CTL_UNCERT_MAX_BINS];
     __shared__ unsigned long long bcc[CTL_UNCERT_MAX_BINS], bsum[CTL_UNCERT_MAX_BINS];      // bcc: count | correct << 32, one atomic for both
     __shared__ double sm[UB / 64][6];
@@ -98,7 +72,7 @@ __global__ __launch_bounds__(UB) void uncert_partial_kernel(const float* __restr
         float M = -INFINITY, S = 0.f;      // running log-sum-exp of the members' log p_y
         for (int t = 0; t < T; ++t) {
             float v[NC];
-            urow_load<CT>(logit + ((int64_t)t * n + b) * hw * c, i, c, v);
+            ctl_row_load<CT>(logit + ((int64_t)t * n + b) * hw * c, i, c, v);
             float vl = 0.f;                // the label's entry of the row as it was read
 #pragma unroll
             for (int k = 0; k < NC; ++k) if (k < c) vl = (l == (int64_t)k) ? v[k] : vl;
@@ -136,7 +110,7 @@ __global__ __launch_bounds__(UB) void uncert_partial_kernel(const float* __restr
         if (o.mi) o.mi[at] = MI;
         if (o.conf) o.conf[at] = conf;
         if (o.pred) o.pred[at] = (uint8_t)yh;
-        if (o.mean_prob) urow_store<CT>(o.mean_prob + b * hw * c, i, c, pb);
+        if (o.mean_prob) ctl_row_store<CT>(o.mean_prob + b * hw * c, i, c, pb);
         aH += (double)H;
         aMI += (double)MI;
         if (valid) {
@@ -186,26 +160,21 @@ __global__ __launch_bounds__(UB) void uncert_finalize_kernel(const double* __res
             const int col = base + grp;
             unsigned long long s = 0ull;
             if (col < ncol) for (int j = lane; j < nb; j += 16) s += pbins[(b * nb + j) * ncol + col];
-            for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o);
+            CTL_GROUP16_SUM(s);
             if (col < ncol && lane == 0) bins[b * ncol + col] = (int64_t)s;
         }
     }
     double s = 0.0;
     if (grp < 6) for (int j = lane; j < nb; j += 16) s += pstats[(b * nb + j) * 6 + grp];
-    for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    CTL_GROUP16_SUM(s);
     if (stats && grp < 6 && lane == 0) stats[b * 6 + grp] = s;
 }
 
 // ------------------------------------------------------------------------------------------------ launchers
-static inline int slice_blocks(int64_t n, int64_t hw) {
-    int64_t nb = ctl_cdiv64(hw, UB), lim = UNCERT_MAX_BLOCKS / n;
-    if (lim < 1) lim = 1;
-    return (int)(nb < lim ? nb : lim);
-}
 static int uncert_check(const char* who, int T, int64_t n, int64_t hw, int c, int B) {
     CTL_REQUIRE(T >= 1 && T <= CTL_UNCERT_MAX_MEMBERS, "%s: %d members (1 .. %d)", who, T, CTL_UNCERT_MAX_MEMBERS);
     CTL_REQUIRE(n > 0 && hw > 0, "%s: sizes must be positive (slices %lld, pixels per slice %lld)", who, (long long)n, (long long)hw);
-    CTL_REQUIRE(c >= 1 && c <= MAXC, "%s: %d classes (1 .. %d)", who, c, MAXC);
+    if (int rc = ctl_check_channels(who, c, "classes")) return rc;
     CTL_REQUIRE(B >= 1 && B <= CTL_UNCERT_MAX_BINS, "%s: %d reliability bins (1 .. %d)", who, B, CTL_UNCERT_MAX_BINS);
     CTL_REQUIRE(n <= 65535, "%s: %lld slices (at most 65535)", who, (long long)n);
     const int64_t row_bytes = c * 4 > 8 ? c * 4 : 8;      // logits: c floats per pixel and member, labels: 8 bytes per pixel
@@ -216,7 +185,7 @@ static int uncert_check(const char* who, int T, int64_t n, int64_t hw, int c, in
 
 extern "C" size_t ctl_predictive_stats_ws_bytes(int32_t T, int32_t n, int64_t hw, int32_t C, int32_t B) {
     if (uncert_check("predictive_stats_ws_bytes", T, n, hw, C, B) != CTL_OK) return 0;
-    const size_t rows = (size_t)n * slice_blocks(n, hw);
+    const size_t rows = (size_t)n * ctl_sample_blocks(n, hw, UB, UNCERT_MAX_BLOCKS);
     return ctl_align256(rows * 6 * sizeof(double)) + rows * B * 3 * sizeof(unsigned long long);
 }
 extern "C" int ctl_predictive_stats(const float* logits, const int64_t* label, int32_t T, int32_t n, int64_t hw, int32_t C, int32_t B, float eps,
@@ -226,16 +195,13 @@ extern "C" int ctl_predictive_stats(const float* logits, const int64_t* label, i
     if (int rc = uncert_check("predictive_stats", T, n, hw, C, B)) return rc;
     CTL_REQUIRE(std::isfinite(eps) && eps >= 0.f, "predictive_stats: eps %g (finite, >= 0)", (double)eps);
     CTL_REQUIRE(workspace && ((uintptr_t)workspace & 7) == 0, "predictive_stats: null or misaligned workspace (8-byte alignment)");
-    const int nb = slice_blocks(n, hw);
+    const int nb = ctl_sample_blocks(n, hw, UB, UNCERT_MAX_BLOCKS);
     const size_t rows = (size_t)n * nb;
     double* pstats = (double*)workspace;
     unsigned long long* pbins = (unsigned long long*)((char*)workspace + ctl_align256(rows * 6 * sizeof(double)));
     const uncert_maps o{entropy, mi, conf, pred, mean_prob};
     const dim3 grid(nb, n);
-    if (ctl_vec4(C, logits, mean_prob))
-        uncert_partial_kernel<4><<<grid, dim3(UB), 0, S_>>>(logits, label, T, n, hw, C, B, eps, is_prob != 0, o, pstats, pbins);
-    else
-        uncert_partial_kernel<0><<<grid, dim3(UB), 0, S_>>>(logits, label, T, n, hw, C, B, eps, is_prob != 0, o, pstats, pbins);
+    CTL_ROW_DISPATCH(uncert_partial_kernel, ctl_vec4(C, logits, mean_prob), grid, logits, label, T, n, hw, C, B, eps, is_prob != 0, o, pstats, pbins);
     if (stats || bins) {
         uncert_finalize_kernel<<<dim3(n), dim3(UB), 0, S_>>>(pstats, pbins, nb, B, stats, bins);
         ctl_count_launches(1);      // partial + finalize

@@ -38,6 +38,22 @@ SMOOTH = 0.01
 DIST_LOSS_NAMES = ("boundary", "hausdorff dt")
 LOSS_NAMES = ("cross entropy", "weighted cross entropy", "dice", "weighted dice", "foreground dice", "focal") + DIST_LOSS_NAMES
 NO_CLASS = 255      # the confident label of a pixel where no class has more than half of the probability
+MAX_CLASSES = 16    # channels of a logit / image tensor the loss and statistics kernels take (CTL_ROW_MAXC of csrc/ctl_rows.h); stated once, here
+
+
+def check_mask(mask, shape):
+    """ValueError unless the per-pixel mask (or None) of [B,C,H,W] tensors is [B,1,H,W] or [B,H,W]."""
+    b, _, h, w = shape
+    if mask is not None and tuple(mask.shape) not in ((b, 1, h, w), (b, h, w)):
+        raise ValueError(f"the mask is per pixel: [{b},1,{h},{w}] or [{b},{h},{w}], got {tuple(mask.shape)}")
+
+
+def mask01(mask, shape, dtype, device):
+    """The mask of [B,C,H,W] tensors as [B,1,H,W] zeros and ones, nonzero -> 1; ones without a mask."""
+    b, _, h, w = shape
+    if mask is None:
+        return torch.ones((b, 1, h, w), dtype=dtype, device=device)
+    return (mask.detach().reshape(b, 1, h, w) != 0).to(device=device, dtype=dtype)
 
 
 def parse_loss_type(loss_type, class_weights=None, num_classes=None):

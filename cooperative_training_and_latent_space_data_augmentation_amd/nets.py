@@ -31,6 +31,7 @@ import torch.nn as nn
 
 from . import _ffi, init as _init
 from ._ffi import lib, check, OP_DTYPE
+from .losses import MAX_CLASSES
 
 (S_X, S_P, S_B, S_NBT, S_WP, S_ACT, S_SCR, S_OUT0, S_OUT1, S_DOUT0, S_DOUT1, S_GRAD, S_DX, S_BSCR, S_TAB, S_STATE, S_KEEP) = range(17)
 N_SLOTS = 17
@@ -1736,7 +1737,7 @@ class MyDecoder(CtlNet):
 
 
 # ------------------------------------------------------------------------------------------------ the supported configurations
-LABEL_MAXC = 16          # the label-space kernels (softmax, cross-entropy, one-hot, argmax) keep a pixel's class row in registers: MAXC, csrc/ctl_elem.hip
+LABEL_MAXC = MAX_CLASSES      # the label-space kernels (softmax, cross-entropy, one-hot, argmax) keep a pixel's class row in registers: CTL_ROW_MAXC, csrc/ctl_rows.h
 
 
 def conv_channels_ok(c: int) -> bool:

@@ -14,6 +14,7 @@ import torch
 
 from . import _ffi
 from ._ffi import lib, call
+from .losses import MAX_CLASSES      # 16: channel rows of the loss / statistics kernels
 
 
 def stream_ptr() -> int:
@@ -75,6 +76,43 @@ def _workspace(query: str, *dims, device, dtype=torch.uint8, floor: int = 1):
     """(tensor, size) for the library's size query `query(*dims)`: a `dtype` device tensor of max(size, floor) elements."""
     size = getattr(lib, query)(*dims)
     return torch.empty(max(size, floor), dtype=dtype, device=device), size
+
+
+def _nhwc_f32(who: str, text: str, *tensors, also: bool = True) -> None:
+    """ValueError(f"{who}: {text}") unless every tensor is 4-D fp32 and NHWC in memory (and `also` holds)."""
+    if not (all(t.dim() == 4 and t.dtype == torch.float32 and t.permute(0, 2, 3, 1).is_contiguous() for t in tensors) and also):
+        raise ValueError(f"{who}: {text}")
+
+
+def _kind_bits(kinds, table, what: str, who: str):
+    """(bits, c_double array of len(table)) of a {name: weight} mapping over the {name: bit} `table`; bit t is kind t, the order of the weights."""
+    if not kinds:
+        raise ValueError(f"{who}: `kinds` maps at least one name to its weight")
+    for name in kinds:
+        if name not in table:
+            raise NotImplementedError(f"{what} {name!r} (one of {', '.join(table)})")
+    bits, weights = 0, [0.0] * len(table)
+    for name, weight in kinds.items():
+        bits |= table[name]
+        weights[table[name].bit_length() - 1] = float(weight)
+    return bits, (C.c_double * len(weights))(*weights)
+
+
+def _class_weight_array(class_weights, c: int):
+    """One double per class of a host sequence (the library normalises it in fp64)."""
+    vals = [float(v) for v in class_weights]
+    if len(vals) != c:
+        raise ValueError(f"each class must have a weight: expected {c} weights, got {len(vals)}")
+    return (C.c_double * c)(*vals)
+
+
+def _pixel_mask(mask, n: int, h: int, w: int, who: str):
+    """A per-pixel mask [n,1,h,w] or [n,h,w] of any dtype as contiguous uint8, nonzero = 1 (None stays None)."""
+    if mask is None:
+        return None
+    if tuple(mask.shape) not in ((n, 1, h, w), (n, h, w)):
+        raise ValueError(f"{who}: the mask is per pixel, [{n},1,{h},{w}] or [{n},{h},{w}], got {tuple(mask.shape)}")
+    return mask if mask.dtype == torch.uint8 and mask.is_contiguous() else (mask != 0).to(torch.uint8).contiguous()
 
 
 # ---------------------------------------------------------------------------------------------- conv (unit-level API)
@@ -255,14 +293,9 @@ def _loss_args(logit, label, kind, class_weights):
             tuple(label.shape) != (logit.shape[0], logit.shape[2], logit.shape[3]):
         raise ValueError("segmentation loss: expected fp32 logits [B,C,H,W] and an int64 label map [B,H,W]")
     n, c, h, w = logit.shape
-    if not (logit.permute(0, 2, 3, 1).is_contiguous() and label.is_contiguous()):
-        raise ValueError("segmentation loss: the logits must be NHWC in memory (channels_last) and the label map contiguous")
-    wts = None
-    if class_weights is not None and LOSS_KINDS[kind] == _ffi.LOSS_WCE:      # a host sequence: the library normalises it in fp64
-        vals = [float(v) for v in class_weights]
-        if len(vals) != c:
-            raise ValueError(f"each class must have a weight: expected {c} weights, got {len(vals)}")
-        wts = (C.c_double * c)(*vals)
+    _nhwc_f32("segmentation loss", "the logits must be NHWC in memory (channels_last) and the label map contiguous", logit,
+              also=label.is_contiguous())
+    wts = _class_weight_array(class_weights, c) if class_weights is not None and LOSS_KINDS[kind] == _ffi.LOSS_WCE else None
     return LOSS_KINDS[kind], n, h * w, c, wts
 
 
@@ -288,7 +321,6 @@ def seg_loss_bwd(logit, label, kind, gout, ws=None, class_weights=None, gamma=2.
 DIST_LOSS_KINDS = {"boundary": _ffi.DLOSS_BOUNDARY, "hausdorff dt": _ffi.DLOSS_HAUSDORFF_DT}      # name -> CTL_DLOSS_* kind
 DIST_LOSS_FORM = {"boundary": "signed", "hausdorff dt": "squared"}                               # the training form of the label fields a loss reads
 FIELD_FORMS = {"d2": _ffi.FIELD_D2, "signed": _ffi.FIELD_SIGNED, "squared": _ffi.FIELD_SQUARED}
-MAX_CLASSES = 16
 
 
 def class_fields(label: torch.Tensor, n_class: int, form: str = "d2") -> torch.Tensor:
@@ -338,8 +370,8 @@ def _dist_loss_args(logit, label, kind, field_a, field_b):
         raise ValueError(f"{kind!r} needs at least 2 classes")
     for f in fields:
         _arg(f, torch.float32, (n, c, h, w), "distance-map loss", "a field")
-    if not (all(t.permute(0, 2, 3, 1).is_contiguous() for t in (logit,) + fields) and label.is_contiguous()):
-        raise ValueError("distance-map loss: the logits and the fields must be NHWC in memory (channels_last) and the label map contiguous")
+    _nhwc_f32("distance-map loss", "the logits and the fields must be NHWC in memory (channels_last) and the label map contiguous", logit,
+              *fields, also=label.is_contiguous())
     return DIST_LOSS_KINDS[kind], n, h * w, c
 
 
@@ -371,36 +403,18 @@ CONSISTENCY_KINDS = {"kl": _ffi.CONS_KL, "ce": _ffi.CONS_CE, "weighted ce": _ffi
 def _consistency_args(output, reference, kinds, class_weights, mask, who):
     """(kind bits, weights, class weights, mask as uint8, n, h, w, c) of a {name: weight} mapping `kinds`; names and weights are checked
     before the tensors are looked at."""
-    if not kinds:
-        raise ValueError(f"{who}: `kinds` maps at least one name to its weight")
-    for name in kinds:
-        if name not in CONSISTENCY_KINDS:
-            raise NotImplementedError(f"consistency loss {name!r} (one of {', '.join(CONSISTENCY_KINDS)})")
+    bits, weights = _kind_bits(kinds, CONSISTENCY_KINDS, "consistency loss", who)
     if "weighted ce" in kinds and class_weights is None:
         raise ValueError("'weighted ce' must be given class weights")
     require_gpu(output, reference, mask)
     if output.dim() != 4 or output.dtype != torch.float32 or reference.dtype != torch.float32 or tuple(reference.shape) != tuple(output.shape):
         raise ValueError(f"{who}: expected fp32 output and reference logits of one shape [B,C,H,W]")
-    if not (output.permute(0, 2, 3, 1).is_contiguous() and reference.permute(0, 2, 3, 1).is_contiguous()):
-        raise ValueError(f"{who}: output and reference must be NHWC in memory (channels_last)")
+    _nhwc_f32(who, "output and reference must be NHWC in memory (channels_last)", output, reference)
     n, c, h, w = (int(v) for v in output.shape)
     if "contour" in kinds and c < 2:
         raise ValueError("'contour' needs at least 2 classes (it runs over the classes 1 .. C-1)")
-    bits, weights = 0, [0.0] * len(CONSISTENCY_KINDS)
-    for name, weight in kinds.items():
-        bits |= CONSISTENCY_KINDS[name]
-        weights[CONSISTENCY_KINDS[name].bit_length() - 1] = float(weight)
-    wts = None
-    if class_weights is not None and "weighted ce" in kinds:
-        vals = [float(v) for v in class_weights]
-        if len(vals) != c:
-            raise ValueError(f"each class must have a weight: expected {c} weights, got {len(vals)}")
-        wts = (C.c_double * c)(*vals)
-    if mask is not None:
-        if tuple(mask.shape) not in ((n, 1, h, w), (n, h, w)):
-            raise ValueError(f"{who}: the mask is per pixel, [{n},1,{h},{w}] or [{n},{h},{w}], got {tuple(mask.shape)}")
-        mask = mask if mask.dtype == torch.uint8 and mask.is_contiguous() else (mask != 0).to(torch.uint8).contiguous()
-    return bits, (C.c_double * len(weights))(*weights), wts, mask, n, h, w, c
+    wts = _class_weight_array(class_weights, c) if class_weights is not None and "weighted ce" in kinds else None
+    return bits, weights, wts, _pixel_mask(mask, n, h, w, who), n, h, w, c
 
 
 def consistency_fwd(output, reference, kinds, class_weights=None, mask=None, is_gt=False):
@@ -431,8 +445,7 @@ def consistency_bwd(output, reference, kinds, gout, ws, class_weights=None, mask
 def _pool_args(x, scale, who):
     require_gpu(x)
     scale = int(scale)
-    if x.dim() != 4 or x.dtype != torch.float32 or not x.permute(0, 2, 3, 1).is_contiguous():
-        raise ValueError(f"{who}: expected an fp32 [B,C,H,W] tensor that is NHWC in memory (channels_last)")
+    _nhwc_f32(who, "expected an fp32 [B,C,H,W] tensor that is NHWC in memory (channels_last)", x)
     if not 1 <= scale <= 4:
         raise ValueError(f"{who}: scale {scale} (1 .. 4)")
     return scale, tuple(int(v) for v in x.shape)
@@ -467,11 +480,7 @@ RECON_KINDS = {"mse": _ffi.RECON_MSE, "l1": _ffi.RECON_L1, "smooth l1": _ffi.REC
 def _recon_args(x, t, kinds, mask, beta, win, reduction, who):
     """(kind bits, weights, mask as uint8, t's batch, n, h, w, c, reduce_sum) of a {name: weight} mapping `kinds`; names, weights and
     parameters are checked before the tensors are looked at."""
-    if not kinds:
-        raise ValueError(f"{who}: `kinds` maps at least one name to its weight")
-    for name in kinds:
-        if name not in RECON_KINDS:
-            raise NotImplementedError(f"image-similarity loss {name!r} (one of {', '.join(RECON_KINDS)})")
+    bits, weights = _kind_bits(kinds, RECON_KINDS, "image-similarity loss", who)
     if reduction == "none":
         raise NotImplementedError(f"{who}: reduction='none' is not offered on the device ('mean' or 'sum')")
     if reduction not in ("mean", "sum"):
@@ -484,22 +493,13 @@ def _recon_args(x, t, kinds, mask, beta, win, reduction, who):
     if x.dim() != 4 or t.dim() != 4 or x.dtype != torch.float32 or t.dtype != torch.float32 or tuple(t.shape[1:]) != tuple(x.shape[1:]) \
             or t.shape[0] not in (1, x.shape[0]):
         raise ValueError(f"{who}: expected an fp32 prediction [B,C,H,W] and an fp32 target of that shape or [1,C,H,W]")
-    if not (x.permute(0, 2, 3, 1).is_contiguous() and t.permute(0, 2, 3, 1).is_contiguous()):
-        raise ValueError(f"{who}: prediction and target must be NHWC in memory (channels_last)")
+    _nhwc_f32(who, "prediction and target must be NHWC in memory (channels_last)", x, t)
     n, c, h, w = (int(v) for v in x.shape)
-    if c > 16:
-        raise ValueError(f"{who}: {c} channels (1 .. 16)")
+    if c > MAX_CLASSES:
+        raise ValueError(f"{who}: {c} channels (1 .. {MAX_CLASSES})")
     if "lncc" in kinds and (win > h or win > w):
         raise ValueError(f"{who}: win = {win} is larger than the {h}x{w} plane")
-    bits, weights = 0, [0.0] * len(RECON_KINDS)
-    for name, weight in kinds.items():
-        bits |= RECON_KINDS[name]
-        weights[RECON_KINDS[name].bit_length() - 1] = float(weight)
-    if mask is not None:
-        if tuple(mask.shape) not in ((n, 1, h, w), (n, h, w)):
-            raise ValueError(f"{who}: the mask is per pixel, [{n},1,{h},{w}] or [{n},{h},{w}], got {tuple(mask.shape)}")
-        mask = mask if mask.dtype == torch.uint8 and mask.is_contiguous() else (mask != 0).to(torch.uint8).contiguous()
-    return bits, (C.c_double * len(weights))(*weights), mask, int(t.shape[0]), n, h, w, c, int(reduction == "sum")
+    return bits, weights, _pixel_mask(mask, n, h, w, who), int(t.shape[0]), n, h, w, c, int(reduction == "sum")
 
 
 def recon_loss_fwd(x, t, kinds, mask=None, beta=1.0 / 9, win=9, zero_mean=True, reduction="mean"):

@@ -44,8 +44,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .losses import MAX_CLASSES, check_mask, mask01
+
 RECON_NAMES = ("mse", "l1", "smooth l1", "ncc", "lncc")
-MAX_CHANNELS = 16
+MAX_CHANNELS = MAX_CLASSES
 EPS = 1e-6
 FLAT_RATIO, FLAG_LO, FLAG_HI = 2.0 ** -40, 2.0 ** -44, 2.0 ** -36
 
@@ -100,16 +102,7 @@ def check_pair(x, t, mask=None):
         raise ValueError(f"expected a prediction [B,C,H,W] and a target of that shape or [1,C,H,W], got {tuple(x.shape)} and {tuple(t.shape)}")
     if t.requires_grad:
         raise ValueError("the target is a constant: detach it (no gradient reaches the target)")
-    b, _, h, w = x.shape
-    if mask is not None and tuple(mask.shape) not in ((b, 1, h, w), (b, h, w)):
-        raise ValueError(f"the mask is per pixel: [{b},1,{h},{w}] or [{b},{h},{w}], got {tuple(mask.shape)}")
-
-
-def _mask01(mask, shape, dtype, device):
-    b, _, h, w = shape
-    if mask is None:
-        return torch.ones((b, 1, h, w), dtype=dtype, device=device)
-    return (mask.detach().reshape(b, 1, h, w) != 0).to(device=device, dtype=dtype)
+    check_mask(mask, x.shape)
 
 
 def box_sum(v, win):
@@ -189,7 +182,7 @@ def similarity_and_grad(x, t, kinds, weights=None, mask=None, *, beta=1.0 / 9, w
     check_params(terms, x.shape, beta, win, reduction)
     xd = x.detach().double().cpu()
     td = t.detach().double().cpu().expand_as(xd)
-    m = _mask01(None if mask is None else mask.cpu(), xd.shape, torch.float64, "cpu")
+    m = mask01(None if mask is None else mask.cpu(), xd.shape, torch.float64, "cpu")
     I, J = td * m, xd * m
     loss, grad = torch.zeros((), dtype=torch.float64), torch.zeros_like(xd)
     values, grads, maps = {}, {}, None
@@ -234,7 +227,7 @@ def _similarity_torch(x, t, terms, mask, beta, win, zero_mean, reduction):
     """The weighted total (or, reduction 'none' with a single kind, its unreduced form) from torch ops in x's float dtype."""
     x = x if x.is_floating_point() else x.float()
     t = t.detach().to(x.dtype).expand_as(x)
-    m = _mask01(mask, x.shape, x.dtype, x.device)
+    m = mask01(mask, x.shape, x.dtype, x.device)
     I, J = t * m, x * m
     red = (lambda v: v.mean()) if reduction == "mean" else (lambda v: v.sum()) if reduction == "sum" else (lambda v: v)
     total = 0.0

@@ -5,11 +5,19 @@ from __future__ import annotations
 import torch
 
 from . import ops
-from ._ffi import CtlError
+from ._ffi import LOSS_DICE, LOSS_FG_DICE, CtlError
+from .consistency import check_kinds as check_consistency_kinds
+from .losses import DIST_LOSS_FORM, LOSS_KINDS, check_constant, check_names, check_two_classes, class_weight_tuple, mask_u8, needs_fields
+from .recon import check_params as check_recon_params, parse_kinds as parse_recon_kinds
 
 
 def _nhwc(t: torch.Tensor) -> torch.Tensor:
     return t.float().contiguous(memory_format=torch.channels_last)
+
+
+def _logit_label(logit, label):
+    """What the label-map losses save and their kernels read: fp32 NHWC logits and a contiguous int64 label map."""
+    return _nhwc(logit), label.long().contiguous()
 
 
 class _NetFn(torch.autograd.Function):
@@ -136,7 +144,7 @@ class _CrossEntropy2D(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logit, label):
-        logit = _nhwc(logit)
+        logit = _nhwc(logit)                  # (_logit_label written out: this forward is on the default step's path, which pays for a call)
         label = label.long().contiguous()
         ctx.save_for_backward(logit, label)
         return ops.ce2d_fwd(logit, label)
@@ -152,8 +160,7 @@ class _PointwiseSegLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logit, label, kind, class_weights, gamma):
-        logit = _nhwc(logit)
-        label = label.long().contiguous()
+        logit, label = _logit_label(logit, label)
         ctx.save_for_backward(logit, label)
         ctx.args = (kind, class_weights, gamma)
         return ops.seg_loss_fwd(logit, label, kind, class_weights, gamma)[0]
@@ -171,8 +178,7 @@ class _DiceSegLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logit, label, kind):
-        logit = _nhwc(logit)
-        label = label.long().contiguous()
+        logit, label = _logit_label(logit, label)
         loss, ws = ops.seg_loss_fwd(logit, label, kind)
         ctx.save_for_backward(logit, label, ws)
         ctx.kind = kind
@@ -209,9 +215,8 @@ class LabelFields:
 
     def get_all(self, loss_type) -> None:
         """Compute, on the current stream, every form the loss name or {name: weight} mapping `loss_type` reads."""
-        for name in (loss_type if isinstance(loss_type, dict) else (loss_type,)):
-            if name in ops.DIST_LOSS_FORM:
-                self.get(ops.DIST_LOSS_FORM[name])
+        for form in needs_fields(loss_type):
+            self.get(form)
 
 
 class _DistSegLoss(torch.autograd.Function):
@@ -220,8 +225,7 @@ class _DistSegLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logit, label, kind, field):
-        logit = _nhwc(logit)
-        label = label.long().contiguous()
+        logit, label = _logit_label(logit, label)
         pred = ops.class_fields(ops.confident_label(logit), logit.shape[1], "squared") if kind == "hausdorff dt" else None
         ctx.kind, ctx.two = kind, pred is not None
         ctx.save_for_backward(*((logit, label, field) + ((pred,) if ctx.two else ())))
@@ -234,24 +238,25 @@ class _DistSegLoss(torch.autograd.Function):
         return ops.dist_loss_bwd(logit, label, ctx.kind, g.float().contiguous(), field, pred), None, None, None
 
 
-class _ConsistencyLoss(torch.autograd.Function):
-    """The weighted sum of consistency losses between an output and a constant reference (consistency.py): one fused forward, whose
-    scratch carries 1/R and the Dice coefficient table to the backward."""
+class _PairLoss(torch.autograd.Function):
+    """The weighted sum of the `kinds` of one family between a tensor and a constant second one: the consistency losses of an output and its
+    reference (consistency.py) and the image-similarity losses of a prediction and its target (recon.py).  `pair` = the family's (fwd, bwd)
+    of ops.py: one fused forward, whose scratch carries what the one backward launch reads (1/R and the Dice coefficient table, resp. the
+    'ncc' table and the 'lncc' coefficient maps).  `params`: the keyword arguments of both."""
 
     @staticmethod
-    def forward(ctx, output, reference, mask, kinds, class_weights, is_gt):
-        output, reference = _nhwc(output), _nhwc(reference)
-        loss, _, ws = ops.consistency_fwd(output, reference, kinds, class_weights, mask, is_gt)
-        ctx.save_for_backward(output, reference, ws, *(() if mask is None else (mask,)))
-        ctx.args = (dict(kinds), class_weights, is_gt)
+    def forward(ctx, x, ref, mask, pair, kinds, params):
+        x, ref = _nhwc(x), _nhwc(ref)
+        loss, _, ws = pair[0](x, ref, kinds, mask=mask, **params)
+        ctx.save_for_backward(x, ref, ws, *(() if mask is None else (mask,)))
+        ctx.args = (pair[1], dict(kinds), dict(params))
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        output, reference, ws = ctx.saved_tensors[:3]
-        mask = ctx.saved_tensors[3] if len(ctx.saved_tensors) > 3 else None
-        kinds, class_weights, is_gt = ctx.args
-        return ops.consistency_bwd(output, reference, kinds, g.float().contiguous(), ws, class_weights, mask, is_gt), None, None, None, None, None
+        x, ref, ws, *mask = ctx.saved_tensors
+        bwd, kinds, params = ctx.args
+        return bwd(x, ref, kinds, g.float().contiguous(), ws, mask=mask[0] if mask else None, **params), None, None, None, None, None
 
 
 class _AvgPool(torch.autograd.Function):
@@ -265,26 +270,6 @@ class _AvgPool(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         return ops.avgpool_bwd(_nhwc(g), ctx.scale, ctx.hw), None
-
-
-class _ImageSimilarityLoss(torch.autograd.Function):
-    """The weighted sum of image-similarity losses between a prediction and a constant target (recon.py): one fused forward, whose
-    scratch carries the 'ncc' table and the 'lncc' coefficient maps to the one backward launch."""
-
-    @staticmethod
-    def forward(ctx, x, t, mask, kinds, params):
-        x, t = _nhwc(x), _nhwc(t)
-        loss, _, ws = ops.recon_loss_fwd(x, t, kinds, mask, **params)
-        ctx.save_for_backward(x, t, ws, *(() if mask is None else (mask,)))
-        ctx.args = (dict(kinds), dict(params))
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        x, t, ws = ctx.saved_tensors[:3]
-        mask = ctx.saved_tensors[3] if len(ctx.saved_tensors) > 3 else None
-        kinds, params = ctx.args
-        return ops.recon_loss_bwd(x, t, kinds, g.float().contiguous(), ws, mask, **params), None, None, None, None
 
 
 class _AdvBiasField(torch.autograd.Function):
@@ -342,50 +327,34 @@ def cross_entropy_2D(logit, label):
 
 
 def segmentation_loss(logit, label, kind, class_weights=None, gamma=2.0, fields=None):
-    """One of the fused segmentation losses of ops.LOSS_KINDS / ops.DIST_LOSS_KINDS on logits [B,C,H,W] and a label map [B,H,W].
+    """One of the fused segmentation losses of losses.LOSS_KINDS / losses.DIST_LOSS_KINDS on logits [B,C,H,W] and a label map [B,H,W].
     `class_weights`: a host sequence of C numbers, used by 'weighted cross entropy' only ('weighted dice' ignores it, as upstream does);
     `gamma`: 'focal' only.  `fields` ('boundary', 'hausdorff dt'): the class fields of `label`, a LabelFields or the fp32 NHWC tensor of
-    the form the loss reads (ops.DIST_LOSS_FORM); computed here when absent."""
-    if kind in ops.DIST_LOSS_KINDS:
-        if logit.size(1) < 2:
-            raise ValueError(f"{kind!r} needs at least 2 classes")
+    the form the loss reads (losses.DIST_LOSS_FORM); computed here when absent."""
+    if kind in DIST_LOSS_FORM:
+        check_two_classes(kind, logit.size(1))
         ops.require_gpu(logit, label)
         if fields is None:
             fields = LabelFields(label, logit.size(1))
         if isinstance(fields, LabelFields):
-            fields = fields.get(ops.DIST_LOSS_FORM[kind])
+            fields = fields.get(DIST_LOSS_FORM[kind])
         return _DistSegLoss.apply(logit, label, kind, fields)
-    if kind not in ops.LOSS_KINDS:
-        raise NotImplementedError(f"segmentation loss {kind!r} (one of {', '.join(tuple(ops.LOSS_KINDS) + tuple(ops.DIST_LOSS_KINDS))})")
+    check_names((kind,), LOSS_KINDS, "segmentation loss")
     ops.require_gpu(logit, label)
-    if ops.LOSS_KINDS[kind] in (ops._ffi.LOSS_DICE, ops._ffi.LOSS_FG_DICE):
+    if LOSS_KINDS[kind] in (LOSS_DICE, LOSS_FG_DICE):
         return _DiceSegLoss.apply(logit, label, kind)
-    if class_weights is not None:
-        class_weights = tuple(float(v) for v in class_weights)
-    return _PointwiseSegLoss.apply(logit, label, kind, class_weights, float(gamma))
-
-
-def _mask_u8(mask):
-    """A mask of any dtype as a contiguous uint8 constant, nonzero = 1 (None stays None): what the loss Functions save and the kernels read."""
-    return None if mask is None else (mask.detach() != 0).to(torch.uint8).contiguous()
+    return _PointwiseSegLoss.apply(logit, label, kind, class_weight_tuple(class_weights), float(gamma))
 
 
 def consistency_loss(output, reference, kinds, class_weights=None, mask=None, is_gt=False):
-    """sum_name kinds[name] * L_name(output, reference) of the consistency losses of ops.CONSISTENCY_KINDS (consistency.py), differentiable
+    """sum_name kinds[name] * L_name(output, reference) of the consistency losses of consistency.CONSISTENCY_KINDS, differentiable
     in `output`; the reference is a constant and must not require grad.  `kinds`: {name: weight}; `class_weights`: a host sequence of C
     numbers ('weighted ce' only); `mask`: per pixel, [B,1,H,W] or [B,H,W], nonzero = 1."""
-    if not kinds:
-        raise ValueError("consistency_loss: `kinds` maps at least one name to its weight")
-    for name in kinds:
-        if name not in ops.CONSISTENCY_KINDS:
-            raise NotImplementedError(f"consistency loss {name!r} (one of {', '.join(ops.CONSISTENCY_KINDS)})")
-    if reference.requires_grad:
-        raise ValueError("the reference is a constant: detach it (no gradient reaches the reference)")
+    check_consistency_kinds(kinds, class_weights)
+    check_constant(reference, "reference")
     ops.require_gpu(output, reference, mask)
-    if class_weights is not None:
-        class_weights = tuple(float(v) for v in class_weights)
-    mask = _mask_u8(mask)
-    return _ConsistencyLoss.apply(output, reference, mask, kinds, class_weights, bool(is_gt))
+    return _PairLoss.apply(output, reference, mask_u8(mask), (ops.consistency_fwd, ops.consistency_bwd), kinds,
+                           dict(class_weights=class_weight_tuple(class_weights), is_gt=bool(is_gt)))
 
 
 def avg_pool(x, scale):
@@ -397,19 +366,15 @@ def avg_pool(x, scale):
 
 
 def image_similarity_loss(x, t, kinds, weights=None, mask=None, *, beta=1.0 / 9, win=9, zero_mean=True, reduction="mean"):
-    """sum_name weight_name * L_name(x, t) of the image-similarity losses of ops.RECON_KINDS (recon.py), differentiable in the prediction
+    """sum_name weight_name * L_name(x, t) of the image-similarity losses of recon.RECON_KINDS, differentiable in the prediction
     `x`; the target `t` ([B,C,H,W] or [1,C,H,W]) is a constant and must not require grad.  `kinds`: a name, names with `weights`, or
     {name: weight}; `mask`: per pixel, [B,1,H,W] or [B,H,W], nonzero = 1, multiplies x and t."""
-    from .recon import parse_kinds
-    kinds = parse_kinds(kinds, weights)
-    if t.requires_grad:
-        raise ValueError("the target is a constant: detach it (no gradient reaches the target)")
-    if reduction == "none":
-        raise NotImplementedError("reduction='none' is not offered on the device ('mean' or 'sum')")
+    kinds = parse_recon_kinds(kinds, weights)
+    check_recon_params(kinds, beta, win, reduction, device=True)
+    check_constant(t, "target")
     ops.require_gpu(x, t, mask)
-    mask = _mask_u8(mask)
-    params = dict(beta=float(beta), win=win, zero_mean=bool(zero_mean), reduction=reduction)
-    return _ImageSimilarityLoss.apply(x, t, mask, kinds, params)
+    return _PairLoss.apply(x, t, mask_u8(mask), (ops.recon_loss_fwd, ops.recon_loss_bwd), kinds,
+                           dict(beta=float(beta), win=win, zero_mean=bool(zero_mean), reduction=reduction))
 
 
 def adv_bias_field(x, theta, spacing):

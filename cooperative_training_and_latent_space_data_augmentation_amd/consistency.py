@@ -31,9 +31,13 @@ from __future__ import annotations
 import torch
 import torch.nn.functional as F
 
-from .losses import SMOOTH, check_mask, mask01, normalised_weights
+from . import _ffi      # the kind constants only: the library itself is loaded by the first call into it
+from .losses import SMOOTH, check_constant, check_mask, check_names, check_two_classes, class_weight_tuple, mask01, normalised_weights
 
-CONSISTENCY_NAMES = ("kl", "ce", "weighted ce", "mse", "Dice", "contour")
+# names of calc_segmentation_consistency (custom_loss.py:892-973) -> CTL_CONS_* bit; bit t is kind t, the order of the terms and of the weights
+CONSISTENCY_KINDS = {"kl": _ffi.CONS_KL, "ce": _ffi.CONS_CE, "weighted ce": _ffi.CONS_WCE, "mse": _ffi.CONS_MSE, "Dice": _ffi.CONS_DICE,
+                     "contour": _ffi.CONS_CONTOUR}
+CONSISTENCY_NAMES = tuple(CONSISTENCY_KINDS)
 MAX_SCALE = 4
 _P8_T = torch.tensor(1e-8, dtype=torch.float32)
 P8 = float(_P8_T)                                   # upstream's torch.where(reference == 0, 1e-8, 1 - 1e-8) is a float32 tensor: 1e-8 and 1.0
@@ -44,15 +48,11 @@ def parse_consistency(divergence_types, divergence_weights, class_weights, scale
     """([(name, weight)], normalised class weights or None, [scale]).  Raises what the module docstring says."""
     names = [divergence_types] if isinstance(divergence_types, str) else list(divergence_types)
     weights = [divergence_weights] if isinstance(divergence_weights, (int, float)) else list(divergence_weights)
-    if len(names) != len(weights) or not names:
-        raise ValueError(f"divergence_types and divergence_weights: {len(names)} names, {len(weights)} weights (the same, positive number)")
-    for name in names:
-        if name not in CONSISTENCY_NAMES:
-            raise NotImplementedError(f"divergence type {name!r} (one of {', '.join(CONSISTENCY_NAMES)})")
-    if "weighted ce" in names and class_weights is None:
-        raise ValueError("'weighted ce' must be given class weights")
-    if "contour" in names and num_classes < 2:
-        raise ValueError("'contour' needs at least 2 classes (it runs over the classes 1 .. C-1)")
+    if len(names) != len(weights):
+        raise ValueError(f"divergence_types and divergence_weights: {len(names)} names, {len(weights)} weights (the same number)")
+    check_kinds(names, class_weights)
+    if "contour" in names:
+        check_two_classes("contour", num_classes)
     wn = None if class_weights is None else normalised_weights(class_weights, num_classes)
     scales = [scales] if isinstance(scales, int) else list(scales)
     if not scales or any(int(s) != s or not 0 <= s <= MAX_SCALE for s in scales):
@@ -62,12 +62,18 @@ def parse_consistency(divergence_types, divergence_weights, class_weights, scale
     return [(n, float(w)) for n, w in zip(names, weights)], wn, [int(s) for s in scales]
 
 
+def check_kinds(names, class_weights):
+    """The names and what they need of the other arguments: checked before any tensor is looked at."""
+    check_names(names, CONSISTENCY_KINDS, "consistency loss")
+    if "weighted ce" in names and class_weights is None:
+        raise ValueError("'weighted ce' must be given class weights")
+
+
 def check_pair(output, reference, mask=None):
     """Shapes of the two predictions and of the mask; the reference must not require grad."""
     if output.dim() != 4 or tuple(output.shape) != tuple(reference.shape):
         raise ValueError(f"expected output and reference logits of one shape [B,C,H,W], got {tuple(output.shape)} and {tuple(reference.shape)}")
-    if reference.requires_grad:
-        raise ValueError("the reference is a constant: detach it (no gradient reaches the reference)")
+    check_constant(reference, "reference")
     check_mask(mask, output.shape)
 
 
@@ -123,7 +129,8 @@ def _through_softmax(q, g):
 
 
 def _one(x, r, name, wn, m, is_gt):
-    """(loss, dloss/dx) of one kind at one scale; float64, m[B,1,H,W] of 0/1."""
+    """(loss, grad) of one kind at one scale, m[B,1,H,W] of 0/1, in x's dtype: the value from differentiable torch ops (the CPU path takes
+    it as it is) and grad() = dloss/dx in closed form, which the host statement evaluates."""
     b, c, h, w = x.shape
     M = float(b * h * w)
     q, logq = torch.softmax(x, 1), torch.log_softmax(x, 1)
@@ -135,27 +142,28 @@ def _one(x, r, name, wn, m, is_gt):
         else:
             p = torch.softmax(r, 1)
             plogp = p * torch.log_softmax(r, 1)
-        return (m * (plogp - p * logq)).sum() / M, (m / M) * (p.sum(1, keepdim=True) * q - p)
+        return (m * (plogp - p * logq)).sum() / M, lambda: (m / M) * (p.sum(1, keepdim=True) * q - p)
     p = r if is_gt else torch.softmax(r, 1)
     if name in ("ce", "weighted ce"):
-        wv = (torch.ones(c, dtype=x.dtype) if name == "ce" else wn).view(1, c, 1, 1)
+        wv = (torch.ones(c, dtype=x.dtype, device=x.device) if name == "ce" else wn.to(device=x.device, dtype=x.dtype)).view(1, c, 1, 1)
         R = float(m.sum())
         if R == 0.0:
-            return torch.zeros((), dtype=x.dtype), torch.zeros_like(x)
-        return -(m * wv * p * logq).sum() / R, (m / R) * (q * (wv * p).sum(1, keepdim=True) - wv * p)
+            return (x * 0.0).sum(), lambda: torch.zeros_like(x)
+        return -(m * wv * p * logq).sum() / R, lambda: (m / R) * (q * (wv * p).sum(1, keepdim=True) - wv * p)
     if name == "mse":
-        return (m * (q - p) ** 2).sum() / M, _through_softmax(q, 2.0 * m * (q - p) / M)
+        return (m * (q - p) ** 2).sum() / M, lambda: _through_softmax(q, 2.0 * m * (q - p) / M)
     if name == "Dice":
         inter = (m * q * p).sum((2, 3), keepdim=True) + SMOOTH
         union = (m * q).sum((2, 3), keepdim=True) + (m * p).sum((2, 3), keepdim=True) + SMOOTH
-        g = -(m / float(b * c)) * (2.0 * p / union - 2.0 * inter / (union * union))
-        return 1.0 - (2.0 * inter / union).sum() / float(b * c), _through_softmax(q, g)
-    if c < 2:
-        raise ValueError("'contour' needs at least 2 classes (it runs over the classes 1 .. C-1)")
+        return 1.0 - (2.0 * inter / union).sum() / float(b * c), \
+            lambda: _through_softmax(q, -(m / float(b * c)) * (2.0 * p / union - 2.0 * inter / (union * union)))
     ex, ey = sobel((q - p)[:, 1:])
-    g = torch.zeros_like(x)
-    g[:, 1:] = sobel_t(m * ex, m * ey) / (float(c - 1) * M)
-    return 0.5 * (m * (ex * ex + ey * ey)).sum() / (float(c - 1) * M), _through_softmax(q, g)
+
+    def contour_grad():
+        g = torch.zeros_like(x)
+        g[:, 1:] = sobel_t(m * ex, m * ey) / (float(c - 1) * M)
+        return _through_softmax(q, g)
+    return 0.5 * (m * (ex * ex + ey * ey)).sum() / (float(c - 1) * M), contour_grad
 
 
 def consistency_and_grad(output, reference, divergence_types=("kl", "contour"), divergence_weights=(1.0, 0.5), class_weights=None,
@@ -172,44 +180,12 @@ def consistency_and_grad(output, reference, divergence_types=("kl", "contour"), 
         for name, weight in terms:
             l, g = _one(xs, rs, name, wn, ms, bool(is_gt))
             loss = loss + float(1 << s) * weight * l
-            grad = grad + float(1 << s) * weight * unpool(g, s, x.shape[2], x.shape[3])
+            grad = grad + float(1 << s) * weight * unpool(g(), s, x.shape[2], x.shape[3])
     n = float(len(scales))
     return loss / n, grad * (float(gout) / n)
 
 
-# ---------------------------------------------------------------------------------------------- the same arithmetic from torch ops
-def _one_torch(x, r, name, wn, m, is_gt):
-    """The value of `_one` from differentiable torch ops, in x's dtype."""
-    b, c, h, w = x.shape
-    M = float(b * h * w)
-    logq = torch.log_softmax(x, 1)
-    q = torch.softmax(x, 1)
-    if name == "kl":
-        if is_gt:
-            nz = r != 0
-            p = torch.where(nz, torch.ones_like(r), torch.full_like(r, P8))
-            plogp = torch.where(nz, torch.zeros_like(r), torch.full_like(r, P8_LOG_P8))
-        else:
-            p = torch.softmax(r, 1)
-            plogp = p * torch.log_softmax(r, 1)
-        return (m * (plogp - p * logq)).sum() / M
-    p = r if is_gt else torch.softmax(r, 1)
-    if name in ("ce", "weighted ce"):
-        wv = (torch.ones(c, dtype=x.dtype, device=x.device) if name == "ce" else wn.to(device=x.device, dtype=x.dtype)).view(1, c, 1, 1)
-        R = float(m.sum())
-        if R == 0.0:
-            return (x * 0.0).sum()
-        return -(m * wv * p * logq).sum() / R
-    if name == "mse":
-        return (m * (q - p) ** 2).sum() / M
-    if name == "Dice":
-        inter = (m * q * p).sum((2, 3)) + SMOOTH
-        union = (m * q).sum((2, 3)) + (m * p).sum((2, 3)) + SMOOTH
-        return 1.0 - (2.0 * inter / union).sum() / float(b * c)
-    ex, ey = sobel((q - p)[:, 1:])
-    return 0.5 * (m * (ex * ex + ey * ey)).sum() / (float(c - 1) * M)
-
-
+# ---------------------------------------------------------------------------------------------- the CPU path of the public functions
 def _consistency_torch(output, reference, terms, wn, scales, mask, is_gt):
     x = output if output.is_floating_point() else output.float()
     r = reference.detach().to(x.dtype)
@@ -219,7 +195,7 @@ def _consistency_torch(output, reference, terms, wn, scales, mask, is_gt):
         xs, rs = pool(x, s), pool(r, s)
         ms = m if s == 0 else torch.ones((xs.shape[0], 1) + tuple(xs.shape[2:]), dtype=x.dtype, device=x.device)
         for name, weight in terms:
-            total = total + float(1 << s) * weight * _one_torch(xs, rs, name, wn, ms, is_gt)
+            total = total + float(1 << s) * weight * _one(xs, rs, name, wn, ms, is_gt)[0]
     return total / float(len(scales))
 
 
@@ -239,8 +215,7 @@ def calc_segmentation_consistency(output, reference, divergence_types=("kl", "co
     kinds = {}
     for name, weight in terms:
         kinds[name] = kinds.get(name, 0.0) + weight
-    if class_weights is not None:
-        class_weights = tuple(float(v) for v in (class_weights.tolist() if hasattr(class_weights, "tolist") else class_weights))
+    class_weights = class_weight_tuple(class_weights)
     reference = reference.detach()
     if scales == [0]:
         return autograd.consistency_loss(output, reference, kinds, class_weights, mask, bool(is_gt))

@@ -34,11 +34,39 @@ from collections.abc import Mapping
 
 import torch
 
+from . import _ffi      # the kind constants only: the library itself is loaded by the first call into it
+
 SMOOTH = 0.01
-DIST_LOSS_NAMES = ("boundary", "hausdorff dt")
-LOSS_NAMES = ("cross entropy", "weighted cross entropy", "dice", "weighted dice", "foreground dice", "focal") + DIST_LOSS_NAMES
+# names of basic_loss_fn (custom_loss.py:8-40) -> CTL_LOSS_* kind of the fused kernels; upstream's 'weighted dice' never uses its weights: it
+# is 'dice'.  'cross entropy' is a name without a fused kind (it has its own kernel pair, ops.ce2d_fwd / ce2d_bwd).
+LOSS_KINDS = {"weighted cross entropy": _ffi.LOSS_WCE, "focal": _ffi.LOSS_FOCAL, "dice": _ffi.LOSS_DICE, "weighted dice": _ffi.LOSS_DICE,
+              "foreground dice": _ffi.LOSS_FG_DICE}
+DIST_LOSS_KINDS = {"boundary": _ffi.DLOSS_BOUNDARY, "hausdorff dt": _ffi.DLOSS_HAUSDORFF_DT}      # name -> CTL_DLOSS_* kind
+DIST_LOSS_FORM = {"boundary": "signed", "hausdorff dt": "squared"}                               # the training form of the label fields a loss reads
+DIST_LOSS_NAMES = tuple(DIST_LOSS_KINDS)
+LOSS_NAMES = ("cross entropy",) + tuple(LOSS_KINDS) + DIST_LOSS_NAMES
 NO_CLASS = 255      # the confident label of a pixel where no class has more than half of the probability
 MAX_CLASSES = 16    # channels of a logit / image tensor the loss and statistics kernels take (CTL_ROW_MAXC of csrc/ctl_rows.h); stated once, here
+
+
+# ---------------------------------------------------------------------------------------------- the rules every loss family shares
+def check_names(names, table, noun):
+    """ValueError for no name at all, NotImplementedError for a name that is not in `table` (a {name: kind} table or a tuple of names)."""
+    if not names:
+        raise ValueError(f"{noun}: no names (`kinds` maps at least one name to its weight)")
+    for name in names:
+        if name not in table:
+            raise NotImplementedError(f"{noun} {name!r} (one of {', '.join(table)})")
+
+
+def check_two_classes(name, c):
+    if c < 2:
+        raise ValueError(f"{name!r} needs at least 2 classes (it runs over the classes 1 .. C-1)")
+
+
+def check_constant(t, what):
+    if t.requires_grad:
+        raise ValueError(f"the {what} is a constant: detach it (no gradient reaches the {what})")
 
 
 def check_mask(mask, shape):
@@ -53,7 +81,35 @@ def mask01(mask, shape, dtype, device):
     b, _, h, w = shape
     if mask is None:
         return torch.ones((b, 1, h, w), dtype=dtype, device=device)
-    return (mask.detach().reshape(b, 1, h, w) != 0).to(device=device, dtype=dtype)
+    return _nonzero(mask).reshape(b, 1, h, w).to(device=device, dtype=dtype)
+
+
+def mask_u8(mask):
+    """A mask of any dtype as a contiguous uint8 constant (None stays None): what the loss Functions save and the kernels read.  The
+    kernels take every nonzero byte as 1, so a contiguous uint8 mask is used as it is."""
+    if mask is None or (mask.dtype == torch.uint8 and mask.is_contiguous()):
+        return mask
+    return _nonzero(mask).to(torch.uint8).contiguous()
+
+
+def _nonzero(mask):
+    return mask.detach() != 0          # nonzero = 1, whatever the mask's dtype
+
+
+def class_weight_tuple(class_weights, c=None):
+    """The class weights (a sequence or a tensor; None stays None) as a tuple of floats, one per class where the class count is known."""
+    if class_weights is None:
+        return None
+    vals = tuple(float(v) for v in (class_weights.flatten().tolist() if hasattr(class_weights, "tolist") else class_weights))
+    if c is not None and len(vals) != c:
+        raise ValueError(f"each class must have a weight: expected {c} weights, got {len(vals)}")
+    return vals
+
+
+def needs_fields(loss_type):
+    """The forms of the label's class fields (ops.class_fields) that a loss name or {name: weight} mapping reads, in its order: empty
+    without a distance-map loss."""
+    return [DIST_LOSS_FORM[n] for n in (loss_type if isinstance(loss_type, Mapping) else (loss_type,)) if n in DIST_LOSS_FORM]
 
 
 def parse_loss_type(loss_type, class_weights=None, num_classes=None):
@@ -61,20 +117,11 @@ def parse_loss_type(loss_type, class_weights=None, num_classes=None):
     'contour_smooth' raise NotImplementedError; class weights of the wrong length, an empty mapping and 'foreground dice', 'boundary' or
     'hausdorff dt' of one class raise ValueError."""
     terms = [(k, float(v)) for k, v in loss_type.items()] if isinstance(loss_type, Mapping) else [(loss_type, 1.0)]
-    for name, _ in terms:
-        if name not in LOSS_NAMES:
-            raise NotImplementedError(f"loss_type {name!r} (one of {', '.join(LOSS_NAMES)}, or a mapping of them to weights)")
-    if not terms:
-        raise ValueError("loss_type: empty mapping")
-    if class_weights is not None:
-        class_weights = tuple(float(v) for v in (class_weights.tolist() if hasattr(class_weights, "tolist") else class_weights))
-        if num_classes is not None and len(class_weights) != num_classes:
-            raise ValueError(f"each class must have a weight: expected {num_classes} weights, got {len(class_weights)}")
-    if num_classes is not None and num_classes < 2 and any(n == "foreground dice" for n, _ in terms):
-        raise ValueError("'foreground dice' needs at least 2 classes")
+    check_names([n for n, _ in terms], LOSS_NAMES, "segmentation loss")
+    class_weights = class_weight_tuple(class_weights, num_classes)
     for n, _ in terms:
-        if num_classes is not None and num_classes < 2 and n in DIST_LOSS_NAMES:
-            raise ValueError(f"{n!r} needs at least 2 classes")
+        if num_classes is not None and (n == "foreground dice" or n in DIST_LOSS_NAMES):
+            check_two_classes(n, num_classes)
     return terms, class_weights
 
 
@@ -82,9 +129,7 @@ def normalised_weights(class_weights, c):
     """w' = w / sum(w) * C in float64 (custom_loss.py:733-734); None = upstream's uniform 1/C, i.e. ones."""
     if class_weights is None:
         return torch.ones(c, dtype=torch.float64)
-    w = torch.as_tensor(class_weights, dtype=torch.float64).flatten()
-    if w.numel() != c:
-        raise ValueError(f"each class must have a weight: expected {c} weights, got {w.numel()}")
+    w = torch.tensor(class_weight_tuple(class_weights, c), dtype=torch.float64)
     total = float(w.sum())
     if not (total > 0.0 and total != float("inf")):
         raise ValueError(f"the class weights sum to {total}: a finite, positive sum is needed")
@@ -123,8 +168,6 @@ def confident_label_host(logit, margin=1e-5):
 
 def _dist_one(x, y, name, pred_fields):
     b, c, h, w = x.shape
-    if c < 2:
-        raise ValueError(f"{name!r} needs at least 2 classes")
     div = float(b * (c - 1) * h * w)
     p = torch.softmax(x, 1)
     fg = torch.ones(c, dtype=torch.float64).view(1, c, 1, 1)
@@ -156,8 +199,6 @@ def _one(x, y, name, class_weights, gamma, pred_fields=None):
             f = (t * wn.view(1, c, 1, 1)).sum(1)
         return (-f * (logp * t).sum(1)).sum() / m, f.unsqueeze(1) * (p - t) / m
     fg = name == "foreground dice"
-    if fg and c < 2:
-        raise ValueError("'foreground dice' needs at least 2 classes")
     sel = torch.ones(c, dtype=torch.float64)
     if fg:
         sel[0] = 0.0

@@ -14,7 +14,11 @@ import torch
 
 from . import _ffi
 from ._ffi import lib, call
-from .losses import MAX_CLASSES      # 16: channel rows of the loss / statistics kernels
+# the loss families own their name -> kind tables and their argument rules (losses.py, consistency.py, recon.py); the wrappers below call them
+from .consistency import CONSISTENCY_KINDS, check_kinds as check_consistency_kinds, check_plane
+from .losses import (DIST_LOSS_FORM, DIST_LOSS_KINDS, LOSS_KINDS, MAX_CLASSES, check_mask, check_names, check_two_classes, class_weight_tuple,
+                     mask_u8)      # MAX_CLASSES = 16: channel rows of the loss / statistics kernels
+from .recon import RECON_KINDS, check_image, check_params as check_recon_params
 
 
 def stream_ptr() -> int:
@@ -84,13 +88,8 @@ def _nhwc_f32(who: str, text: str, *tensors, also: bool = True) -> None:
         raise ValueError(f"{who}: {text}")
 
 
-def _kind_bits(kinds, table, what: str, who: str):
-    """(bits, c_double array of len(table)) of a {name: weight} mapping over the {name: bit} `table`; bit t is kind t, the order of the weights."""
-    if not kinds:
-        raise ValueError(f"{who}: `kinds` maps at least one name to its weight")
-    for name in kinds:
-        if name not in table:
-            raise NotImplementedError(f"{what} {name!r} (one of {', '.join(table)})")
+def _kind_bits(kinds, table):
+    """(bits, c_double array of len(table)) of a checked {name: weight} mapping over the {name: bit} `table`; bit t is kind t, the order of the weights."""
     bits, weights = 0, [0.0] * len(table)
     for name, weight in kinds.items():
         bits |= table[name]
@@ -100,19 +99,33 @@ def _kind_bits(kinds, table, what: str, who: str):
 
 def _class_weight_array(class_weights, c: int):
     """One double per class of a host sequence (the library normalises it in fp64)."""
-    vals = [float(v) for v in class_weights]
-    if len(vals) != c:
-        raise ValueError(f"each class must have a weight: expected {c} weights, got {len(vals)}")
-    return (C.c_double * c)(*vals)
+    return (C.c_double * c)(*class_weight_tuple(class_weights, c))
 
 
-def _pixel_mask(mask, n: int, h: int, w: int, who: str):
-    """A per-pixel mask [n,1,h,w] or [n,h,w] of any dtype as contiguous uint8, nonzero = 1 (None stays None)."""
-    if mask is None:
-        return None
-    if tuple(mask.shape) not in ((n, 1, h, w), (n, h, w)):
-        raise ValueError(f"{who}: the mask is per pixel, [{n},1,{h},{w}] or [{n},{h},{w}], got {tuple(mask.shape)}")
-    return mask if mask.dtype == torch.uint8 and mask.is_contiguous() else (mask != 0).to(torch.uint8).contiguous()
+def _kinds_scratch(query: str, dims, table, device):
+    """(ws, loss) of a fused forward over the kinds of `table`: its fp64 scratch of `query(*dims)` doubles and the fp32 vector [total, one
+    term per kind] it writes."""
+    return _workspace(query, *dims, device=device, dtype=torch.float64)[0], torch.empty(1 + len(table), dtype=torch.float32, device=device)
+
+
+def _scratch_given(ws, gout, query: str, dims, who: str, fwd: str) -> None:
+    """ValueError unless `ws` can be the scratch that the forward `fwd` returned for these sizes."""
+    require_gpu(gout, ws)
+    _arg(ws, torch.float64, (None,), who, "ws", dense=True)
+    if ws.numel() < getattr(lib, query)(*dims):
+        raise ValueError(f"{who}: `ws` is not the scratch of {fwd} for these arguments")
+
+
+def _logits_and_label(logit, label, who: str, *fields):
+    """(n, c, h, w) of fp32 NHWC logits [B,C,H,W], their contiguous int64 label map [B,H,W] and the fp32 NHWC `fields` of the logits' shape"""
+    if logit.dim() != 4 or logit.dtype != torch.float32 or label.dtype != torch.int64 or \
+            tuple(label.shape) != (logit.shape[0], logit.shape[2], logit.shape[3]):
+        raise ValueError(f"{who}: expected fp32 logits [B,C,H,W] and an int64 label map [B,H,W]")
+    for f in fields:
+        _arg(f, torch.float32, tuple(logit.shape), who, "a field")
+    _nhwc_f32(who, "the logits" + (" and the fields" if fields else "") + " must be NHWC in memory (channels_last) and the label map contiguous",
+              logit, *fields, also=label.is_contiguous())
+    return tuple(int(v) for v in logit.shape)
 
 
 # ---------------------------------------------------------------------------------------------- conv (unit-level API)
@@ -280,21 +293,11 @@ def ce2d_bwd(logit, label, gout):
     return d
 
 
-# loss names of basic_loss_fn (custom_loss.py:8-40) -> CTL_LOSS_* kind; upstream's 'weighted dice' never uses its weights: it is 'dice'
-LOSS_KINDS = {"weighted cross entropy": _ffi.LOSS_WCE, "focal": _ffi.LOSS_FOCAL, "dice": _ffi.LOSS_DICE, "weighted dice": _ffi.LOSS_DICE,
-              "foreground dice": _ffi.LOSS_FG_DICE}
-
-
 def _loss_args(logit, label, kind, class_weights):
-    if kind not in LOSS_KINDS:
-        raise NotImplementedError(f"segmentation loss {kind!r} (one of {', '.join(LOSS_KINDS)})")
+    """The kinds of losses.LOSS_KINDS; the name is checked before the tensors are looked at."""
+    check_names((kind,), LOSS_KINDS, "segmentation loss")
     require_gpu(logit, label)
-    if logit.dim() != 4 or logit.dtype != torch.float32 or label.dtype != torch.int64 or \
-            tuple(label.shape) != (logit.shape[0], logit.shape[2], logit.shape[3]):
-        raise ValueError("segmentation loss: expected fp32 logits [B,C,H,W] and an int64 label map [B,H,W]")
-    n, c, h, w = logit.shape
-    _nhwc_f32("segmentation loss", "the logits must be NHWC in memory (channels_last) and the label map contiguous", logit,
-              also=label.is_contiguous())
+    n, c, h, w = _logits_and_label(logit, label, "segmentation loss")
     wts = _class_weight_array(class_weights, c) if class_weights is not None and LOSS_KINDS[kind] == _ffi.LOSS_WCE else None
     return LOSS_KINDS[kind], n, h * w, c, wts
 
@@ -318,8 +321,6 @@ def seg_loss_bwd(logit, label, kind, gout, ws=None, class_weights=None, gamma=2.
 
 
 # ---------------------------------------------------------------------------------------------- distance-map losses
-DIST_LOSS_KINDS = {"boundary": _ffi.DLOSS_BOUNDARY, "hausdorff dt": _ffi.DLOSS_HAUSDORFF_DT}      # name -> CTL_DLOSS_* kind
-DIST_LOSS_FORM = {"boundary": "signed", "hausdorff dt": "squared"}                               # the training form of the label fields a loss reads
 FIELD_FORMS = {"d2": _ffi.FIELD_D2, "signed": _ffi.FIELD_SIGNED, "squared": _ffi.FIELD_SQUARED}
 
 
@@ -355,23 +356,14 @@ def confident_label(logit: torch.Tensor) -> torch.Tensor:
 
 
 def _dist_loss_args(logit, label, kind, field_a, field_b):
-    if kind not in DIST_LOSS_KINDS:
-        raise NotImplementedError(f"distance-map loss {kind!r} (one of {', '.join(DIST_LOSS_KINDS)})")
+    check_names((kind,), DIST_LOSS_KINDS, "distance-map loss")
     two = kind == "hausdorff dt"
     fields = (field_a, field_b) if two else (field_a,)
     if any(f is None for f in fields):
         raise ValueError(f"{kind!r} needs {'two field tensors (label, prediction)' if two else 'the signed map of the label'}")
     require_gpu(logit, label, *fields)
-    if logit.dim() != 4 or logit.dtype != torch.float32 or label.dtype != torch.int64 or \
-            tuple(label.shape) != (logit.shape[0], logit.shape[2], logit.shape[3]):
-        raise ValueError("distance-map loss: expected fp32 logits [B,C,H,W] and an int64 label map [B,H,W]")
-    n, c, h, w = logit.shape
-    if c < 2:
-        raise ValueError(f"{kind!r} needs at least 2 classes")
-    for f in fields:
-        _arg(f, torch.float32, (n, c, h, w), "distance-map loss", "a field")
-    _nhwc_f32("distance-map loss", "the logits and the fields must be NHWC in memory (channels_last) and the label map contiguous", logit,
-              *fields, also=label.is_contiguous())
+    n, c, h, w = _logits_and_label(logit, label, "distance-map loss", *fields)
+    check_two_classes(kind, c)
     return DIST_LOSS_KINDS[kind], n, h * w, c
 
 
@@ -395,26 +387,21 @@ def dist_loss_bwd(logit, label, kind, gout, field_a, field_b=None):
 
 
 # ---------------------------------------------------------------------------------------------- consistency losses
-# names of calc_segmentation_consistency (custom_loss.py:892-973) -> CTL_CONS_* bit; bit t is kind t, the order of `terms` and of the weights
-CONSISTENCY_KINDS = {"kl": _ffi.CONS_KL, "ce": _ffi.CONS_CE, "weighted ce": _ffi.CONS_WCE, "mse": _ffi.CONS_MSE, "Dice": _ffi.CONS_DICE,
-                     "contour": _ffi.CONS_CONTOUR}
-
-
 def _consistency_args(output, reference, kinds, class_weights, mask, who):
     """(kind bits, weights, class weights, mask as uint8, n, h, w, c) of a {name: weight} mapping `kinds`; names and weights are checked
     before the tensors are looked at."""
-    bits, weights = _kind_bits(kinds, CONSISTENCY_KINDS, "consistency loss", who)
-    if "weighted ce" in kinds and class_weights is None:
-        raise ValueError("'weighted ce' must be given class weights")
+    check_consistency_kinds(kinds, class_weights)
+    bits, weights = _kind_bits(kinds, CONSISTENCY_KINDS)
     require_gpu(output, reference, mask)
     if output.dim() != 4 or output.dtype != torch.float32 or reference.dtype != torch.float32 or tuple(reference.shape) != tuple(output.shape):
         raise ValueError(f"{who}: expected fp32 output and reference logits of one shape [B,C,H,W]")
     _nhwc_f32(who, "output and reference must be NHWC in memory (channels_last)", output, reference)
     n, c, h, w = (int(v) for v in output.shape)
-    if "contour" in kinds and c < 2:
-        raise ValueError("'contour' needs at least 2 classes (it runs over the classes 1 .. C-1)")
+    if "contour" in kinds:
+        check_two_classes("contour", c)
     wts = _class_weight_array(class_weights, c) if class_weights is not None and "weighted ce" in kinds else None
-    return bits, weights, wts, _pixel_mask(mask, n, h, w, who), n, h, w, c
+    check_mask(mask, output.shape)
+    return bits, weights, wts, mask_u8(mask), n, h, w, c
 
 
 def consistency_fwd(output, reference, kinds, class_weights=None, mask=None, is_gt=False):
@@ -422,8 +409,7 @@ def consistency_fwd(output, reference, kinds, class_weights=None, mask=None, is_
     CONSISTENCY_KINDS (0 for a name that is not in `kinds`), and the scratch consistency_bwd reads.  `mask`: [B,1,H,W] or [B,H,W], any
     dtype, nonzero = 1 (a contiguous uint8 mask is used as it is)."""
     bits, weights, wts, mask, n, h, w, c = _consistency_args(output, reference, kinds, class_weights, mask, "consistency_fwd")
-    ws = torch.empty(max(1, lib.ctl_consistency_ws_doubles(bits, n, h, w, c)), dtype=torch.float64, device=output.device)
-    loss = torch.empty(1 + len(CONSISTENCY_KINDS), dtype=torch.float32, device=output.device)
+    ws, loss = _kinds_scratch("ctl_consistency_ws_doubles", (bits, n, h, w, c), CONSISTENCY_KINDS, output.device)
     call("ctl_consistency_fwd", bits, weights, wts, ptr(output), ptr(reference), ptr(mask), int(bool(is_gt)), n, h, w, c, ptr(ws), ptr(loss),
          stream_ptr())
     return loss[0], loss[1:], ws
@@ -432,10 +418,7 @@ def consistency_fwd(output, reference, kinds, class_weights=None, mask=None, is_
 def consistency_bwd(output, reference, kinds, gout, ws, class_weights=None, mask=None, is_gt=False):
     """gout (0-d fp32 device tensor) * d total / d output; `ws` is what consistency_fwd returned for the same arguments."""
     bits, weights, wts, mask, n, h, w, c = _consistency_args(output, reference, kinds, class_weights, mask, "consistency_bwd")
-    require_gpu(gout, ws)
-    _arg(ws, torch.float64, (None,), "consistency_bwd", "ws", dense=True)
-    if ws.numel() < lib.ctl_consistency_ws_doubles(bits, n, h, w, c):
-        raise ValueError("consistency_bwd: `ws` is not the scratch of consistency_fwd for these arguments")
+    _scratch_given(ws, gout, "ctl_consistency_ws_doubles", (bits, n, h, w, c), "consistency_bwd", "consistency_fwd")
     d = torch.empty_like(output)
     call("ctl_consistency_bwd", bits, weights, wts, ptr(output), ptr(reference), ptr(mask), int(bool(is_gt)), ptr(gout), ptr(ws), n, h, w, c,
          ptr(d), stream_ptr())
@@ -454,8 +437,7 @@ def _pool_args(x, scale, who):
 def avgpool_fwd(x: torch.Tensor, scale: int) -> torch.Tensor:
     """AvgPool2d(2^scale) (window = stride, floor sizes) of fp32 NHWC logits: the fp64 window mean, rounded once."""
     scale, (n, c, h, w) = _pool_args(x, scale, "avgpool_fwd")
-    if (h >> scale) < 1 or (w >> scale) < 1:
-        raise ValueError(f"avgpool_fwd: a {h}x{w} plane is smaller than the {1 << scale}x{1 << scale} window of scale {scale}")
+    check_plane(h, w, scale)
     y = empty_nhwc(n, c, h >> scale, w >> scale, x.device)
     call("ctl_avgpool_fwd", ptr(x), n, h, w, c, scale, ptr(y), stream_ptr())
     return y
@@ -473,33 +455,21 @@ def avgpool_bwd(gy: torch.Tensor, scale: int, hw) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------------- image-similarity (reconstruction) losses
-# names of recon.py (custom_loss.py:310-318, :514-571, :574-661) -> CTL_RECON_* bit; bit k is kind k, the order of `terms` and of the weights
-RECON_KINDS = {"mse": _ffi.RECON_MSE, "l1": _ffi.RECON_L1, "smooth l1": _ffi.RECON_SMOOTH_L1, "ncc": _ffi.RECON_NCC, "lncc": _ffi.RECON_LNCC}
-
-
 def _recon_args(x, t, kinds, mask, beta, win, reduction, who):
     """(kind bits, weights, mask as uint8, t's batch, n, h, w, c, reduce_sum) of a {name: weight} mapping `kinds`; names, weights and
     parameters are checked before the tensors are looked at."""
-    bits, weights = _kind_bits(kinds, RECON_KINDS, "image-similarity loss", who)
-    if reduction == "none":
-        raise NotImplementedError(f"{who}: reduction='none' is not offered on the device ('mean' or 'sum')")
-    if reduction not in ("mean", "sum"):
-        raise ValueError(f"{who}: reduction {reduction!r} ('mean' or 'sum')")
-    if "smooth l1" in kinds and not float(beta) > 0.0:
-        raise ValueError(f"{who}: beta = {beta} (smooth l1 needs beta > 0)")
-    if "lncc" in kinds and (int(win) != win or win % 2 == 0 or not 3 <= win <= 15):
-        raise ValueError(f"{who}: win = {win} (odd, 3 .. 15)")
+    check_names(kinds, RECON_KINDS, "image-similarity loss")
+    check_recon_params(kinds, beta, win, reduction, device=True)
+    bits, weights = _kind_bits(kinds, RECON_KINDS)
     require_gpu(x, t, mask)
     if x.dim() != 4 or t.dim() != 4 or x.dtype != torch.float32 or t.dtype != torch.float32 or tuple(t.shape[1:]) != tuple(x.shape[1:]) \
             or t.shape[0] not in (1, x.shape[0]):
         raise ValueError(f"{who}: expected an fp32 prediction [B,C,H,W] and an fp32 target of that shape or [1,C,H,W]")
     _nhwc_f32(who, "prediction and target must be NHWC in memory (channels_last)", x, t)
     n, c, h, w = (int(v) for v in x.shape)
-    if c > MAX_CLASSES:
-        raise ValueError(f"{who}: {c} channels (1 .. {MAX_CLASSES})")
-    if "lncc" in kinds and (win > h or win > w):
-        raise ValueError(f"{who}: win = {win} is larger than the {h}x{w} plane")
-    return bits, weights, _pixel_mask(mask, n, h, w, who), int(t.shape[0]), n, h, w, c, int(reduction == "sum")
+    check_image(kinds, x.shape, win)
+    check_mask(mask, x.shape)
+    return bits, weights, mask_u8(mask), int(t.shape[0]), n, h, w, c, int(reduction == "sum")
 
 
 def recon_loss_fwd(x, t, kinds, mask=None, beta=1.0 / 9, win=9, zero_mean=True, reduction="mean"):
@@ -507,8 +477,7 @@ def recon_loss_fwd(x, t, kinds, mask=None, beta=1.0 / 9, win=9, zero_mean=True, 
     or [1,C,H,W]): the 0-d weighted total, fp32 terms[5] in the order of RECON_KINDS (0 for a name that is not in `kinds`), and the
     scratch recon_loss_bwd reads.  `mask`: [B,1,H,W] or [B,H,W], any dtype, nonzero = 1 (a contiguous uint8 mask is used as it is)."""
     bits, weights, mask, tb, n, h, w, c, rsum = _recon_args(x, t, kinds, mask, beta, win, reduction, "recon_loss_fwd")
-    ws = torch.empty(max(1, lib.ctl_recon_ws_doubles(bits, n, h, w, c, int(win))), dtype=torch.float64, device=x.device)
-    loss = torch.empty(1 + len(RECON_KINDS), dtype=torch.float32, device=x.device)
+    ws, loss = _kinds_scratch("ctl_recon_ws_doubles", (bits, n, h, w, c, int(win)), RECON_KINDS, x.device)
     call("ctl_recon_loss_fwd", bits, weights, ptr(x), ptr(t), ptr(mask), tb, n, h, w, c, float(beta), int(win), int(bool(zero_mean)), rsum,
          ptr(ws), ptr(loss), stream_ptr())
     return loss[0], loss[1:], ws
@@ -517,10 +486,7 @@ def recon_loss_fwd(x, t, kinds, mask=None, beta=1.0 / 9, win=9, zero_mean=True, 
 def recon_loss_bwd(x, t, kinds, gout, ws, mask=None, beta=1.0 / 9, win=9, zero_mean=True, reduction="mean"):
     """gout (0-d fp32 device tensor) * d total / d x; `ws` is what recon_loss_fwd returned for the same arguments."""
     bits, weights, mask, tb, n, h, w, c, rsum = _recon_args(x, t, kinds, mask, beta, win, reduction, "recon_loss_bwd")
-    require_gpu(gout, ws)
-    _arg(ws, torch.float64, (None,), "recon_loss_bwd", "ws", dense=True)
-    if ws.numel() < lib.ctl_recon_ws_doubles(bits, n, h, w, c, int(win)):
-        raise ValueError("recon_loss_bwd: `ws` is not the scratch of recon_loss_fwd for these arguments")
+    _scratch_given(ws, gout, "ctl_recon_ws_doubles", (bits, n, h, w, c, int(win)), "recon_loss_bwd", "recon_loss_fwd")
     d = torch.empty_like(x)
     call("ctl_recon_loss_bwd", bits, weights, ptr(x), ptr(t), ptr(mask), tb, ptr(gout), ptr(ws), n, h, w, c, float(beta), int(win),
          int(bool(zero_mean)), rsum, ptr(d), stream_ptr())

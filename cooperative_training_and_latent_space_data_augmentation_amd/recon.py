@@ -44,9 +44,12 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .losses import MAX_CLASSES, check_mask, mask01
+from . import _ffi      # the kind constants only: the library itself is loaded by the first call into it
+from .losses import MAX_CLASSES, check_constant, check_mask, check_names, mask01
 
-RECON_NAMES = ("mse", "l1", "smooth l1", "ncc", "lncc")
+# the names (custom_loss.py:310-318, :514-571, :574-661) -> CTL_RECON_* bit; bit k is kind k, the order of the terms and of the weights
+RECON_KINDS = {"mse": _ffi.RECON_MSE, "l1": _ffi.RECON_L1, "smooth l1": _ffi.RECON_SMOOTH_L1, "ncc": _ffi.RECON_NCC, "lncc": _ffi.RECON_LNCC}
+RECON_NAMES = tuple(RECON_KINDS)
 MAX_CHANNELS = MAX_CLASSES
 EPS = 1e-6
 FLAT_RATIO, FLAG_LO, FLAG_HI = 2.0 ** -40, 2.0 ** -44, 2.0 ** -36
@@ -68,12 +71,11 @@ def parse_kinds(kinds, weights=None):
     else:
         names = list(kinds)
         weights = [1.0] * len(names) if weights is None else ([weights] if isinstance(weights, (int, float)) else list(weights))
-    if not names or len(names) != len(weights):
-        raise ValueError(f"kinds and weights: {len(names)} names, {len(weights)} weights (the same, positive number)")
+    if len(names) != len(weights):
+        raise ValueError(f"kinds and weights: {len(names)} names, {len(weights)} weights (the same number)")
+    check_names(names, RECON_KINDS, "image-similarity loss")
     out = {}
     for name, weight in zip(names, weights):
-        if name not in RECON_NAMES:
-            raise NotImplementedError(f"image-similarity loss {name!r} (one of {', '.join(RECON_NAMES)})")
         weight = float(weight)
         if weight != weight or weight in (float("inf"), float("-inf")):
             raise ValueError(f"the weight of {name!r} is {weight} (finite)")
@@ -81,27 +83,37 @@ def parse_kinds(kinds, weights=None):
     return out
 
 
-def check_params(names, shape, beta=1.0 / 9, win=9, reduction="mean"):
-    """ValueError for a parameter no kernel takes; `reduction='none'` is left to the callers that offer it."""
-    _, c, h, w = shape
-    if not 1 <= c <= MAX_CHANNELS:
-        raise ValueError(f"{c} channels (1 .. {MAX_CHANNELS})")
+def check_win(win):
+    if int(win) != win or win % 2 == 0 or not 3 <= win <= 15:
+        raise ValueError(f"win = {win} (the window size win_size: odd, 3 .. 15)")
+
+
+def check_params(names, beta=1.0 / 9, win=9, reduction="mean", device=False):
+    """ValueError for a parameter no kernel takes, of the kinds `names` only; checked before any tensor is looked at.  device: the
+    kernels do not offer reduction='none' (NotImplementedError), which only the CPU path of image_similarity takes."""
+    if device and reduction == "none":
+        raise NotImplementedError("reduction='none' is not offered on the device ('mean' or 'sum'; CPU tensors take 'none')")
     if reduction not in ("mean", "sum"):
         raise ValueError(f"reduction {reduction!r} ('mean' or 'sum')")
     if "smooth l1" in names and not float(beta) > 0.0:
         raise ValueError(f"beta = {beta} (smooth l1 needs beta > 0)")
     if "lncc" in names:
-        if int(win) != win or win % 2 == 0 or not 3 <= win <= 15:
-            raise ValueError(f"win = {win} (odd, 3 .. 15)")
-        if win > h or win > w:
-            raise ValueError(f"win = {win} is larger than the {h}x{w} plane (window size must not exceed the image dimension)")
+        check_win(win)
+
+
+def check_image(names, shape, win=9):
+    """ValueError for an image [B,C,H,W] the kernels do not take: its channel count, and a plane smaller than the window of 'lncc'."""
+    _, c, h, w = shape
+    if not 1 <= c <= MAX_CHANNELS:
+        raise ValueError(f"{c} channels (1 .. {MAX_CHANNELS})")
+    if "lncc" in names and (win > h or win > w):
+        raise ValueError(f"win = {win} is larger than the {h}x{w} plane (window size must not exceed the image dimension)")
 
 
 def check_pair(x, t, mask=None):
     if x.dim() != 4 or t.dim() != 4 or tuple(t.shape[1:]) != tuple(x.shape[1:]) or t.shape[0] not in (1, x.shape[0]):
         raise ValueError(f"expected a prediction [B,C,H,W] and a target of that shape or [1,C,H,W], got {tuple(x.shape)} and {tuple(t.shape)}")
-    if t.requires_grad:
-        raise ValueError("the target is a constant: detach it (no gradient reaches the target)")
+    check_constant(t, "target")
     check_mask(mask, x.shape)
 
 
@@ -140,30 +152,27 @@ def lncc_maps(I, J, win):
 
 
 def _one(name, I, J, m, beta, win, zero_mean, mean):
-    """(loss, dloss/dx, lncc maps or None) of one kind at unit weight; float64, I / J masked, m[B,1,H,W] of 0/1"""
+    """(loss, dloss/dx, lncc maps or None) of one kind at unit weight; float64, I / J masked, m[B,1,H,W] of 0/1.  The value of a pointwise
+    kind is `_value`, the function the CPU path differentiates; the gradient is the closed form of the module docstring."""
     b, c, h, w = J.shape
-    n_all = float(b * c * h * w)
     d = J - I
     if name in ("mse", "l1", "smooth l1"):
-        div = n_all if mean else 1.0
-        if name == "mse":
-            return (d * d).sum() / div, m * 2.0 * d / div, None
-        if name == "l1":
-            return d.abs().sum() / div, m * torch.sign(d) / div, None
-        n = d.abs()
-        val = torch.where(n < beta, 0.5 * n ** 2 / beta, n - 0.5 * beta)
-        return val.sum() / div, m * torch.where(n < beta, d / beta, torch.sign(d)) / div, None
+        div = float(b * c * h * w) if mean else 1.0
+        g = 2.0 * d if name == "mse" else torch.sign(d) if name == "l1" else torch.where(d.abs() < beta, d / beta, torch.sign(d))
+        return _value(name, I, J, beta, win, zero_mean, "mean" if mean else "sum"), m * g / div, None
     if name == "ncc":
         a, u = (J - J.mean((2, 3), keepdim=True), I - I.mean((2, 3), keepdim=True)) if zero_mean else (J, I)
         dot = (a * u).sum((1, 2, 3))
         na, nu = (a * a).sum((1, 2, 3)).sqrt(), (u * u).sum((1, 2, 3)).sqrt()
         Na, Nu = na.clamp_min(EPS), nu.clamp_min(EPS)
-        s = dot / (Na * Nu)
+        s = dot / (Na * Nu)             # its own statement: the norm() of `_ncc_scores_torch` rounds differently
         alpha = 1.0 / (Na * Nu)
         bet = torch.where(na > EPS, dot / (Na ** 3 * Nu), torch.zeros_like(dot))
         div = float(b) if mean else 1.0
         g = alpha.view(b, 1, 1, 1) * u - bet.view(b, 1, 1, 1) * a
         return 1.0 - s.sum() / div, -m * g / div, None
+    # 'lncc' keeps two statements of its value as well: box_sum in index order is the definition, the conv2d form of `_value` is the CPU
+    # path, and the two round differently
     mp = lncc_maps(I, J, win)
     a_p = 1.0 / mp["D"]
     b_p = torch.where(mp["flat_J"], torch.zeros_like(a_p),
@@ -178,8 +187,9 @@ def _one(name, I, J, m, beta, win, zero_mean, mean):
 def similarity_and_grad(x, t, kinds, weights=None, mask=None, *, beta=1.0 / 9, win=9, zero_mean=True, reduction="mean", gout=1.0):
     """The definition (module docstring): a `Similarity` of float64 CPU tensors, the gradient with respect to x in closed form."""
     terms = parse_kinds(kinds, weights)
+    check_params(terms, beta, win, reduction)
     check_pair(x, t, mask)
-    check_params(terms, x.shape, beta, win, reduction)
+    check_image(terms, x.shape, win)
     xd = x.detach().double().cpu()
     td = t.detach().double().cpu().expand_as(xd)
     m = mask01(None if mask is None else mask.cpu(), xd.shape, torch.float64, "cpu")
@@ -195,7 +205,7 @@ def similarity_and_grad(x, t, kinds, weights=None, mask=None, *, beta=1.0 / 9, w
     return Similarity(loss, grad * float(gout), values, grads, flagged, maps)
 
 
-# ---------------------------------------------------------------------------------------------- the same arithmetic from torch ops
+# ---------------------------------------------------------------------------------------------- the values from differentiable torch ops
 def _lncc_scores_torch(I, J, win):
     """score [B,1,H,W] from differentiable torch ops in J's dtype, the flat rule included (a flat variance: 0, and no gradient through it)"""
     A = float(win * win)
@@ -223,30 +233,32 @@ def _ncc_scores_torch(I, J, zero_mean):
     return (a * u).sum(1) / (torch.where(na > EPS, na, torch.full_like(na, EPS)) * nu.clamp_min(EPS))
 
 
+def _value(name, I, J, beta, win, zero_mean, reduction):
+    """One kind at unit weight between the masked target I and prediction J, in J's dtype; reduction 'none' gives its unreduced form."""
+    red = (lambda v: v.mean()) if reduction == "mean" else (lambda v: v.sum()) if reduction == "sum" else (lambda v: v)
+    d = J - I
+    if name == "mse":
+        return red(d * d)
+    if name == "l1":
+        return red(d.abs())
+    if name == "smooth l1":
+        n = d.abs()
+        return red(torch.where(n < beta, 0.5 * n ** 2 / beta, n - 0.5 * beta))
+    if name == "ncc":
+        s = _ncc_scores_torch(I, J, zero_mean)
+        return 1.0 - (s.sum() / float(J.shape[0]) if reduction == "mean" else s.sum() if reduction == "sum" else s)
+    return 1.0 - red(_lncc_scores_torch(I, J, win).expand(-1, J.shape[1], -1, -1))
+
+
 def _similarity_torch(x, t, terms, mask, beta, win, zero_mean, reduction):
     """The weighted total (or, reduction 'none' with a single kind, its unreduced form) from torch ops in x's float dtype."""
     x = x if x.is_floating_point() else x.float()
     t = t.detach().to(x.dtype).expand_as(x)
     m = mask01(mask, x.shape, x.dtype, x.device)
     I, J = t * m, x * m
-    red = (lambda v: v.mean()) if reduction == "mean" else (lambda v: v.sum()) if reduction == "sum" else (lambda v: v)
     total = 0.0
     for name, weight in terms.items():
-        d = J - I
-        if name == "mse":
-            val = red(d * d)
-        elif name == "l1":
-            val = red(d.abs())
-        elif name == "smooth l1":
-            n = d.abs()
-            val = red(torch.where(n < beta, 0.5 * n ** 2 / beta, n - 0.5 * beta))
-        elif name == "ncc":
-            s = _ncc_scores_torch(I, J, zero_mean)
-            val = 1.0 - (s.sum() / float(x.shape[0]) if reduction == "mean" else s.sum() if reduction == "sum" else s)
-        else:
-            s = _lncc_scores_torch(I, J, win).expand(-1, x.shape[1], -1, -1)
-            val = 1.0 - red(s)
-        total = total + weight * val
+        total = total + weight * _value(name, I, J, beta, win, zero_mean, reduction)
     return total
 
 
@@ -255,16 +267,16 @@ def image_similarity(x, t, kinds, weights=None, mask=None, *, beta=1.0 / 9, win=
     kernels (fp32); CPU tensors take the same arithmetic from torch ops in their own float dtype.  `reduction='none'` (one kind, CPU
     tensors only) returns the unreduced form; on the device it raises NotImplementedError."""
     terms = parse_kinds(kinds, weights)
-    check_pair(x, t, mask)
-    if reduction == "none":
-        if x.is_cuda or t.is_cuda:
-            raise NotImplementedError("reduction='none' is not offered on the device ('mean' or 'sum'; CPU tensors take 'none')")
+    device = x.is_cuda or t.is_cuda
+    if reduction == "none" and not device:
         if len(terms) != 1:
             raise ValueError("reduction='none' takes a single kind")
-        check_params(terms, x.shape, beta, win, "mean")
+        check_params(terms, beta, win, "mean")
     else:
-        check_params(terms, x.shape, beta, win, reduction)
-    if not (x.is_cuda or t.is_cuda):
+        check_params(terms, beta, win, reduction, device)
+    check_pair(x, t, mask)
+    check_image(terms, x.shape, win)
+    if not device:
         return _similarity_torch(x, t, terms, mask, float(beta), int(win), bool(zero_mean), reduction)
     from . import autograd
     return autograd.image_similarity_loss(x, t.detach(), terms, None, mask, beta=beta, win=win, zero_mean=zero_mean, reduction=reduction)
@@ -297,8 +309,7 @@ class CustomLocalNormalizedCrossCorrelationLoss(nn.Module):
         super().__init__()
         if reduction not in ("mean", "sum", "none"):
             raise NotImplementedError(f"reduction {reduction!r} ('mean', 'sum' or 'none')")
-        if int(win_size) != win_size or win_size % 2 == 0 or not 3 <= win_size <= 15:
-            raise ValueError(f"win_size = {win_size} (odd, 3 .. 15)")
+        check_win(win_size)
         self.use_gpu, self.epsilon, self.reduction, self.win_size = use_gpu, EPS, reduction, int(win_size)
 
     def forward(self, template, image, mask=None):

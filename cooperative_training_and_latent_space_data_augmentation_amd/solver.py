@@ -21,7 +21,8 @@ import torch.nn as nn
 
 from . import _ffi, ops
 from .autograd import LabelFields, cross_entropy_2D, image_similarity_loss, net_apply, scaled_mse, segmentation_loss, softmax_t, split_halves
-from .losses import DIST_LOSS_NAMES, parse_loss_type
+from . import losses
+from .losses import parse_loss_type
 from .metrics import runningScore
 from .model_util import (_disable_tracking_bn_stats, _draw_seed, get_scheduler, mask_latent_code_channel_wise,
                          mask_latent_code_spatial_wise, set_grad)
@@ -34,8 +35,7 @@ _DEFAULT_SEG_CFG = {"loss_name": "ce", "mask_type": "random", "max_threshold": 0
 
 def needs_fields(loss_type) -> bool:
     """Does the loss name or {name: weight} mapping contain a distance-map loss, i.e. read the class fields of the label?"""
-    names = loss_type if isinstance(loss_type, dict) else (loss_type,)
-    return any(n in DIST_LOSS_NAMES for n in names)
+    return bool(losses.needs_fields(loss_type))
 
 
 def basic_loss_fn(pred, target, loss_type="cross entropy", class_weights=None, use_gpu=True, fields=None):
@@ -50,7 +50,7 @@ def basic_loss_fn(pred, target, loss_type="cross entropy", class_weights=None, u
         return cross_entropy_2D(pred, target)
     terms, class_weights = parse_loss_type(loss_type, class_weights, pred.size(1))
     total = None
-    if fields is None and any(name in DIST_LOSS_NAMES for name, _ in terms):
+    if fields is None and needs_fields(loss_type):
         ops.require_gpu(pred, target)
         fields = LabelFields(target, pred.size(1))
     for name, weight in terms:
@@ -467,13 +467,14 @@ class AdvancedTripletReconSegmentationModel(nn.Module):
     @staticmethod
     def _parse_recon(recon_loss_type, recon_loss_params, image_ch):
         """(type, params, {name: 0.5 * weight} or None for the default scaled_mse call); NotImplementedError / ValueError as recon.py raises."""
-        from .recon import check_params, parse_kinds
+        from .recon import check_image, check_params, parse_kinds
         params = dict(recon_loss_params or {})
         unknown = sorted(set(params) - {"beta", "win", "zero_mean", "reduction"})
         if unknown:
             raise ValueError(f"recon_loss_params: unknown parameter(s) {unknown} (beta, win, zero_mean, reduction)")
         kinds = parse_kinds(recon_loss_type)
-        check_params(kinds, (1, image_ch, 15, 15), params.get("beta", 1.0 / 9), params.get("win", 9), params.get("reduction", "mean"))
+        check_params(kinds, params.get("beta", 1.0 / 9), params.get("win", 9), params.get("reduction", "mean"))
+        check_image(kinds, (1, image_ch, 15, 15))
         rtype = dict(recon_loss_type) if isinstance(recon_loss_type, dict) else recon_loss_type
         if recon_loss_type == "mse" and not params:
             return rtype, params, None

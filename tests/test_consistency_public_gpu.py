@@ -10,7 +10,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import ref_cpu as O  # noqa: E402
 from cooperative_training_and_latent_space_data_augmentation_amd import autograd, consistency as K, ops  # noqa: E402
-from cooperative_training_and_latent_space_data_augmentation_amd.solver import AdvancedTripletReconSegmentationModel  # noqa: E402
+from cooperative_training_and_latent_space_data_augmentation_amd.solver import AdvancedTripletReconSegmentationModel, basic_loss_fn  # noqa: E402
 from test_consistency_gpu import U, kind_bounds  # noqa: E402
 
 DEV = "cuda"
@@ -82,6 +82,29 @@ def test_wrappers_are_the_special_cases():
         K.calc_segmentation_consistency(x, r.clone().requires_grad_(True))
     with pytest.raises(ValueError, match="mask"):
         K.calc_segmentation_consistency(x, r, scales=[0, 1], mask=mask)
+    # the rules that only device tensors reach: every layer that takes the argument states them in the same words
+    x8, r8 = pair(2, 4, 8, 8, seed=7)
+    one, ws = torch.ones((), device=DEV), torch.zeros(64, dtype=torch.float64, device=DEV)
+    kl = {"kl": 1.0}
+    for bad in (torch.ones(2, 2, 8, 8, device=DEV), torch.ones(1, 1, 8, 8, device=DEV), torch.ones(2, 8, 7, device=DEV)):
+        for fn in (lambda: K.calc_segmentation_consistency(x8, r8, mask=bad), lambda: autograd.consistency_loss(x8, r8, kl, mask=bad),
+                   lambda: ops.consistency_fwd(x8, r8, kl, mask=bad), lambda: ops.consistency_bwd(x8, r8, kl, one, ws, mask=bad)):
+            with pytest.raises(ValueError, match=r"the mask is per pixel: \[2,1,8,8\] or \[2,8,8\]"):
+                fn()
+    x1, r1 = pair(2, 1, 8, 8, seed=8)
+    y1, contour = torch.zeros(2, 8, 8, dtype=torch.long, device=DEV), {"contour": 1.0}
+    for name, fns in (("contour", (lambda: K.calc_segmentation_consistency(x1, r1, ["contour"], [1.0]), lambda: autograd.consistency_loss(x1, r1, contour),
+                                   lambda: ops.consistency_fwd(x1, r1, contour), lambda: ops.consistency_bwd(x1, r1, contour, one, ws))),
+                      ("boundary", (lambda: basic_loss_fn(x1, y1, "boundary"), lambda: autograd.segmentation_loss(x1, y1, "boundary"),
+                                    lambda: ops.dist_loss_fwd(x1, y1, "boundary", x1), lambda: ops.dist_loss_bwd(x1, y1, "boundary", one, x1))),
+                      ("hausdorff dt", (lambda: autograd.segmentation_loss(x1, y1, "hausdorff dt"), lambda: ops.dist_loss_fwd(x1, y1, "hausdorff dt", x1, x1)))):
+        for fn in fns:
+            with pytest.raises(ValueError, match=f"'{name}' needs at least 2 classes"):
+                fn()
+    xs, rs = pair(2, 1, 2, 2, seed=9)
+    for fn in (lambda: K.calc_segmentation_consistency(xs, rs, ["mse"], [1.0], scales=[2]), lambda: autograd.avg_pool(xs, 2), lambda: ops.avgpool_fwd(xs, 2)):
+        with pytest.raises(ValueError, match="a 2x2 plane is smaller than the 4x4 window of scale 2"):
+            fn()
 
 
 def test_recorded_upstream_cases_on_the_device():

@@ -81,6 +81,21 @@ def test_public_entries_give_the_bits_of_the_ops_calls():
         autograd.image_similarity_loss(x, t.clone().requires_grad_(True), "mse")
     with pytest.raises(ValueError, match="win"):
         autograd.image_similarity_loss(x, t, "lncc", win=21)
+    # the rules that only device tensors reach: every layer that takes the argument states them in the same words
+    ws, mse, lncc = torch.zeros(64, dtype=torch.float64, device=DEV), {"mse": 1.0}, {"lncc": 1.0}
+    x8, t8, _ = _pair(2, 1, 8, 8, 2)
+    for bad in (torch.ones(2, 2, 8, 8, device=DEV), torch.ones(1, 1, 8, 8, device=DEV), torch.ones(2, 8, 7, device=DEV)):
+        for fn in (lambda: recon.image_similarity(x8, t8, mse, mask=bad), lambda: autograd.image_similarity_loss(x8, t8, mse, mask=bad),
+                   lambda: ops.recon_loss_fwd(x8, t8, mse, mask=bad), lambda: ops.recon_loss_bwd(x8, t8, mse, one, ws, mask=bad)):
+            with pytest.raises(ValueError, match=r"the mask is per pixel: \[2,1,8,8\] or \[2,8,8\]"):
+                fn()
+    x2, t2, _ = _pair(2, 1, 2, 2, 3)
+    for (xx, tt), win, plane in (((x8, t8), 9, "8x8"), ((x2, t2), 3, "2x2")):
+        for fn in (lambda: recon.image_similarity(xx, tt, lncc, win=win), lambda: autograd.image_similarity_loss(xx, tt, lncc, win=win),
+                   lambda: ops.recon_loss_fwd(xx, tt, lncc, win=win), lambda: ops.recon_loss_bwd(xx, tt, lncc, one, ws, win=win),
+                   lambda: recon.CustomLocalNormalizedCrossCorrelationLoss(win_size=win)(tt, xx)):
+            with pytest.raises(ValueError, match=f"win = {win} is larger than the {plane} plane"):
+                fn()
 
 
 def test_recorded_upstream_cases_on_the_device():
